@@ -1,7 +1,13 @@
 """bench.py -- EM iterations/s of the PPLS_simult inner loop on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|...] [--no-cpu]
-                    [--comm rccl|host] [--oversubscribe] [--xprod-steps K] [--no-call]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|...] [--dump-outputs DIR]
+                    [--comm rccl|host] [--oversubscribe]
+                    [--full [--no-cpu] [--xprod-steps K] [--no-call]]
+
+A plain run does what the headline figure needs and no more: it generates the data, warms up, times
+K steps, writes the estimates the timed iterations ended on (--dump-outputs DIR: DIR/<name>.npy,
+float64; data, theta0 and therefore these arrays are the same from run to run) and prints the result
+line.  --full adds the sections described at the end of this text.
 
 One "step" = one EM iteration = sweep over X, Y (E-step sufficient statistics + log-likelihood of
 the current theta) + deterministic reduction + [RCCL all-reduce] + finalize (M-step incl. polar
@@ -11,7 +17,8 @@ normals) generated on the device before the timed region.  Rank 0 prints ONE JSO
 the ranks disagree (theta digests, RCCL's own rank count, a non-finite log-likelihood), nothing on
 stdout, the reason on stderr and exit status 3.
 
-Beside the headline: the cross-product form of the same iterations ("xprod"), and the whole
+With --full, beside the headline: the CPU baseline and its parity figures (unless --no-cpu), the
+cross-product form of the same iterations ("xprod"), and the whole
 user-facing call PPLS_simult(X, Y, r) with its defaults ("call": the 'random' PPLS(X, Y, r, 20,
 1e-4) initialiser, EMsteps = 10, atol = 1e-4, Expectations) under each statistics path, with the
 C restatement of the same call timed on a row sample of the host.
@@ -500,6 +507,16 @@ def _theta_arrays(est, ll):
     return [est.W, est.C, est.B, est.sigT, np.array([est.sigE, est.sigF, est.sigH]), ll]
 
 
+def dump_outputs(outdir, est, ll):
+    """What a caller of the timed path receives after its last step (ppls_em_state): the estimates
+    and the log-likelihood trace of the warm-up + timed iterations, one float64 .npy each (C3: 160 kB
+    in all)."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = dict(W=est.W, C=est.C, B=est.B, sigT=est.sigT, sig=np.array([est.sigE, est.sigF, est.sigH]), loglik=ll)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -507,6 +524,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--sweep", type=int, default=0, help="0 auto, 3 panel")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the estimates and the log-likelihood trace they ended on "
+                         "as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the CPU baseline and its parity check, the cross-product "
+                         "form and the whole-call timings (the options below choose among them)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--cpu-iters", type=int, default=3, help="timed CPU-baseline iterations (full n)")
     ap.add_argument("--cpu-call-rows", type=int, default=0,
@@ -525,6 +548,9 @@ def main():
     ap.add_argument("--oversubscribe", action="store_true",
                     help="with --comm host: allow more ranks than visible GPUs (rank r on GPU r % count)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        print("error: --steps must be at least 1 and --warmup at least 0", file=sys.stderr)
+        return 2
     if args.oversubscribe and args.comm != "host":
         print("error: --oversubscribe needs --comm host (RCCL refuses two ranks on one GPU)", file=sys.stderr)
         return 2
@@ -606,15 +632,17 @@ def main():
     info = ctx.sweep_info(r)
     rccl_nranks, rccl_rank, ar_ms, ar_calls = ctx.comm_info(reset=True)
     digest_parts = _theta_arrays(est, ll)
+    if args.dump_outputs and rank == 0:   # every rank holds the same estimates (the digests below)
+        dump_outputs(args.dump_outputs, est, ll)
     xp = None
-    if args.xprod_steps > 0:
+    if args.full and args.xprod_steps > 0:
         MARK.push("xprod")
         est_x, ll_x, xp = bench_xprod(ctx, th0, args, barrier, tmax, r, ll, dt / args.steps)
         MARK.pop()
         digest_parts += _theta_arrays(est_x, ll_x)
         ctx.set_option("xprod", 0)
     call = None
-    if not args.no_call:
+    if args.full and not args.no_call:
         MARK.push("call")
         call = bench_call(ctx, r, barrier, tmax)
         MARK.pop()
@@ -648,7 +676,7 @@ def main():
         problems.append(f"ranks hold different estimates (theta digests {digests})")
     if backend == "rccl" and rccl_nranks != world:
         problems.append(f"RCCL reports {rccl_nranks} ranks for a world of {world}")
-    if not (len(ll) and np.isfinite(ll).all()):
+    if not np.isfinite(ll).all():   # (the trace is empty after a single iteration: --steps 1 --warmup 0)
         problems.append("non-finite log-likelihood")
     if problems:
         if rank == 0:
@@ -742,7 +770,7 @@ def main():
             out["call"] = dict(what=f"PPLS_simult(X, Y, {r}) with its defaults: PPLS(X, Y, {r}, 20, 1e-4, 'random') "
                                     "initialiser, EMsteps 10, atol 1e-4, Expectations to the host; S formed inside "
                                     "the xprod / auto calls", **call)
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             MARK.push("cpu_baseline")
             cb, rel, werr = cpu_baseline(ctx, th0, cfg, args.cpu_iters)
             MARK.pop()

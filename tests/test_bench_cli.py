@@ -18,6 +18,11 @@ def test_oversubscribe_needs_host_comm():
     assert pr.returncode == 2 and "--comm host" in pr.stderr and pr.stdout == ""
 
 
+def test_zero_timed_steps_is_refused():
+    pr = _run("--gpus", "1", "--steps", "0")
+    assert pr.returncode == 2 and "--steps" in pr.stderr and pr.stdout == ""
+
+
 def test_more_ranks_than_gpus_is_refused():
     # no GPU here: 0 visible devices, so even one rank per GPU cannot be honoured
     pr = _run("--gpus", "2", "--comm", "host")

@@ -18,13 +18,13 @@ from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
-ARGS = ["--config", "c4s", "--steps", "10", "--xprod-steps", "50", "--no-cpu"]
+ARGS = ["--config", "c4s", "--steps", "10", "--full", "--xprod-steps", "50", "--no-cpu"]
 
 
-def _bench(extra, env_extra=None, timeout=300):
+def _bench(extra, env_extra=None, timeout=300, args=ARGS):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE")}
     env.update(env_extra or {})
-    pr = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), *extra, *ARGS], cwd=ROOT, env=env,
+    pr = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), *extra, *args], cwd=ROOT, env=env,
                         capture_output=True, text=True, timeout=timeout)
     lines = [ln for ln in pr.stdout.splitlines() if ln.startswith("{")]
     return pr, (json.loads(lines[-1]) if lines else None)
@@ -70,3 +70,23 @@ def test_bench_diverging_ranks_fail_loudly():
     assert pr.returncode == 3, (pr.returncode, pr.stderr[-2000:])
     assert line is None   # no value printed
     assert "ranks hold different estimates" in pr.stderr
+
+
+def test_plain_run_times_only_the_headline_and_dumps_its_outputs(tmp_path):
+    """Without --full: the asked number of timed steps, no section beyond the headline, and
+    --dump-outputs leaves what ppls_em_state returned after the last timed step (float64 .npy)."""
+    import numpy as np
+    d = tmp_path / "out"
+    pr, line = _bench(["--gpus", "1", "--dump-outputs", str(d)], args=["--config", "c2", "--steps", "7", "--warmup", "2"])
+    assert pr.returncode == 0, pr.stderr[-3000:]
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["ms_per_step"] > 0
+    assert abs(line["value"] * line["ms_per_step"] - 1e3) < 1e-6
+    assert line["xprod"] is None and line["cpu_baseline"] is None
+    assert not {"call", "call_seconds", "loglik_rel_err_vs_cpu", "W_abs_err_vs_cpu"} & set(line)
+    shapes = dict(W=(1000, 3), C=(1000, 3), B=(3,), sigT=(3,), sig=(3,), loglik=(2 + 7 - 1,))
+    assert sorted(os.listdir(d)) == sorted(f"{k}.npy" for k in shapes)
+    got = {k: np.load(d / f"{k}.npy") for k in shapes}
+    for k, a in got.items():
+        assert a.dtype == np.float64 and a.shape == shapes[k] and np.isfinite(a).all(), k
+    assert got["loglik"][-1] == line["loglik_last"]
+    assert np.abs(got["W"].T @ got["W"] - np.eye(3)).max() < 1e-10   # loadings: orthonormal columns

@@ -4,6 +4,7 @@
 # usage: tools/pmc_compute.sh <tag> <bench args...>      (summary: tools/pmc_compute_summary.py <tag>)
 set -o pipefail
 tag="$1"; shift
+set -- --full "$@"   # the Gram and xprod kernels run in bench.py's --full sections
 R="${GRAFT_REPO_ROOT:-$(pwd)}"
 cd /tmp && export TMPDIR=/tmp
 P1="GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_INSTS_VALU_MFMA_F64 SQ_INSTS_VALU"

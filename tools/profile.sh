@@ -3,6 +3,7 @@
 # (never combined with other trace domains).  usage: tools/profile.sh <tag> <bench args...>
 set -o pipefail
 tag="$1"; shift
+set -- --full "$@"   # the xprod (and call) sections are profiled in the same command
 R="${GRAFT_REPO_ROOT:-$(pwd)}"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/gpurun_out/prof_$tag/trace" -o run \

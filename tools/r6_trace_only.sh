@@ -9,7 +9,7 @@ R="${GRAFT_REPO_ROOT:-$(pwd)}"
 O="$R/gpurun_out/r6_profiles"
 mkdir -p "$O"
 T="$R/gpurun_out/prof_$tag"
-cmd=(python3 "$R/bench.py" --gpus 1 "$@")
+cmd=(python3 "$R/bench.py" --gpus 1 --full "$@")
 (cd /tmp && export TMPDIR=/tmp && PPLS_ROCTX=1 timeout -k 10 600 rocprofv3 --kernel-trace --marker-trace --stats \
    --output-format csv -d "$T/trace" -o run -- "${cmd[@]}" > "$O/${tag}_bench_line.log" 2> "$O/${tag}_trace_stderr.log") || exit $?
 cd "$R" || exit 1
