@@ -280,6 +280,69 @@ int ppls_xprod_prepare(ppls_ctx* ctx, double* ms, double* total_ms);
  * residue planes stay: see option "gram_int8".) */
 int ppls_xprod_release(ppls_ctx* ctx);
 
+/* ---- cross-validation: predict.PPLS, cv_PPLS, crossval_PPLS ----------------------------------
+ * Package/PPLS/R/crossval_PPLS.R:12-114.  The reference refits on X[-folds[ii], ], Y[-folds[ii], ]
+ * (:48), copied from R into Eigen on every EM step; here a fold's training rows are gathered on the
+ * device, their cross-products are S - S_fold, and the held-out rows are scored where they lie. */
+
+/* X[rows, ], Y[rows, ] of src into dst, on the device (replaces the row subsetting of :48 and the
+ * upload of its result).  rows: nrows strictly ascending local row indices into src's resident
+ * data; dst then holds those rows in that order as if ppls_set_data had been called with them: src's
+ * storage dtype, dst's own padded layout with zeroed slack, ||X||^2 and ||Y||^2 recomputed and
+ * all-reduced, the non-finite verdict, a stale S dropped.  n_total: the subset's rows over all ranks
+ * (<= 0: nrows).  With shards each rank passes its own rows; a rank with nrows = 0 still joins the
+ * collectives.  PPLS_E_ARG: an index out of range or not ascending, dst == src, src without data,
+ * contexts on different devices. */
+int ppls_set_data_from(ppls_ctx* dst, ppls_ctx* src, const int64_t* rows, int64_t nrows, int64_t n_total);
+
+/* dst's cross-products as src's minus the Gram of src's rows out_rows (n_out strictly ascending
+ * local indices), marked ready as by ppls_xprod_prepare; src's S is formed first if it is not ready.
+ * The caller guarantees that dst's data are src's rows without out_rows (what ppls_set_data_from
+ * loaded); the row counts are checked, on this rank and over all ranks, and a mismatch is
+ * PPLS_E_ARG on every rank.  Entrywise S - S_out carries the rounding of the Gram of all rows,
+ * u sum_i |x_ij x_il| over all of them: at most K / (K - 1) times the bound of a direct Gram of the
+ * training rows when 1 / K of the rows are held out.  More rows held out than kept (over all ranks)
+ * is refused with PPLS_E_ARG: form S directly then.  Collective when the rows are sharded (the
+ * ranks first agree that every allocation succeeded, then all-reduce the held-out Gram).  Replaces
+ * the K re-reads of X[-fold, ] per EM step behind :48. */
+int ppls_xprod_downdate(ppls_ctx* dst, ppls_ctx* src, const int64_t* out_rows, int64_t n_out);
+
+/* predict.PPLS (:12-24): xory 0 ("X") pred = newdata W diag(B) C' (n x q), xory 1 ("Y") pred =
+ * newdata C diag(1/B) W' (n x p); W p x k, C q x k column-major, B k, with p, q the shape of the
+ * data last loaded into ctx (newdata itself is independent of the resident rows: it is streamed
+ * through a device staging buffer in row blocks, in fp64 whatever the storage dtype).  newdata:
+ * n x p (or n x q) host matrix in `layout`; pred: column-major.  The column-count check of :16-17 is
+ * the caller's. */
+int ppls_predict(ppls_ctx* ctx, const double* W, const double* C, const double* B, int k, int xory,
+                 const double* newdata, int64_t n, int layout, double* pred);
+
+/* The held-out error of :49 for every number of components at once, on the resident rows `rows`
+ * (nrows strictly ascending local indices): with yhat_i(j) = sum_{m <= j} (x_i w_m) B_m c_m,
+ * sse[j-1] = sum_i ||y_i - yhat_i(j)||^2 for j = 1..k, all-reduced over ranks.  One pass over X and Y
+ * of those rows (fp64 arithmetic on either storage dtype), the residual formed directly, fixed-order
+ * sums.  A rank with nrows = 0 still joins the all-reduce. */
+int ppls_heldout_sse(ppls_ctx* ctx, const double* W, const double* C, const double* B, int k,
+                     const int64_t* rows, int64_t nrows, double* sse /* k values */);
+
+/* cv_PPLS's loop (:40-52) for given folds.  fold_of_row: the fold (0..nfolds-1) of each of this
+ * rank's rows; fold_total: rows per fold over all ranks; init: nfolds x a starting values (fold f's
+ * are init[f*a .. f*a+a), as for ppls_ppls).  Per fold: the other rows, in their order (R's
+ * X[-folds[ii], ] keeps it), go into a training context the library creates once and reuses
+ * (ppls_set_data_from; ctx's options xprod, dtype, gram_int8 and its reducer / communicator carry
+ * over); if the fits read S it comes from ppls_xprod_downdate; ppls_ppls_ex fits a components;
+ * ppls_heldout_sse scores the fold's rows in ctx.
+ *   rmsep[f*a + j] = sqrt(sse_j / (fold_total[f] q))        (nfolds x a, fold-major)
+ * is sqrt(mse(Y[fold, ], predict(fit, X[fold, ], "X"))) of :49 for the (j+1)-component fit -- PPLS is
+ * sequential, so components 1..j of an a-component fit are the j-component fit, and one fit per fold
+ * gives every prefix.  mse is OmicsPLS's, mse(x, y) = mean((x - y)^2); OmicsPLS is not vendored with
+ * the reference, so that definition, and with it parity against an R run, is unpinned.  A fold whose
+ * fit stops early (ncomp[f] < a, the rank-collapse rule of :258-263) gets NaN for the components it
+ * did not reach. */
+int ppls_cv_ppls(ppls_ctx* ctx, int a, int nfolds, const int32_t* fold_of_row /* n_local, 0..nfolds-1 */,
+                 const int64_t* fold_total /* nfolds: rows per fold over all ranks */,
+                 int max_steps, double atol, int crit_abs, const ppls_theta* init /* nfolds x a */,
+                 double* rmsep /* nfolds x a, fold-major */, int* ncomp /* nfolds */);
+
 /* ---- host-side algebra (no GPU; the same code the device finalize runs) ------------------------ */
 /* From the all-reduced sufficient statistics of one sweep with theta (stats = [X'mu_T p x r |
  * Y'mu_U q x r | Gram 2r x 2r], all column-major) compute Expect_M's moments, logl_W(theta) and

@@ -91,6 +91,13 @@ int ppls_finalize_trace(ppls_ctx* ctx, int64_t* stamps, double* tick_ns);
  * workgroups copied.  Requires set_option("strace", 1). */
 #define PPLS_STRACE_MAX_WG 4096
 int ppls_sweep_trace(ppls_ctx* ctx, int64_t* stamps, int cap, int* n, double* tick_ns);
+/* The cross-validation calls on ctx since the last reset (ppls_set_data_from and
+ * ppls_xprod_downdate with ctx as the source, ppls_heldout_sse and ppls_cv_ppls on ctx):
+ * out6 = {row gathers (HIP events), held-out Gram + downdate incl. its all-reduce (wall clock, the
+ * gather taken out), the fits of ppls_cv_ppls (wall clock: a host-driven loop), scoring kernel and
+ * its reduction (HIP events)} in ms, then the bytes the gathers read + wrote and the bytes the
+ * scoring kernel read. */
+int ppls_cv_timing(ppls_ctx* ctx, double* out6, int reset);
 
 #ifdef __cplusplus
 }

@@ -130,6 +130,13 @@ SIGNATURES = {
                                       ct.c_int, ct.c_int, ct.POINTER(PplsTheta), ct.c_int,
                                       ct.POINTER(PplsTheta), ct.POINTER(PplsExpect), _dp]),
     "ppls_mu_coefficients": (ct.c_int, [ct.POINTER(PplsTheta), ct.c_int, _dp]),
+    "ppls_set_data_from": (ct.c_int, [ct.c_void_p, ct.c_void_p, _i64p, ct.c_int64, ct.c_int64]),
+    "ppls_xprod_downdate": (ct.c_int, [ct.c_void_p, ct.c_void_p, _i64p, ct.c_int64]),
+    "ppls_predict": (ct.c_int, [ct.c_void_p, _dp, _dp, _dp, ct.c_int, ct.c_int, _dp, ct.c_int64, ct.c_int, _dp]),
+    "ppls_heldout_sse": (ct.c_int, [ct.c_void_p, _dp, _dp, _dp, ct.c_int, _i64p, ct.c_int64, _dp]),
+    "ppls_cv_ppls": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(ct.c_int32), _i64p, ct.c_int,
+                                ct.c_double, ct.c_int, ct.POINTER(PplsTheta), _dp, ct.POINTER(ct.c_int)]),
+    "ppls_cv_timing": (ct.c_int, [ct.c_void_p, _dp, ct.c_int]),
 }
 
 

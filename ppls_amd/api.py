@@ -465,6 +465,101 @@ class Context:
         self._chk(self._L.ppls_scores(self.h, dptr(W), dptr(C), int(k), dptr(T), dptr(U)))
         return T, U
 
+    # -- cross-validation (crossval_PPLS.R:12-114)
+    @staticmethod
+    def _rows(rows):
+        rows = np.ascontiguousarray(np.ravel(np.asarray(rows, dtype=np.int64)))
+        return rows, rows.ctypes.data_as(_lib._i64p)
+
+    def set_data_from(self, src: "Context", rows, n_total=None):
+        """This context's data := rows ``rows`` (ascending local indices) of ``src``'s resident
+        data, gathered on the device (ppls_set_data_from).  ``n_total``: the subset's rows over
+        all ranks (default: ``len(rows)``)."""
+        rows, rp = self._rows(rows)
+        nt = rows.shape[0] if n_total is None else int(n_total)
+        self._chk(self._L.ppls_set_data_from(self.h, src.h, rp, rows.shape[0], nt))
+        self.p, self.q, self.n_local, self.n_total, self.row0 = src.p, src.q, rows.shape[0], nt, 0
+
+    def xprod_downdate(self, src: "Context", out_rows):
+        """This context's cross-products S := ``src``'s S minus the Gram of ``src``'s rows
+        ``out_rows`` (ppls_xprod_downdate); this context must hold ``src``'s other rows."""
+        rows, rp = self._rows(out_rows)
+        self._chk(self._L.ppls_xprod_downdate(self.h, src.h, rp, rows.shape[0]))
+
+    @staticmethod
+    def _fit_arrays(W, C, B):
+        W = np.asfortranarray(np.array(W, dtype=np.float64, ndmin=2))
+        C = np.asfortranarray(np.array(C, dtype=np.float64, ndmin=2))
+        B = np.asarray(B, dtype=np.float64)
+        B = np.ascontiguousarray(np.diag(B) if B.ndim == 2 else np.ravel(B)).copy()
+        if W.shape[1] != C.shape[1] or B.shape[0] != W.shape[1]:
+            raise ValueError("W, C and B need the same number of components")
+        return W, C, B
+
+    def predict(self, W, C, B, newdata, xory=0):
+        """predict.PPLS (crossval_PPLS.R:12-24) for a host matrix ``newdata``: xory 0 gives
+        newdata W diag(B) C', xory 1 newdata C diag(1/B) W' (ppls_predict).  The context supplies the
+        device and the shape (p, q) of its data; ``newdata`` is independent of the resident rows."""
+        W, C, B = self._fit_arrays(W, C, B)
+        if W.shape[0] != self.p or C.shape[0] != self.q:
+            raise ValueError(f"the fit is {W.shape[0]} x {C.shape[0]}, the context's data {self.p} x {self.q}")
+        nd = np.asarray(newdata, dtype=np.float64)
+        if nd.ndim != 2 or nd.shape[1] != (self.q if xory else self.p):
+            raise ValueError("Number of columns mismatch!")
+        if nd.flags.f_contiguous and not nd.flags.c_contiguous:
+            layout = _lib.PPLS_LAYOUT_COLMAJOR
+        else:
+            nd = np.ascontiguousarray(nd)
+            layout = _lib.PPLS_LAYOUT_ROWMAJOR
+        pred = np.zeros((nd.shape[0], self.p if xory else self.q), order="F")
+        self._chk(self._L.ppls_predict(self.h, dptr(W), dptr(C), dptr(B), W.shape[1], int(xory), dptr(nd),
+                                       nd.shape[0], layout, dptr(pred)))
+        return pred
+
+    def heldout_sse(self, W, C, B, rows):
+        """sum_i ||y_i - yhat_i(j)||^2 over the resident rows ``rows`` for every prefix j = 1..k of
+        the components, summed over ranks (ppls_heldout_sse): k values."""
+        W, C, B = self._fit_arrays(W, C, B)
+        if W.shape[0] != self.p or C.shape[0] != self.q:
+            raise ValueError(f"the fit is {W.shape[0]} x {C.shape[0]}, the context's data {self.p} x {self.q}")
+        rows, rp = self._rows(rows)
+        sse = np.zeros(W.shape[1])
+        self._chk(self._L.ppls_heldout_sse(self.h, dptr(W), dptr(C), dptr(B), W.shape[1], rp, rows.shape[0],
+                                           dptr(sse)))
+        return sse
+
+    def cv_ppls(self, a: int, fold_of_row, fold_total, max_steps: int, atol: float, inits, crit_abs=False):
+        """cv_PPLS's loop for given folds (ppls_cv_ppls).  ``fold_of_row``: the fold of each local
+        row; ``fold_total``: rows per fold over all ranks; ``inits``: per fold a list of ``a``
+        starting values (dicts as for ``ppls``).  Returns (rmsep nfolds x a, ncomp nfolds): the RMSEP
+        of every prefix of the components, NaN past a fold's ncomp."""
+        p, q = self.p, self.q
+        fold_of_row = np.ascontiguousarray(np.ravel(np.asarray(fold_of_row, dtype=np.int32)))
+        fold_total = np.ascontiguousarray(np.ravel(np.asarray(fold_total, dtype=np.int64)))
+        K = fold_total.shape[0]
+        if fold_of_row.shape[0] != self.n_local:
+            raise ValueError(f"{fold_of_row.shape[0]} fold labels for {self.n_local} local rows")
+        if len(inits) != K or any(len(f) != a for f in inits):
+            raise ValueError(f"starting values: one list of {a} per fold ({K} folds)")
+        ths = [Theta(np.reshape(t["W"], (p, 1)), np.reshape(t["C"], (q, 1)), float(np.ravel(t["B"])[0]),
+                     t["sigE"], t["sigF"], t["sigH"], float(np.ravel(t["sigT"])[0])) for f in inits for t in f]
+        arr = (_lib.PplsTheta * (K * a))(*[t.struct() for t in ths])
+        rmsep = np.full((K, a), np.nan)
+        ncomp = np.zeros(K, dtype=np.int32)
+        self._chk(self._L.ppls_cv_ppls(self.h, int(a), int(K), fold_of_row.ctypes.data_as(ct.POINTER(ct.c_int32)),
+                                       fold_total.ctypes.data_as(_lib._i64p), int(max_steps), float(atol),
+                                       int(bool(crit_abs)), arr, dptr(rmsep), ncomp.ctypes.data_as(ct.POINTER(ct.c_int))))
+        return rmsep, ncomp
+
+    def cv_timing(self, reset=True):
+        """Phases of the cross-validation calls on this context since the last reset
+        (ppls_cv_timing): ms of the row gathers, the held-out Gram + downdate, the fits and the
+        scoring kernel, and the bytes the gathers and the scoring kernel moved."""
+        out = np.zeros(6)
+        self._chk(self._L.ppls_cv_timing(self.h, dptr(out), int(bool(reset))))
+        return dict(gather_ms=out[0], downdate_ms=out[1], fit_ms=out[2], score_ms=out[3], gather_bytes=out[4],
+                    score_bytes=out[5])
+
     def synchronize(self):
         self._chk(self._L.ppls_synchronize(self.h))
 
@@ -1141,4 +1236,193 @@ def PPLS_simult(X, Y, a, EMsteps=10, atol=1e-4, type=("SVD", "QR"), init=None, c
     out["class"] = "PPLS_simult"
     if timings is not None:
         timings.update(init=t1 - t0, loop=time.perf_counter() - t1, init_steps=init_steps)
+    return out
+
+
+# ---------------------------------------------------------------------------- cross-validation
+# predict.PPLS, cv_PPLS, crossval_PPLS (Package/PPLS/R/crossval_PPLS.R:12-114).  Two statements below
+# rest on no R run: mse(x, y) = mean((x - y)^2) is OmicsPLS's (not vendored with the reference), and
+# cv_blocks restates base R's cut.default.
+
+def cv_blocks(N, K):
+    """R's ``as.numeric(cut(seq(1:N), breaks=K, labels=F))`` (crossval_PPLS.R:43) restated from
+    cut.default: K equal-width intervals over [1, N] (breaks seq(1, N, length.out = K + 1)), the two
+    ends moved out by (N - 1) / 1000, intervals right-closed.  Returns the 1-based block label of
+    1..N (non-decreasing); N = 10, K = 3 gives sizes 4, 3, 3."""
+    N, K = int(N), int(K)
+    if N < 1 or K < 1:
+        raise ValueError("cv_blocks needs N >= 1 and K >= 1")
+    dx = float(N - 1)
+    if dx == 0.0:      # cut.default's constant-x branch: dx = |x|, breaks over [x - dx/1000, x + dx/1000]
+        breaks = np.linspace(1.0 - 1e-3, 1.0 + 1e-3, K + 1)
+    else:
+        breaks = 1.0 + np.arange(K + 1) * (dx / K)
+        breaks[-1] = float(N)
+        breaks[0] -= dx / 1000
+        breaks[-1] += dx / 1000
+    return np.searchsorted(breaks, np.arange(1, N + 1, dtype=np.float64), side="left").astype(np.int64)
+
+
+_PREDICT_CTX = None
+
+
+def _fit_parts(obj):
+    est = obj.get("estimates", obj)
+    W = np.array(est["W"], dtype=np.float64, ndmin=2)
+    C = np.array(est["C"], dtype=np.float64, ndmin=2)
+    return W, C, est["B"]
+
+
+def predict_PPLS(object, newdata, XorY=("X", "Y"), ctx=None):
+    """predict.PPLS (crossval_PPLS.R:12-24): ``newdata W diag(B) C'`` for XorY = "X" (newdata is X,
+    the prediction is of Y) or ``newdata C diag(1/B) W'`` for "Y", on the GPU.  A 1-D ``newdata`` is
+    one row (R's ``t(newdata)``).  ``ctx``: a context whose data have the fit's shape; by default
+    the default context when its shape matches, else a private context that holds no rows."""
+    global _PREDICT_CTX
+    xy = XorY if isinstance(XorY, str) else XorY[0]          # match.arg
+    if xy not in ("X", "Y"):
+        raise ValueError("'arg' should be one of \"X\", \"Y\"")
+    W, C, B = _fit_parts(object)
+    nd = np.asarray(newdata, dtype=np.float64)
+    if nd.ndim != 2:
+        nd = nd.reshape(1, -1)
+    if nd.shape[1] != (W.shape[0] if xy == "X" else C.shape[0]):
+        raise ValueError("Number of columns mismatch!")
+    p, q = W.shape[0], C.shape[0]
+    if ctx is None:
+        ctx = _DEFAULT_CTX if _DEFAULT_CTX is not None and (_DEFAULT_CTX.p, _DEFAULT_CTX.q) == (p, q) else None
+    if ctx is None:
+        if _PREDICT_CTX is None:
+            _PREDICT_CTX = Context(0)
+        ctx = _PREDICT_CTX
+        if (ctx.p, ctx.q) != (p, q):
+            ctx.set_data(np.zeros((0, p)), np.zeros((0, q)))   # the shape only
+    return ctx.predict(W, C, B, nd, 0 if xy == "X" else 1)
+
+
+_CV_PPLS_ARGS = ("EMsteps", "atol", "initialGuess", "customGuess", "critfunc")
+
+
+def _cv_args(ppls_args):
+    bad = [k for k in ppls_args if k not in _CV_PPLS_ARGS]
+    if bad:
+        raise TypeError(f"cv_PPLS takes PPLS's {', '.join(_CV_PPLS_ARGS)}; got {', '.join(bad)}")
+    kind = ppls_args.get("initialGuess", "equal")
+    kind = kind if isinstance(kind, str) else kind[0]
+    custom = ppls_args.get("customGuess")
+    if custom is not None:
+        kind = "custom"
+    if kind == "o2m":
+        raise NotImplementedError("initialGuess='o2m' inside cross-validation is not implemented "
+                                  "(its starting values come from per-fold SVDs of the training rows)")
+    if kind not in ("equal", "random", "custom"):
+        raise ValueError(f"unknown initialGuess {kind!r}")
+    if kind == "custom" and custom is None:
+        raise ValueError("initialGuess='custom' needs customGuess")
+    return (kind, custom, int(ppls_args.get("EMsteps", 100)), float(ppls_args.get("atol", 1e-4)),
+            _crit_abs(ppls_args.get("critfunc")))
+
+
+def _cv_run(ctx, a, nr_folds, folds, rng, ppls_args):
+    """The folds of cv_PPLS (:42-44) and one ppls_cv_ppls call with ``a`` components:
+    (rmsep nr_folds x a, ncomp)."""
+    kind, custom, steps, atol, crit_abs = _cv_args(ppls_args)
+    N, K = int(ctx.n_total), int(nr_folds)
+    if K < 2:
+        raise ValueError("Cross-validation with 1 fold does not make sense, use 2 folds or more")
+    if N < K:
+        raise ValueError("nrow(X) >= nr_folds is not TRUE")
+    blocks = cv_blocks(N, K)
+    if folds is None:
+        rng = rng if rng is not None else np.random.default_rng()
+        folds = rng.permutation(N)                 # R: folds <- sample(N)
+    folds = np.asarray(folds, dtype=np.int64)
+    if folds.shape != (N,) or not np.array_equal(np.sort(folds), np.arange(N)):
+        raise ValueError("folds must be a permutation of 0..N-1")
+    fold_of = np.empty(N, dtype=np.int32)
+    fold_of[folds] = blocks - 1                    # fold i holds rows folds[blocks == i]
+    fold_total = np.bincount(fold_of, minlength=K).astype(np.int64)
+    if kind == "custom":
+        one = list(custom) if isinstance(custom, (list, tuple)) else [custom] * a
+        inits = [one] * K
+    elif kind == "equal":
+        inits = [[initial_guess(ctx.p, ctx.q, "equal") for _ in range(a)]] * K
+    else:                                          # fold by fold, component by component
+        rng = rng if rng is not None else np.random.default_rng()
+        inits = [[initial_guess(ctx.p, ctx.q, "random", rng) for _ in range(a)] for _ in range(K)]
+    lo = int(ctx.row0)
+    return ctx.cv_ppls(a, fold_of[lo: lo + ctx.n_local], fold_total, steps, atol, inits, crit_abs)
+
+
+def _cv_err(rmsep, ncomp, nr_comp):
+    """Per-fold error of the nr_comp-component fit; a fold whose fit stopped early is scored with
+    the components it has, as R's predict would with the truncated fit (and PPLS's warning)."""
+    k = np.minimum(ncomp, nr_comp)
+    if np.any(k < nr_comp):
+        warnings.warn("From component %d on the residuals are of rank < 1e-14 and calculations are stopped."
+                      % (int(k.min()) + 1))
+    return np.array([rmsep[f, k[f] - 1] if k[f] > 0 else np.nan for f in range(rmsep.shape[0])])
+
+
+def cv_PPLS(X, Y, nr_comp, nr_folds, folds=None, rng=None, ctx=None, per_fold=False, **ppls_args):
+    """cv_PPLS (crossval_PPLS.R:40-52): the RMSEP of Y predicted from X by an nr_comp-component PPLS
+    fit, cross-validated over nr_folds folds, averaged over the folds (``mean(err)``); with
+    ``per_fold=True`` also the per-fold errors.  ``folds``: the permutation R's ``sample(N)`` would
+    give, 0-based (default ``rng.permutation(N)``); fold i holds ``folds[cv_blocks(N, K) == i]``.
+    ``ppls_args``: PPLS's EMsteps, atol, initialGuess ('equal', 'random', 'custom'), customGuess,
+    critfunc; 'random' starts are drawn from ``rng`` fold by fold, component by component.  The folds
+    run on the device (ppls_cv_ppls).  mse(x, y) = mean((x - y)^2) as in OmicsPLS."""
+    _cv_args(ppls_args)
+    if int(nr_folds) < 2:
+        raise ValueError("Cross-validation with 1 fold does not make sense, use 2 folds or more")
+    ctx = _ctx_with(X, Y, ctx)
+    rmsep, ncomp = _cv_run(ctx, int(nr_comp), nr_folds, folds, rng, ppls_args)
+    err = _cv_err(rmsep, ncomp, int(nr_comp))
+    return (float(np.mean(err)), err) if per_fold else float(np.mean(err))
+
+
+def crossval_PPLS(X, Y, a, nr_folds, nr_cores=1, shared_folds=False, ctx=None, **ppls_args):
+    """crossval_PPLS (crossval_PPLS.R:78-114): cv_PPLS for every number of components in ``a``.
+    Returns a dict of class "cvPPLS": ``errors`` (one per entry of ``a``), ``which_error`` (index of
+    the minimum into ``a``, 0-based), ``a_min`` and ``time`` (seconds).  ``nr_cores`` is checked as
+    in R and otherwise ignored: the folds run on the one device.  Default: a fresh fold permutation
+    per entry of ``a`` as in R, one device loop per entry.  ``shared_folds=True``: one permutation and
+    one loop with max(a) components whose prefixes give every entry (PPLS is sequential): K fits
+    instead of K * len(a).  ``rng`` / ``folds`` are passed on as for cv_PPLS."""
+    tic = time.perf_counter()
+    a = [int(v) for v in np.atleast_1d(a)]
+    rng = ppls_args.pop("rng", None)
+    folds = ppls_args.pop("folds", None)
+    _cv_args(ppls_args)
+    if X is not None:
+        X = np.asarray(X, dtype=np.float64)
+        Y = np.asarray(Y, dtype=np.float64)
+        if X.ndim != 2 or Y.ndim != 2:
+            raise ValueError("X and Y must be matrices")
+        if np.any(np.abs(X.mean(axis=0)) > 1e-5):
+            warnings.warn("Data is not centered, proceeding...")
+        p, q, n = X.shape[1], Y.shape[1], X.shape[0]
+    else:
+        if ctx is None or ctx.n_local is None:
+            raise ValueError("no data: pass X and Y or a context with resident data")
+        p, q, n = ctx.p, ctx.q, ctx.n_total
+    if not a or min(a) < 1:
+        raise ValueError("a must hold positive integers")
+    if not (p > max(a) and q > max(a) and n >= nr_folds):         # stopifnot(...) :84
+        raise ValueError("ncol(X) > max(a), ncol(Y) > max(a), nrow(X) >= nr_folds are not all TRUE")
+    if nr_cores != abs(round(nr_cores)):                          # :85
+        raise ValueError("nr_cores == abs(round(nr_cores)) is not TRUE")
+    if nr_folds == 1:
+        raise ValueError("Cross-validation with 1 fold does not make sense, use 2 folds or more")
+    ctx = _ctx_with(X, Y, ctx)
+    if shared_folds:
+        rmsep, ncomp = _cv_run(ctx, max(a), nr_folds, folds, rng, ppls_args)
+        errors = [float(np.mean(_cv_err(rmsep, ncomp, e))) for e in a]
+    else:
+        rng = rng if rng is not None else np.random.default_rng()
+        errors = [cv_PPLS(None, None, e, nr_folds, folds=folds, rng=rng, ctx=ctx, **ppls_args) for e in a]
+    errors = np.array(errors)
+    which = int(np.nanargmin(errors)) if np.any(np.isfinite(errors)) else 0
+    out = dict(errors=errors, which_error=which, a_min=a[which], time=round(time.perf_counter() - tic, 2))
+    out["class"] = "cvPPLS"
     return out

@@ -24,6 +24,7 @@
 #include "../../include/ppls_debug.h"
 #include "ppls_kernels.h"
 #include "ppls_math.h"
+#include "ppls_cv.h"
 #include "ppls_xprod.h"
 
 struct ppls_ctx {
@@ -167,6 +168,13 @@ struct ppls_ctx {
   size_t ev_ar_used = 0;
   double ar_ms = 0.0;
   int64_t ar_calls = 0;
+  // cross-validation (ppls_cv_ppls): the training context, created once and reused for every fold
+  // (it borrows this context's communicator), and the phases of the calls since the last reset --
+  // {gather, held-out Gram + downdate, fits, scoring} in ms and the bytes the gather and the scoring
+  // kernel moved (ppls_cv_timing)
+  ppls_ctx* cv_train = nullptr;
+  double cv_ms[4] = {0, 0, 0, 0};
+  double cv_bytes[2] = {0, 0};
 };
 
 namespace {
@@ -1279,6 +1287,11 @@ int ppls_ctx_create(int device, ppls_ctx** out) {
 
 void ppls_ctx_destroy(ppls_ctx* c) {
   if (!c) return;
+  if (c->cv_train) {   // the training context of ppls_cv_ppls borrowed c's communicator
+    c->cv_train->comm = nullptr;
+    ppls_ctx_destroy(c->cv_train);
+    c->cv_train = nullptr;
+  }
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->comm) ncclCommDestroy(c->comm);
@@ -3436,6 +3449,420 @@ int ppls_finalize_host(const double* SX, const double* SY, const double* G, doub
     next->sigH = nx.sigH;
     if (next->W && SX && host_orth(SX, p, r, type, next->W) != PPLS_OK) return PPLS_E_NUMERIC;
     if (next->C && SY && host_orth(SY, q, r, type, next->C) != PPLS_OK) return PPLS_E_NUMERIC;
+  }
+  return PPLS_OK;
+}
+
+}  // extern "C"
+
+// ============================================================================ cross-validation
+// predict.PPLS, cv_PPLS and crossval_PPLS (Package/PPLS/R/crossval_PPLS.R:12-114) on the device:
+// a fold's training rows are gathered from the resident data into a second context (no host round
+// trip), its cross-products are S - S_fold, and the held-out rows are scored where they lie.
+namespace {
+
+// Device temporaries of one call, freed on every return path.
+struct CvScratch {
+  std::vector<void*> ptrs;
+  ~CvScratch() {
+    for (void* p : ptrs)
+      if (p) (void)hipFree(p);
+  }
+  template <typename T>
+  int get(ppls_ctx* c, T** out, size_t count) {
+    *out = nullptr;
+    const int rc = dalloc(c, out, count);
+    if (!rc) ptrs.push_back(*out);
+    return rc;
+  }
+};
+
+// A HIP-event bracket on one stream; ms() after the stream was synchronised.
+struct CvEvents {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~CvEvents() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  hipError_t begin(hipStream_t st) {
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = hipEventRecord(e0, st);
+    return e;
+  }
+  hipError_t end(hipStream_t st) { return hipEventRecord(e1, st); }
+  double ms() {
+    float f = 0.f;
+    return hipEventElapsedTime(&f, e0, e1) == hipSuccess ? (double)f : 0.0;
+  }
+};
+
+// Local row indices into a context's resident rows: in [0, limit), strictly ascending.
+int cv_check_rows(ppls_ctx* c, const int64_t* rows, int64_t nrows, int64_t limit) {
+  if (nrows < 0 || (nrows > 0 && !rows)) return fail(c, PPLS_E_ARG, "row list: %lld rows, NULL indices", (long long)nrows);
+  for (int64_t i = 0; i < nrows; ++i) {
+    if (rows[i] < 0 || rows[i] >= limit)
+      return fail(c, PPLS_E_ARG, "row index %lld (entry %lld) outside [0, %lld)", (long long)rows[i], (long long)i,
+                  (long long)limit);
+    if (i > 0 && rows[i] <= rows[i - 1])
+      return fail(c, PPLS_E_ARG, "row indices must be strictly ascending (entries %lld, %lld)", (long long)(i - 1),
+                  (long long)i);
+  }
+  return PPLS_OK;
+}
+
+int cv_upload_rows(ppls_ctx* c, CvScratch& tmp, const int64_t* rows, int64_t nrows, int64_t** d_rows) {
+  int rc;
+  if ((rc = tmp.get(c, d_rows, (size_t)std::max<int64_t>(nrows, 1)))) return rc;
+  if (nrows > 0) HIPCHK(c, hipMemcpy(*d_rows, rows, sizeof(int64_t) * nrows, hipMemcpyHostToDevice));
+  return PPLS_OK;
+}
+
+// Rows d_rows of s's resident X, Y into X, Y (rows of ldx / ldy elements of s's storage type): the
+// 16-byte units that hold real columns are copied (s's padding inside them is zero), the rest zeroed.
+hipError_t cv_gather(const ppls_ctx* s, const int64_t* d_rows, int64_t nrows, void* X, void* Y, int ldx, int ldy,
+                     hipStream_t st) {
+  const int64_t es = s->dtype ? 4 : 8;
+  hipError_t e = ppls_launch_gather_rows(s->X, s->ldx * es / 16, X, ldx * es / 16, (int)((s->p * es + 15) / 16), d_rows,
+                                         nrows, st);
+  if (e == hipSuccess)
+    e = ppls_launch_gather_rows(s->Y, s->ldy * es / 16, Y, ldy * es / 16, (int)((s->q * es + 15) / 16), d_rows, nrows, st);
+  return e;
+}
+
+double cv_gather_bytes(const ppls_ctx* s, int64_t nrows, int ldx, int ldy) {   // read + written
+  const double es = s->dtype ? 4.0 : 8.0;
+  return (double)nrows * es * ((double)s->p + s->q + ldx + ldy);
+}
+
+// M (rowsM x k column-major) zero-padded to ((rowsM + 3) & ~3) x k on the device.
+int cv_upload_coef(ppls_ctx* c, CvScratch& tmp, const double* M, int rowsM, int k, double** out) {
+  const int ld4 = (rowsM + 3) & ~3;
+  std::vector<double> h((size_t)ld4 * k, 0.0);
+  for (int m = 0; m < k; ++m) memcpy(&h[(size_t)m * ld4], M + (size_t)m * rowsM, sizeof(double) * rowsM);
+  int rc;
+  if ((rc = tmp.get(c, out, h.size()))) return rc;
+  HIPCHK(c, hipMemcpy(*out, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
+  return PPLS_OK;
+}
+
+bool cv_collective(const ppls_ctx* c) { return c->nranks > 1 || c->reducer; }
+
+}  // namespace
+
+extern "C" {
+
+int ppls_set_data_from(ppls_ctx* dst, ppls_ctx* src, const int64_t* rows, int64_t nrows, int64_t n_total) {
+  if (!dst || !src) return dst ? fail(dst, PPLS_E_ARG, "NULL source context") : PPLS_E_ARG;
+  if (dst == src) return fail(dst, PPLS_E_ARG, "source and destination are the same context");
+  if (!src->have_data) return fail(dst, PPLS_E_ARG, "the source context has no data");
+  if (dst->device != src->device)
+    return fail(dst, PPLS_E_ARG, "contexts on different devices (%d, %d)", dst->device, src->device);
+  int rc;
+  if ((rc = cv_check_rows(dst, rows, nrows, src->n_local))) return rc;
+  if (n_total > 0 && n_total < nrows) return fail(dst, PPLS_E_ARG, "n_total=%lld < %lld local rows", (long long)n_total, (long long)nrows);
+  HIPCHK(dst, hipSetDevice(dst->device));
+  CvScratch tmp;
+  int64_t* d_rows = nullptr;
+  if ((rc = cv_upload_rows(dst, tmp, rows, nrows, &d_rows))) return rc;
+  dst->dtype = src->dtype;
+  if ((rc = alloc_data(dst, nrows, src->p, src->q, n_total))) return rc;
+  // the slack of dst's new buffers is zeroed on dst's stream, the gather reads src: it runs on src's
+  // stream, behind whatever src still has queued
+  HIPCHK(dst, hipStreamSynchronize(dst->stream));
+  CvEvents ev;
+  HIPCHK(dst, ev.begin(src->stream));
+  HIPCHK(dst, cv_gather(src, d_rows, nrows, dst->X, dst->Y, dst->ldx, dst->ldy, src->stream));
+  HIPCHK(dst, ev.end(src->stream));
+  HIPCHK(dst, hipStreamSynchronize(src->stream));
+  src->cv_ms[0] += ev.ms();
+  src->cv_bytes[0] += cv_gather_bytes(src, nrows, dst->ldx, dst->ldy);
+  dst->have_data = true;
+  if ((rc = compute_ssq(dst))) return rc;   // drops a stale S; collective when sharded (also with no rows)
+  return check_finite_data(dst);
+}
+
+int ppls_xprod_downdate(ppls_ctx* dst, ppls_ctx* src, const int64_t* out_rows, int64_t n_out) {
+  if (!dst || !src) return dst ? fail(dst, PPLS_E_ARG, "NULL source context") : PPLS_E_ARG;
+  if (dst == src) return fail(dst, PPLS_E_ARG, "source and destination are the same context");
+  if (!src->have_data || !dst->have_data) return fail(dst, PPLS_E_STATE, "no data");
+  if (dst->device != src->device)
+    return fail(dst, PPLS_E_ARG, "contexts on different devices (%d, %d)", dst->device, src->device);
+  if (dst->p != src->p || dst->q != src->q || dst->ldx != src->ldx || dst->ldy != src->ldy || dst->dtype != src->dtype)
+    return fail(dst, PPLS_E_ARG, "the contexts' data differ in shape, padding or storage type");
+  HIPCHK(dst, hipSetDevice(src->device));
+  int rc;
+  // S of all rows first (a collective of its own when sharded: every rank is here)
+  if ((rc = xprod_setup(src))) {
+    dst->err = src->err;
+    return rc;
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  const bool coll = cv_collective(src);
+  const int P = src->ldx + src->ldy;
+  const size_t PP = (size_t)P * P;
+  // this rank's verdict on its arguments joins the agreement below, so that ranks return together
+  int bad = cv_check_rows(dst, out_rows, n_out, src->n_local);
+  if (!bad && dst->n_local != src->n_local - n_out)
+    bad = fail(dst, PPLS_E_ARG, "row counts: %lld resident - %lld held out != %lld training rows on this rank",
+               (long long)src->n_local, (long long)n_out, (long long)dst->n_local);
+  if (bad && !coll) return bad;
+  // every allocation of the call, then the ranks agree that all of them succeeded before anyone
+  // enters the all-reduce of the held-out Gram (as xprod_setup does for S)
+  CvScratch tmp;
+  int64_t* d_rows = nullptr;
+  double *gX = nullptr, *gY = nullptr, *Gout = nullptr, *part = nullptr;
+  const int64_t no = bad ? 0 : n_out;
+  const size_t es = src->dtype ? 4 : 8;
+  const size_t xb = (size_t)std::max<int64_t>(no, 1) * src->ldx * es, yb = (size_t)std::max<int64_t>(no, 1) * src->ldy * es;
+  const GramShape g{P, src->p, src->ldx, src->q, nullptr, src->ldx, nullptr, src->ldy, src->ldy};
+  xprod_free(dst);
+  int rc_alloc = dalloc(dst, &dst->xp_S, PP);
+  if (!rc_alloc) rc_alloc = tmp.get(src, &Gout, PP);
+  if (!rc_alloc) rc_alloc = cv_upload_rows(src, tmp, out_rows, no, &d_rows);
+  if (!rc_alloc) rc_alloc = tmp.get(src, &gX, (xb + 7) / 8 + 64);
+  if (!rc_alloc) rc_alloc = tmp.get(src, &gY, (yb + 7) / 8 + 64);
+  if (!rc_alloc && no > 0) {
+    int* q = nullptr;
+    rc_alloc = tmp.get(src, &part, (size_t)ppls_gram_part_doubles(P, gram_nsplit(src, g, no, 0)));
+    if (!rc_alloc) rc_alloc = gram_queue(src, g, no, 0, &q);
+  }
+  double n_out_total = (double)no;
+  if (coll) {
+    double f[3] = {rc_alloc ? 1.0 : 0.0, bad ? 1.0 : 0.0, (double)no};
+    HIPCHK(dst, hipMemcpyAsync(src->flag, f, sizeof f, hipMemcpyHostToDevice, src->stream));
+    if ((rc = allreduce(src, src->flag, 3))) { dfree(dst->xp_S); dst->err = src->err; return rc; }
+    HIPCHK(dst, hipMemcpyAsync(f, src->flag, sizeof f, hipMemcpyDeviceToHost, src->stream));
+    HIPCHK(dst, hipStreamSynchronize(src->stream));
+    if (f[0] > 0.0) {
+      dfree(dst->xp_S);
+      return fail(dst, PPLS_E_NOMEM, "downdate of S: %d rank(s) could not allocate S, the held-out rows or their Gram", (int)f[0]);
+    }
+    if (f[1] > 0.0) {
+      dfree(dst->xp_S);
+      return bad ? bad : fail(dst, PPLS_E_ARG, "downdate of S: %d other rank(s) passed bad held-out rows", (int)f[1]);
+    }
+    n_out_total = f[2];
+  } else if (rc_alloc) {
+    dfree(dst->xp_S);
+    if (dst->err.empty()) dst->err = src->err;
+    return rc_alloc;
+  }
+  // the totals every rank shares: held out + training = all rows, and no more held out than kept
+  // (beyond that S - S_out loses more than a direct Gram of the training rows: form S directly)
+  if (n_out_total != (double)(src->n_total - dst->n_total) || n_out_total > (double)dst->n_total) {
+    dfree(dst->xp_S);
+    return fail(dst, PPLS_E_ARG, "row counts over all ranks: %lld rows, %.0f held out, %lld training rows%s",
+                (long long)src->n_total, n_out_total, (long long)dst->n_total,
+                n_out_total > (double)dst->n_total ? " (more held out than kept: form S directly)" : "");
+  }
+  hipError_t e = hipMemsetAsync((char*)gX + xb, 0, ((xb + 7) / 8 + 64) * 8 - xb, src->stream);
+  if (e == hipSuccess) e = hipMemsetAsync((char*)gY + yb, 0, ((yb + 7) / 8 + 64) * 8 - yb, src->stream);
+  CvEvents ev;
+  if (e == hipSuccess) e = ev.begin(src->stream);
+  if (e == hipSuccess) e = cv_gather(src, d_rows, no, gX, gY, src->ldx, src->ldy, src->stream);
+  if (e == hipSuccess) e = ev.end(src->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(src->stream);
+  if (e != hipSuccess) { dfree(dst->xp_S); return fail(dst, PPLS_E_HIP, "held-out gather: %s", hipGetErrorString(e)); }
+  const double gather_ms = ev.ms();
+  src->cv_ms[0] += gather_ms;
+  src->cv_bytes[0] += cv_gather_bytes(src, no, src->ldx, src->ldy);
+  if (no > 0) {
+    GramShape gs = g;
+    gs.X = gX;
+    gs.Y = gY;
+    const int oz_used = src->oz_used;   // src's record of how its own S was formed stays
+    rc = gram_run_s(src, gs, no, Gout, nullptr, part);
+    src->oz_used = oz_used;
+    if (rc) { dfree(dst->xp_S); dst->err = src->err; return rc; }
+  } else {
+    HIPCHK(dst, hipMemsetAsync(Gout, 0, sizeof(double) * PP, src->stream));
+  }
+  if ((rc = allreduce(src, Gout, PP))) { dfree(dst->xp_S); dst->err = src->err; return rc; }
+  e = ppls_launch_downdate(src->xp_S, Gout, dst->xp_S, (int64_t)PP, src->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(src->stream);
+  if (e != hipSuccess) { dfree(dst->xp_S); return fail(dst, PPLS_E_HIP, "downdate of S: %s", hipGetErrorString(e)); }
+  dst->xp_ready = true;
+  dst->xp_explicit = true;   // given by the caller, like ppls_xprod_prepare's: kept until new data or release
+  src->cv_ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - gather_ms;
+  return PPLS_OK;
+}
+
+int ppls_predict(ppls_ctx* c, const double* W, const double* C, const double* B, int k, int xory, const double* newdata,
+                 int64_t n, int layout, double* pred) {
+  if (!c) return PPLS_E_ARG;
+  if (c->p < 1 || c->q < 1) return fail(c, PPLS_E_STATE, "no data shape: load data (p, q) first");
+  if (!W || !C || !B || k < 1 || k > PPLS_RMAX) return fail(c, PPLS_E_ARG, "W, C, B must be given with 1 <= k <= %d", PPLS_RMAX);
+  if (xory != 0 && xory != 1) return fail(c, PPLS_E_ARG, "xory must be 0 (newdata is X) or 1 (Y)");
+  if (layout != PPLS_LAYOUT_COLMAJOR && layout != PPLS_LAYOUT_ROWMAJOR)
+    return fail(c, PPLS_E_ARG, "layout must be 0 (column-major) or 1 (row-major)");
+  if (n < 0 || (n > 0 && (!newdata || !pred))) return fail(c, PPLS_E_ARG, "NULL newdata or pred");
+  if (n == 0) return PPLS_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  // newdata W diag(B) C' (X) or newdata C diag(1/B) W' (Y), crossval_PPLS.R:19-21
+  const int pa = xory ? c->q : c->p, qb = xory ? c->p : c->q;
+  const int lda = (pa + 1) & ~1, ldo = (qb + 1) & ~1;
+  std::vector<double> s(k);
+  for (int m = 0; m < k; ++m) s[m] = xory ? 1.0 / B[m] : B[m];
+  int rc;
+  CvScratch tmp;
+  double *A = nullptr, *Bm = nullptr, *sd = nullptr, *in = nullptr, *out = nullptr, *cm = nullptr;
+  if ((rc = cv_upload_coef(c, tmp, xory ? C : W, pa, k, &A))) return rc;
+  if ((rc = cv_upload_coef(c, tmp, xory ? W : C, qb, k, &Bm))) return rc;
+  if ((rc = cv_upload_coef(c, tmp, s.data(), k, 1, &sd))) return rc;
+  // row blocks of newdata through a staging buffer (~64 MB of input rows at a time)
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(64 << 20) / (8LL * std::max(lda, ldo))));
+  if ((rc = tmp.get(c, &in, (size_t)chunk * lda))) return rc;
+  if ((rc = tmp.get(c, &out, (size_t)chunk * ldo))) return rc;
+  if ((rc = tmp.get(c, &cm, (size_t)chunk * std::max(pa, qb)))) return rc;
+  HIPCHK(c, hipMemsetAsync(in, 0, sizeof(double) * chunk * lda, c->stream));
+  for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+    const int64_t nc = std::min(chunk, n - r0);
+    if (layout == PPLS_LAYOUT_ROWMAJOR) {
+      HIPCHK(c, hipMemcpy2DAsync(in, sizeof(double) * lda, newdata + r0 * pa, sizeof(double) * pa, sizeof(double) * pa, nc,
+                                 hipMemcpyHostToDevice, c->stream));
+    } else {
+      HIPCHK(c, hipMemcpy2DAsync(cm, sizeof(double) * nc, newdata + r0, sizeof(double) * n, sizeof(double) * nc, pa,
+                                 hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, ppls_launch_to_rowmajor(cm, nc, pa, lda, in, c->stream));
+    }
+    HIPCHK(c, ppls_launch_cv_score(in, lda, pa, nullptr, 0, qb, 0, nullptr, nc, A, Bm, sd, k, nullptr, out, ldo,
+                                   ppls_cv_grid(nc, k, c->num_cus), c->stream));
+    HIPCHK(c, ppls_launch_to_colmajor(out, nc, qb, ldo, cm, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy2D(pred + r0, sizeof(double) * n, cm, sizeof(double) * nc, sizeof(double) * nc, qb,
+                          hipMemcpyDeviceToHost));
+  }
+  return PPLS_OK;
+}
+
+int ppls_heldout_sse(ppls_ctx* c, const double* W, const double* C, const double* B, int k, const int64_t* rows,
+                     int64_t nrows, double* sse) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  if (!W || !C || !B || !sse || k < 1 || k > PPLS_RMAX)
+    return fail(c, PPLS_E_ARG, "W, C, B, sse must be given with 1 <= k <= %d", PPLS_RMAX);
+  int rc;
+  if ((rc = cv_check_rows(c, rows, nrows, c->n_local))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  CvScratch tmp;
+  double *A = nullptr, *Bm = nullptr, *sd = nullptr, *part = nullptr, *tot = nullptr;
+  int64_t* d_rows = nullptr;
+  const int grid = ppls_cv_grid(nrows, k, c->num_cus);
+  const int nparts = grid * PPLS_CV_WAVES;
+  if ((rc = cv_upload_coef(c, tmp, W, c->p, k, &A))) return rc;
+  if ((rc = cv_upload_coef(c, tmp, C, c->q, k, &Bm))) return rc;
+  if ((rc = cv_upload_coef(c, tmp, B, k, 1, &sd))) return rc;
+  if ((rc = cv_upload_rows(c, tmp, rows, nrows, &d_rows))) return rc;
+  if ((rc = tmp.get(c, &part, (size_t)nparts * k))) return rc;
+  if ((rc = tmp.get(c, &tot, (size_t)k))) return rc;
+  CvEvents ev;
+  HIPCHK(c, ev.begin(c->stream));
+  // (a rank with no held-out row launches too: its waves write zero partials)
+  HIPCHK(c, ppls_launch_cv_score(c->X, c->ldx, c->p, c->Y, c->ldy, c->q, c->dtype, d_rows, nrows, A, Bm, sd, k, part,
+                                 nullptr, 0, grid, c->stream));
+  HIPCHK(c, ppls_launch_cv_sse_reduce(part, nparts, k, tot, c->stream));
+  HIPCHK(c, ev.end(c->stream));
+  if ((rc = allreduce(c, tot, (size_t)k))) return rc;
+  HIPCHK(c, hipMemcpyAsync(sse, tot, sizeof(double) * k, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->cv_ms[3] += ev.ms();
+  c->cv_bytes[1] += (double)nrows * (c->dtype ? 4.0 : 8.0) * ((double)c->p + c->q);
+  return PPLS_OK;
+}
+
+int ppls_cv_ppls(ppls_ctx* c, int a, int nfolds, const int32_t* fold_of_row, const int64_t* fold_total, int max_steps,
+                 double atol, int crit_abs, const ppls_theta* init, double* rmsep, int* ncomp) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  if (!fold_total || !init || !rmsep || !ncomp || (c->n_local > 0 && !fold_of_row)) return fail(c, PPLS_E_ARG, "NULL argument");
+  if (a < 1 || a > PPLS_RMAX) return fail(c, PPLS_E_ARG, "nr_comp=%d outside [1,%d]", a, PPLS_RMAX);
+  if (nfolds < 2) return fail(c, PPLS_E_ARG, "Cross-validation with 1 fold does not make sense, use 2 folds or more");
+  int64_t tot = 0;
+  for (int f = 0; f < nfolds; ++f) {
+    if (fold_total[f] < 1) return fail(c, PPLS_E_ARG, "fold %d holds %lld rows", f, (long long)fold_total[f]);
+    tot += fold_total[f];
+  }
+  if (tot != c->n_total) return fail(c, PPLS_E_ARG, "the folds hold %lld rows, the data %lld", (long long)tot, (long long)c->n_total);
+  std::vector<std::vector<int64_t>> in_fold((size_t)nfolds);
+  for (int64_t i = 0; i < c->n_local; ++i) {
+    if (fold_of_row[i] < 0 || fold_of_row[i] >= nfolds) return fail(c, PPLS_E_ARG, "fold_of_row[%lld]=%d outside [0,%d)", (long long)i, fold_of_row[i], nfolds);
+    in_fold[(size_t)fold_of_row[i]].push_back(i);
+  }
+  for (int f = 0; f < nfolds; ++f)
+    if ((int64_t)in_fold[(size_t)f].size() > fold_total[f])
+      return fail(c, PPLS_E_ARG, "fold %d: %zu local rows, %lld over all ranks", f, in_fold[(size_t)f].size(), (long long)fold_total[f]);
+  for (int k = 0; k < nfolds * a; ++k)
+    if (!init[k].W || !init[k].C || !init[k].B || !init[k].sigT) return fail(c, PPLS_E_ARG, "init[%d] has NULL fields", k);
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if (!c->cv_train && (rc = ppls_ctx_create(c->device, &c->cv_train))) return fail(c, rc, "could not create the training context");
+  ppls_ctx* t = c->cv_train;
+  // c's options carry over; the communicator is borrowed (ppls_ctx_destroy(c) takes it back)
+  t->xprod = c->xprod;
+  t->xprod_rw = c->xprod_rw;
+  t->xprod_fuse = c->xprod_fuse;
+  if (t->gram_int8 && !c->gram_int8) {
+    HIPCHK(c, hipStreamSynchronize(t->stream));
+    oz_free(t);
+  }
+  t->gram_int8 = c->gram_int8;
+  t->ldpad = c->ldpad;
+  t->sweep_mode = c->sweep_mode;
+  t->grid_opt = c->grid_opt;
+  t->nt_loads = c->nt_loads;
+  t->reducer = c->reducer;
+  t->reducer_user = c->reducer_user;
+  t->comm = c->comm;
+  t->nranks = c->nranks;
+  t->rank = c->rank;
+  const int p = c->p, q = c->q;
+  std::vector<double> W((size_t)p * a), C((size_t)q * a), B((size_t)a), sig((size_t)4 * a), sse((size_t)a);
+  std::vector<int64_t> train;
+  for (int f = 0; f < nfolds; ++f) {
+    const std::vector<int64_t>& out = in_fold[(size_t)f];
+    // R's X[-folds[ii], ] (crossval_PPLS.R:48): the other rows, in their order
+    train.clear();
+    for (int64_t i = 0; i < c->n_local; ++i)
+      if (fold_of_row[i] != f) train.push_back(i);
+    const int64_t n_train = c->n_total - fold_total[f];
+    if (n_train < 1) return fail(c, PPLS_E_ARG, "fold %d leaves no training row", f);
+    if ((rc = ppls_set_data_from(t, c, train.data(), (int64_t)train.size(), n_train))) { c->err = t->err; return rc; }
+    // fits that read S get it as S - S_fold; a fold larger than its training set (2 uneven folds)
+    // is past the downdate's error statement: ppls_ppls_ex then forms S from the training rows
+    if (xprod_choose(t, a * max_steps, 1) && fold_total[f] <= n_train)
+      if ((rc = ppls_xprod_downdate(t, c, out.data(), (int64_t)out.size()))) { c->err = t->err; return rc; }
+    ppls_seq_fit fit;
+    memset(&fit, 0, sizeof fit);
+    fit.W = W.data();
+    fit.C = C.data();
+    fit.B = B.data();
+    fit.sig = sig.data();
+    const auto t0 = std::chrono::steady_clock::now();
+    rc = ppls_ppls_ex(t, a, max_steps, atol, crit_abs, init + (size_t)f * a, nullptr, &fit);
+    c->cv_ms[2] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rc) { c->err = t->err; return rc; }
+    ncomp[f] = fit.ncomp;
+    for (int j = 0; j < a; ++j) rmsep[(size_t)f * a + j] = NAN;
+    if (fit.ncomp < 1) continue;   // every rank alike: the fits are the same on all ranks
+    if ((rc = ppls_heldout_sse(c, W.data(), C.data(), B.data(), fit.ncomp, out.data(), (int64_t)out.size(), sse.data())))
+      return rc;
+    // sqrt(mse(Y[fold, ], predict(fit, X[fold, ], "X"))) with mse(x, y) = mean((x - y)^2) (:49)
+    for (int j = 0; j < fit.ncomp; ++j) rmsep[(size_t)f * a + j] = std::sqrt(sse[j] / ((double)fold_total[f] * q));
+  }
+  return PPLS_OK;
+}
+
+int ppls_cv_timing(ppls_ctx* c, double* out6, int reset) {
+  if (!c) return PPLS_E_ARG;
+  if (out6) {
+    for (int i = 0; i < 4; ++i) out6[i] = c->cv_ms[i];
+    out6[4] = c->cv_bytes[0];
+    out6[5] = c->cv_bytes[1];
+  }
+  if (reset) {
+    for (int i = 0; i < 4; ++i) c->cv_ms[i] = 0.0;
+    c->cv_bytes[0] = c->cv_bytes[1] = 0.0;
   }
   return PPLS_OK;
 }
