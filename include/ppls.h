@@ -160,6 +160,25 @@ int ppls_get_data(ppls_ctx* ctx, double* X, double* Y, int64_t row_begin, int64_
 int ppls_get_data_rows(ppls_ctx* ctx, double* X, double* Y, int64_t row_begin, int64_t nrows);
 int ppls_data_ssq(ppls_ctx* ctx, double* ssqX, double* ssqY);   /* global (all ranks) */
 
+/* R's scale(X, center, scale) and scale(Y, center, scale) applied to the resident data, in place
+ * (columns over ALL ranks' rows): center_j = sum_i x_ij / n_total, then scale_j =
+ * sqrt(sum_i (x_ij - center_j)^2 / (n_total - 1)) (center = 0: center_j = 0, R's root-mean-square),
+ * then x_ij <- (x_ij - center_j) / scale_j.  fp64 arithmetic on either storage dtype (fp32 storage:
+ * one rounding, at the store); fixed-order sums, so the result is bitwise repeatable.  Collective
+ * when the rows are sharded: one all-reduce of p + q doubles per statistic; a rank with n_local = 0
+ * still joins.  center = scale = 0 is a no-op.  PPLS_E_ARG, with the data untouched and on every
+ * rank alike: scale = 1 with n_total < 2, or with a column whose scale_j is not > 0 or not finite (R
+ * would fill it with NaN); the message names the block and the column, 1-based.  Afterwards the
+ * context is as if the transformed matrix had been loaded with ppls_set_data: ||X||^2, ||Y||^2
+ * recomputed, a resident S dropped (the next run that reads S forms it from the new values), an
+ * ppls_em_begin session ended (ppls_em_iterate returns PPLS_E_STATE until the next ppls_em_begin). */
+int ppls_scale_data(ppls_ctx* ctx, int center, int scale);
+/* The transform the resident data carry relative to what was loaded:
+ * loaded = resident * scale + center, column-wise.  p + q values each (X's columns, then Y's);
+ * center 0 / scale 1 after ppls_set_data, ppls_generate_synthetic; calls of ppls_scale_data compose;
+ * ppls_set_data_from copies the source's. */
+int ppls_get_scaling(ppls_ctx* ctx, double* center, double* scale);
+
 /* ---- the hot path ------------------------------------------------------------------------ */
 int ppls_estep(ppls_ctx* ctx, const ppls_theta* th, int r, ppls_expect* out);
 int ppls_mstep(ppls_ctx* ctx, const ppls_expect* fit, int r, int type, ppls_theta* out);

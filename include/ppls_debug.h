@@ -99,6 +99,11 @@ int ppls_sweep_trace(ppls_ctx* ctx, int64_t* stamps, int cap, int* n, double* ti
  * scoring kernel read. */
 int ppls_cv_timing(ppls_ctx* ctx, double* out6, int reset);
 
+/* The passes of the last ppls_scale_data on this context: {column sums, centred squares, apply},
+ * X and Y together: ms3 from HIP events around the pass's kernels (0 for a pass that did not run),
+ * bytes3 the bytes the pass read (the apply pass: read + written) on this rank. */
+int ppls_scale_timing(ppls_ctx* ctx, double* ms3, double* bytes3);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,9 @@ SIGNATURES = {
     "ppls_cv_ppls": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(ct.c_int32), _i64p, ct.c_int,
                                 ct.c_double, ct.c_int, ct.POINTER(PplsTheta), _dp, ct.POINTER(ct.c_int)]),
     "ppls_cv_timing": (ct.c_int, [ct.c_void_p, _dp, ct.c_int]),
+    "ppls_scale_data": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int]),
+    "ppls_get_scaling": (ct.c_int, [ct.c_void_p, _dp, _dp]),
+    "ppls_scale_timing": (ct.c_int, [ct.c_void_p, _dp, _dp]),
 }
 
 

@@ -177,6 +177,30 @@ class Context:
         self._chk(self._L.ppls_data_ssq(self.h, ct.byref(a), ct.byref(b)))
         return a.value, b.value
 
+    def scale_data(self, center=True, scale=True):
+        """R's ``scale(X, center, scale)`` and ``scale(Y, center, scale)`` on the resident data, in
+        place on the device (ppls_scale_data): column means and standard deviations over all
+        ranks' rows.  Collective when the rows are sharded.  A column without spread under
+        ``scale=True`` is an argument error and leaves the data untouched."""
+        self._chk(self._L.ppls_scale_data(self.h, int(bool(center)), int(bool(scale))))
+
+    def scaling(self):
+        """The transform the resident data carry relative to what was loaded (ppls_get_scaling):
+        ``loaded = resident * scale + center`` column-wise, as ``dict(centerX, scaleX, centerY,
+        scaleY)`` -- R's ``attr(, "scaled:center")`` / ``"scaled:scale"`` after one ``scale_data``."""
+        cen = np.zeros(self.p + self.q)
+        scl = np.ones(self.p + self.q)
+        self._chk(self._L.ppls_get_scaling(self.h, dptr(cen), dptr(scl)))
+        return dict(centerX=cen[: self.p].copy(), scaleX=scl[: self.p].copy(),
+                    centerY=cen[self.p:].copy(), scaleY=scl[self.p:].copy())
+
+    def scale_timing(self):
+        """The passes of the last ``scale_data`` (ppls_scale_timing): per pass (column sums, centred
+        squares, apply) the ms between HIP events and the bytes moved on this rank."""
+        ms, by = np.zeros(3), np.zeros(3)
+        self._chk(self._L.ppls_scale_timing(self.h, dptr(ms), dptr(by)))
+        return dict(ms=ms, bytes=by)
+
     # -- hot path
     def estep(self, th: Theta, want_mu=True) -> Expect:
         e = Expect(th.r, self.n_local, want_mu)
@@ -1239,6 +1263,19 @@ def PPLS_simult(X, Y, a, EMsteps=10, atol=1e-4, type=("SVD", "QR"), init=None, c
     return out
 
 
+# ---------------------------------------------------------------------------- scale()
+def scale_data(X=None, Y=None, center=True, scale=True, ctx=None):
+    """R's ``scale(X, center, scale)`` and ``scale(Y, center, scale)`` on the device, in place: what
+    every example of the reference does before a fit (man/PPLS.Rd:57-58).  ``X``, ``Y``: loaded
+    first if given, else the context's resident data are scaled.  Returns ``dict(centerX, scaleX,
+    centerY, scaleY)``, R's ``attr(, "scaled:center")`` / ``"scaled:scale"`` (for data scaled more
+    than once: of the composed transform).  The scaled data stay resident:
+    ``scale_data(X, Y, ctx=ctx); PPLS(None, None, 3, ctx=ctx)``."""
+    ctx = _ctx_with(X, Y, ctx)
+    ctx.scale_data(center, scale)
+    return ctx.scaling()
+
+
 # ---------------------------------------------------------------------------- cross-validation
 # predict.PPLS, cv_PPLS, crossval_PPLS (Package/PPLS/R/crossval_PPLS.R:12-114).  Two statements below
 # rest on no R run: mse(x, y) = mean((x - y)^2) is OmicsPLS's (not vendored with the reference), and
@@ -1273,11 +1310,15 @@ def _fit_parts(obj):
     return W, C, est["B"]
 
 
-def predict_PPLS(object, newdata, XorY=("X", "Y"), ctx=None):
+def predict_PPLS(object, newdata, XorY=("X", "Y"), ctx=None, rescale=False):
     """predict.PPLS (crossval_PPLS.R:12-24): ``newdata W diag(B) C'`` for XorY = "X" (newdata is X,
     the prediction is of Y) or ``newdata C diag(1/B) W'`` for "Y", on the GPU.  A 1-D ``newdata`` is
     one row (R's ``t(newdata)``).  ``ctx``: a context whose data have the fit's shape; by default
-    the default context when its shape matches, else a private context that holds no rows."""
+    the default context when its shape matches, else a private context that holds no rows.
+    ``rescale=True``: ``newdata`` is in the units the data were loaded in; with a context whose data
+    were scaled on the device (``scale_data``) it is brought to the fit's scale with the stored
+    centre and scale of its block, on the host, and the prediction is mapped back to the loaded
+    units of the other block."""
     global _PREDICT_CTX
     xy = XorY if isinstance(XorY, str) else XorY[0]          # match.arg
     if xy not in ("X", "Y"):
@@ -1297,6 +1338,12 @@ def predict_PPLS(object, newdata, XorY=("X", "Y"), ctx=None):
         ctx = _PREDICT_CTX
         if (ctx.p, ctx.q) != (p, q):
             ctx.set_data(np.zeros((0, p)), np.zeros((0, q)))   # the shape only
+    if rescale:
+        sc = ctx.scaling()
+        cin, sin, cout, sout = ((sc["centerX"], sc["scaleX"], sc["centerY"], sc["scaleY"]) if xy == "X" else
+                                (sc["centerY"], sc["scaleY"], sc["centerX"], sc["scaleX"]))
+        if np.any(cin != 0) or np.any(sin != 1) or np.any(cout != 0) or np.any(sout != 1):
+            return ctx.predict(W, C, B, (nd - cin) / sin, 0 if xy == "X" else 1) * sout + cout
     return ctx.predict(W, C, B, nd, 0 if xy == "X" else 1)
 
 
