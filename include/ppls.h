@@ -362,6 +362,67 @@ int ppls_cv_ppls(ppls_ctx* ctx, int a, int nfolds, const int32_t* fold_of_row /*
                  int max_steps, double atol, int crit_abs, const ppls_theta* init /* nfolds x a */,
                  double* rmsep /* nfolds x a, fold-major */, int* ncomp /* nfolds */);
 
+/* ---- streamed data: fit from row chunks, no rows resident -------------------------------------
+ * Since the cross-product form a PPLS_simult iteration and every rank-1 step of PPLS read only
+ * S = [X Y]'[X Y] (8 (p+q)^2 bytes); the rows are needed once, to form S.  These calls form S -- of the
+ * data centred and scaled as R's scale() does, if asked -- from row chunks that come from the host or
+ * from another context's resident rows, so neither a host array nor HBM ever holds all rows.
+ * Afterwards the context is "streamed": have data, n_local = 0, n_total = the rows streamed over all
+ * ranks, S ready and kept as if by ppls_xprod_prepare.  The library never computes from the zero
+ * resident rows:
+ *   - statistics come from S whatever option "xprod" holds (setting it to 0 neither frees S nor ends a
+ *     session): ppls_em_run, ppls_em_begin / _iterate / _state, ppls_em_step, ppls_estep,
+ *     ppls_loglik, ppls_loglC_fast(X = Y = NULL), ppls_ppls / ppls_ppls_ex, ppls_data_ssq,
+ *     ppls_get_scaling and ppls_predict work (ppls_ppls_ex keeps the running ||Xc||^2 where a resident
+ *     context would recompute a cancelled one from the rows);
+ *   - PPLS_E_STATE "the rows were streamed and are not resident", before any work: mu_T / mu_U asked of
+ *     ppls_estep, ppls_em_step or ppls_em_run; ppls_mstep (X'mu_T of caller-supplied mu needs the rows);
+ *     ppls_scores; ppls_get_data / _rows; ppls_variances; ppls_heldout_sse; ppls_cv_ppls;
+ *     ppls_set_data_from / ppls_xprod_downdate with a streamed source; ppls_scale_data;
+ *     ppls_meta_emstep / ppls_meta_ppls; ppls_comm_init and ppls_set_reducer (set them before
+ *     ppls_stream_begin); option "dtype";
+ *   - ppls_xprod_release, ppls_set_data, ppls_generate_synthetic and ppls_stream_begin end the state
+ *     (after ppls_xprod_release the context has no data).
+ * While a stream is open (between begin and end) the context has no data: every fit and data entry
+ * point returns PPLS_E_STATE, and so do ppls_comm_init, ppls_set_reducer and a change of option
+ * "dtype" (what ppls_stream_end's collectives run over is fixed at ppls_stream_begin). */
+
+/* Open a stream of p + q columns: drops resident data, S and an ppls_em_begin session; allocates S
+ * (P x P, P = ldx + ldy in the padded layout) zeroed and the running column means; the row count
+ * starts at 0.  center, scale: 0 or 1, R's meaning as in ppls_scale_data (scale without center: the
+ * root-mean-square). */
+int ppls_stream_begin(ppls_ctx* ctx, int p, int q, int center, int scale);
+/* One chunk of nrows >= 1 rows (X nrows x p, Y nrows x q, either layout; nrows = 0: no-op).  The
+ * chunk is staged in a device buffer the context owns -- always fp64, whatever option "dtype" holds,
+ * since nothing becomes resident; two buffers sized to the largest chunk seen so far (plus, for
+ * column-major chunks, one nrows x max(p, q) scratch), so the caller's chunk size bounds the device
+ * memory: 16 nrows (ldx + ldy) bytes.  Returns as soon as the chunk is on the device: the caller may
+ * reuse X, Y at once; the chunk's device work (column means, centring, the fp64 MFMA Gram -- option
+ * "gram_int8" is ignored here --, the merge into S) runs on a second HIP stream behind the next
+ * call's upload.  With center = 1 the merge is the pairwise update S += G_c + (N n_c / (N + n_c)) d d',
+ * d = chunk mean - running mean, with G_c the Gram of the chunk centred about its own mean -- not the
+ * one-pass S - N m m'.  Fixed-order sums: the same chunk sequence gives the same S bit for bit.  An
+ * asynchronous failure is reported by the next ppls_stream_* call; from then the stream is unusable
+ * (PPLS_E_STATE) until the next ppls_stream_begin. */
+int ppls_stream_rows(ppls_ctx* ctx, const double* X, const double* Y, int64_t nrows, int layout);
+/* All of src's resident rows as one chunk, device to device (fp32 storage is widened); src is left
+ * untouched.  PPLS_E_ARG: src on another device, without data, of another shape, or ctx itself. */
+int ppls_stream_rows_from(ppls_ctx* ctx, ppls_ctx* src);
+/* Close the stream.  Collective when sharded (RCCL or the host reducer; a rank that streamed no rows
+ * still joins): all-reduce {N_r, N_r m_r} -> the global N and mean m; each rank adds
+ * N_r (m_r - m)(m_r - m)' to its S; the ranks agree that nobody failed; one all-reduce of S.  scale = 1:
+ * d_j = sqrt(S_jj / (N - 1)), then S_ij <- S_ij / (d_i d_j) (exactly symmetric, padding zero);
+ * PPLS_E_ARG on every rank alike, with the stream dropped, for N < 2 or a d_j that is not > 0 or not
+ * finite (the message names the block and the 1-based column).  ||X||^2, ||Y||^2 are the traces of
+ * S's diagonal blocks; a NaN or Inf in any chunk makes them non-finite -> PPLS_E_ARG, stream dropped.
+ * Records the transform for ppls_get_scaling (center = m or 0, scale = d or 1).  Every error return
+ * drops the stream (no data afterwards); a HIP error on one rank is agreed on in the collectives, so
+ * every rank returns. */
+int ppls_stream_end(ppls_ctx* ctx);
+/* state: 0 none, 1 open, 2 streamed; rows_local / chunks: this rank's so far; n_total: rows over all
+ * ranks once streamed (while open: this rank's so far).  All nullable. */
+int ppls_stream_info(ppls_ctx* ctx, int* state, int64_t* rows_local, int64_t* n_total, int64_t* chunks);
+
 /* ---- host-side algebra (no GPU; the same code the device finalize runs) ------------------------ */
 /* From the all-reduced sufficient statistics of one sweep with theta (stats = [X'mu_T p x r |
  * Y'mu_U q x r | Gram 2r x 2r], all column-major) compute Expect_M's moments, logl_W(theta) and

@@ -99,6 +99,11 @@ int ppls_sweep_trace(ppls_ctx* ctx, int64_t* stamps, int cap, int* n, double* ti
  * scoring kernel read. */
 int ppls_cv_timing(ppls_ctx* ctx, double* out6, int reset);
 
+/* The cross-products S as the context holds them (ready: formed, prepared, downdated or streamed; else
+ * PPLS_E_STATE): *P = ldx + ldy and *ldx (X's padded width; Y's columns start there), and, if S is
+ * not null, the P x P doubles of S (row-major; symmetric, padding rows and columns included). */
+int ppls_xprod_get(ppls_ctx* ctx, double* S, int* P, int* ldx);
+
 /* The passes of the last ppls_scale_data on this context: {column sums, centred squares, apply},
  * X and Y together: ms3 from HIP events around the pass's kernels (0 for a pass that did not run),
  * bytes3 the bytes the pass read (the apply pass: read + written) on this rank. */

@@ -140,6 +140,12 @@ SIGNATURES = {
     "ppls_scale_data": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int]),
     "ppls_get_scaling": (ct.c_int, [ct.c_void_p, _dp, _dp]),
     "ppls_scale_timing": (ct.c_int, [ct.c_void_p, _dp, _dp]),
+    "ppls_xprod_get": (ct.c_int, [ct.c_void_p, _dp, ct.POINTER(ct.c_int), ct.POINTER(ct.c_int)]),
+    "ppls_stream_begin":(ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_int]),
+    "ppls_stream_rows": (ct.c_int, [ct.c_void_p, _dp, _dp, ct.c_int64, ct.c_int]),
+    "ppls_stream_rows_from": (ct.c_int, [ct.c_void_p, ct.c_void_p]),
+    "ppls_stream_end": (ct.c_int, [ct.c_void_p]),
+    "ppls_stream_info": (ct.c_int, [ct.c_void_p, ct.POINTER(ct.c_int), _i64p, _i64p, _i64p]),
 }
 
 

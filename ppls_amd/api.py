@@ -20,6 +20,7 @@ in the context (no copy), which is how multi-GPU shards and large synthetic prob
 from __future__ import annotations
 
 import ctypes as ct
+import itertools
 import math
 import time
 import warnings
@@ -201,6 +202,44 @@ class Context:
         self._chk(self._L.ppls_scale_timing(self.h, dptr(ms), dptr(by)))
         return dict(ms=ms, bytes=by)
 
+    # -- streamed data: S from row chunks, no rows resident
+    def stream_begin(self, p, q, center=False, scale=False):
+        """Open a stream of ``p + q`` columns (ppls_stream_begin): drops resident data and S.
+        ``center`` / ``scale`` as in R's ``scale()``, applied to the streamed rows as a whole."""
+        self._chk(self._L.ppls_stream_begin(self.h, int(p), int(q), int(bool(center)), int(bool(scale))))
+        self.p, self.q, self.n_local, self.n_total, self.row0 = int(p), int(q), 0, 0, 0
+
+    def stream_rows(self, X, Y):
+        """One chunk of rows (ppls_stream_rows): float64 matrices, C- or F-contiguous (both in the
+        same order are passed without a copy).  Returns once the chunk is on the device."""
+        X, Y, layout = _chunk_arrays(X, Y, self.p, self.q)
+        self._chk(self._L.ppls_stream_rows(self.h, dptr(X), dptr(Y), X.shape[0], layout))
+
+    def stream_rows_from(self, src: "Context"):
+        """All resident rows of ``src`` as one chunk, device to device; ``src`` is left untouched."""
+        self._chk(self._L.ppls_stream_rows_from(self.h, src.h))
+
+    def stream_end(self):
+        """Close the stream (ppls_stream_end; collective when sharded).  Returns ``dict(n, centerX,
+        scaleX, centerY, scaleY)``: the rows over all ranks and the transform S carries."""
+        self._chk(self._L.ppls_stream_end(self.h))
+        self.n_local, self.n_total = 0, self.stream_info()["n_total"]
+        out = dict(n=self.n_total)
+        out.update(self.scaling())
+        return out
+
+    def stream_info(self):
+        st = ct.c_int()
+        rows, nt, ch = ct.c_int64(), ct.c_int64(), ct.c_int64()
+        self._chk(self._L.ppls_stream_info(self.h, ct.byref(st), ct.byref(rows), ct.byref(nt), ct.byref(ch)))
+        return dict(state=("none", "open", "streamed")[st.value], rows_local=rows.value, n_total=nt.value,
+                    chunks=ch.value)
+
+    @property
+    def streamed(self):
+        """True when the context fits from streamed cross-products and holds no rows."""
+        return self.stream_info()["state"] == "streamed"
+
     # -- hot path
     def estep(self, th: Theta, want_mu=True) -> Expect:
         e = Expect(th.r, self.n_local, want_mu)
@@ -365,7 +404,10 @@ class Context:
         Returns (W, B_exp scalars, varMatrix a x p x p, seLoad p x a, SSt_exp, SSt_star) -- the
         last two (a x p x p) only with full=True."""
         # no copy when mu is already a column-major float64 n_local x a array (the fits' Expectations are)
-        mu = np.asfortranarray(np.asarray(mu, dtype=np.float64).reshape(self.n_local, -1))
+        mu = np.asarray(mu, dtype=np.float64)
+        if mu.ndim != 2 or mu.shape[0] != self.n_local:   # (a 0 x a matrix cannot be reshaped with -1)
+            mu = mu.reshape(self.n_local, -1)
+        mu = np.asfortranarray(mu)
         a = mu.shape[1]
         p = self.q if xory else self.p
         Cd = np.ascontiguousarray(np.ravel(Cdiag), dtype=np.float64)
@@ -446,6 +488,19 @@ class Context:
         """Free the cross-products S now (ppls_xprod_release; 8 (p+q)^2 bytes of HBM); the next run
         that reads S forms it again."""
         self._chk(self._L.ppls_xprod_release(self.h))
+
+    def xprod_matrix(self, padded=False):
+        """The cross-products S the context holds (formed, prepared, downdated or streamed):
+        ``(p + q) x (p + q)``, or with ``padded=True`` ``(S, ldx)`` -- the P x P matrix in the padded
+        layout (X's columns at [0, p), Y's at [ldx, ldx + q), zeros elsewhere)."""
+        P, ldx = ct.c_int(), ct.c_int()
+        self._chk(self._L.ppls_xprod_get(self.h, None, ct.byref(P), ct.byref(ldx)))
+        S = np.zeros((P.value, P.value))
+        self._chk(self._L.ppls_xprod_get(self.h, dptr(S), ct.byref(P), ct.byref(ldx)))
+        if padded:
+            return S, ldx.value
+        live = np.r_[np.arange(self.p), ldx.value + np.arange(self.q)]
+        return S[np.ix_(live, live)]
 
     def xprod_tile_timing(self, reps=200):
         """Average ms of the cross-product tile kernel over reps back-to-back launches (HIP events
@@ -907,6 +962,10 @@ def _ppls_o2m(ctx, a, steps, atol, constraints, crit_abs):
 
 
 def _joint_gram(ctx):
+    if ctx.streamed:
+        raise NotImplementedError("initialGuess='o2m' on a streamed context: the rows were streamed and are not "
+                                  "resident, and the joint Gram of raw rows is not kept; use 'equal', 'random' "
+                                  "or 'custom'")
     if ctx.n_local != ctx.n_total:
         raise NotImplementedError("initialGuess='o2m' on row shards: all-reduce the ranks' Context.gram(2) "
                                   "and call o2m_guess_from_gram")
@@ -1250,7 +1309,8 @@ def PPLS_simult(X, Y, a, EMsteps=10, atol=1e-4, type=("SVD", "QR"), init=None, c
     th = Theta(init["W"], init["C"], init["B"], init["sigE"], init["sigF"], init["sigH"], init["sigT"])
     if th.r != a:
         raise ValueError(f"init has {th.r} components, a = {a}")
-    est, ll, eout, neg = ctx.em_run(th, int(EMsteps), float(atol), t, want_eout=True, want_mu=True)
+    # streamed context: no rows, so Expectations carries the moments and mu_T = mu_U = None
+    est, ll, eout, neg = ctx.em_run(th, int(EMsteps), float(atol), t, want_eout=True, want_mu=not ctx.streamed)
     if neg:
         warnings.warn("Negative increments of likelihood")
     d = est.as_dict()
@@ -1274,6 +1334,45 @@ def scale_data(X=None, Y=None, center=True, scale=True, ctx=None):
     ctx = _ctx_with(X, Y, ctx)
     ctx.scale_data(center, scale)
     return ctx.scaling()
+
+
+def _chunk_arrays(X, Y, p=None, q=None):
+    """One chunk as float64 matrices in one memory order, and that order's layout code: F-contiguous
+    pairs go as they are (column-major), everything else C-contiguous (copied only if it is not)."""
+    X = np.asarray(X, dtype=np.float64)
+    Y = np.asarray(Y, dtype=np.float64)
+    if X.ndim != 2 or Y.ndim != 2 or X.shape[0] != Y.shape[0]:
+        raise ValueError("a chunk is a pair of matrices X, Y with the same number of rows")
+    if (p is not None and X.shape[1] != p) or (q is not None and Y.shape[1] != q):
+        raise ValueError(f"chunk of {X.shape[1]} + {Y.shape[1]} columns in a stream of {p} + {q}")
+    if X.flags.f_contiguous and Y.flags.f_contiguous and not (X.flags.c_contiguous and Y.flags.c_contiguous):
+        return X, Y, _lib.PPLS_LAYOUT_COLMAJOR
+    return np.ascontiguousarray(X), np.ascontiguousarray(Y), _lib.PPLS_LAYOUT_ROWMAJOR
+
+
+def stream_data(chunks, center=True, scale=True, ctx=None):
+    """Load data too large to hold at once: ``chunks`` is an iterable of ``(X, Y)`` row blocks (numpy
+    matrices, e.g. slices of a memory-mapped file).  Their cross-products -- of the rows centred and
+    scaled as R's ``scale()`` would the whole matrix -- are accumulated on the device; no rows stay
+    resident.  Returns ``dict(n, centerX, scaleX, centerY, scaleY)``.  Afterwards
+    ``PPLS(None, None, a, ctx=ctx)`` and ``PPLS_simult(None, None, a, ctx=ctx)`` fit from them."""
+    if isinstance(chunks, np.ndarray) or not hasattr(chunks, "__iter__"):
+        raise TypeError("chunks must be an iterable of (X, Y) pairs")
+    it = iter(chunks)
+    first = next(it, None)
+    if first is None:
+        raise ValueError("chunks is empty: no rows to stream")
+    p = q = None
+    for pair in itertools.chain([first], it):
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+            raise TypeError("every chunk must be an (X, Y) pair")
+        X, Y, _ = _chunk_arrays(pair[0], pair[1], p, q)   # (checked before a device is touched)
+        if p is None:
+            p, q = X.shape[1], Y.shape[1]
+            ctx = ctx or default_context()
+            ctx.stream_begin(p, q, center, scale)
+        ctx.stream_rows(X, Y)
+    return ctx.stream_end()
 
 
 # ---------------------------------------------------------------------------- cross-validation

@@ -26,6 +26,7 @@
 #include "ppls_math.h"
 #include "ppls_cv.h"
 #include "ppls_scale.h"
+#include "ppls_stream.h"
 #include "ppls_xprod.h"
 
 struct ppls_ctx {
@@ -182,6 +183,26 @@ struct ppls_ctx {
   std::vector<double> sc_center, sc_scale;
   double scale_ms[3] = {0, 0, 0};
   double scale_bytes[3] = {0, 0, 0};
+  // streamed data (ppls_stream_*): S and the column means accumulated from row chunks, no rows
+  // resident.  A chunk is staged in one of two fp64 device buffers (each [X rows | Y rows] in the
+  // padded row layout, sized for the largest chunk seen); its device work runs on st_stream while
+  // the next chunk uploads on `stream`, st_done[b] marking buffer b free again.
+  int st_state = 0;          // 0 none, 1 open (between begin and end), 2 streamed (fits read S only)
+  bool st_failed = false;    // an open stream hit an error: PPLS_E_STATE until the next ppls_stream_begin
+  int st_center = 0, st_scale = 0;
+  int64_t st_rows = 0, st_chunks = 0;   // this rank's rows and chunks so far
+  hipStream_t st_stream = nullptr;
+  hipEvent_t st_done[2] = {nullptr, nullptr};
+  double* st_buf[2] = {nullptr, nullptr};
+  int64_t st_cap = 0;        // rows a staging buffer holds
+  int st_next = 0;           // the buffer the next chunk goes to
+  double* st_cm = nullptr;   // column-major upload scratch (rows x max(p, q))
+  int64_t st_cm_len = 0;
+  double* st_vec = nullptr;  // joint-layout vectors of P: chunk sums, chunk mean, delta, mean, ones; then P + 2 for reductions
+  double* st_part = nullptr; // the chunk Gram's split partials
+  int64_t st_part_len = 0;
+  double* st_colpart = nullptr;   // the column sums' row-block partials
+  int64_t st_colpart_len = 0;
 };
 
 namespace {
@@ -572,8 +593,28 @@ int timing_pair(ppls_ctx* c, hipEvent_t* e0, hipEvent_t* e1) {
 
 // One sweep with theta[slot] -> c->stats (all-reduced).  mu_only: just this rank's mu rows (the
 // statistics are not reduced: no collective).
+int xprod_stats(ppls_ctx* c, int r, int slot, bool fuse = false);
+
+#define PPLS_STREAMED_MSG "the rows were streamed and are not resident"
+#define NEED_ROWS(c)                                                        \
+  do {                                                                      \
+    if ((c)->st_state == 2) return fail((c), PPLS_E_STATE, PPLS_STREAMED_MSG); \
+  } while (0)
+
+// The ranks of an open stream hold half-accumulated S, N and means: what ppls_stream_end's
+// collectives run over cannot change under them.
+#define NOT_WHILE_OPEN(c, what)                                                                          \
+  do {                                                                                                   \
+    if ((c)->st_state == 1)                                                                              \
+      return fail((c), PPLS_E_STATE, "a stream is open: %s cannot change before ppls_stream_end", what); \
+  } while (0)
+
 int sweep(ppls_ctx* c, int r, int slot, bool write_mu, bool mu_only = false) {
   int rc;
+  if (c->st_state == 2) {   // streamed: the statistics come from S, never from the zero resident rows
+    if (write_mu || mu_only || c->seg_rows >= 0) return fail(c, PPLS_E_STATE, PPLS_STREAMED_MSG);
+    return xprod_stats(c, r, slot, false);
+  }
   PplsSweepArgs a;
   const int plan = sweep_plan(c, r, &a);
   const int64_t nrows = sweep_rows(c);
@@ -707,18 +748,23 @@ GramShape gram_shape(const ppls_ctx* c, bool joint, int xory) {
   return GramShape{p, p, ld, 0, xory ? (const void*)c->Y : (const void*)c->X, ld, nullptr, 0, 0};
 }
 
-int gram_wave_slots(const ppls_ctx* c) { return c->num_cus * ppls_gram_occupancy(c->dtype) * 4; }
+// f32: the storage type of the rows the Gram reads (-1: the context's resident rows, option dtype;
+// the streamed chunks are staged in fp64 whatever that option holds and pass 0)
+int gram_wave_slots(const ppls_ctx* c, int f32 = -1) {
+  return c->num_cus * ppls_gram_occupancy(f32 < 0 ? c->dtype : f32) * 4;
+}
 
 // Row splits of a Gram over n rows (0 = auto: halving splits, ppls_gram_plan).
-int gram_nsplit(const ppls_ctx* c, const GramShape& g, int64_t n, int req) {
-  return ppls_gram_plan(g.p, g.xreal, g.xcols, g.yreal, n, gram_wave_slots(c), req, nullptr);
+int gram_nsplit(const ppls_ctx* c, const GramShape& g, int64_t n, int req, int f32 = -1) {
+  return ppls_gram_plan(g.p, g.xreal, g.xcols, g.yreal, n, gram_wave_slots(c, f32), req, nullptr);
 }
 
 // The Gram's work queue for (shape, n, req, split plan, wave slots), prepared once and kept while
-// all of them repeat.
-int gram_queue(ppls_ctx* c, const GramShape& g, int64_t n, int req, int** q) {
-  const int nsplit = gram_nsplit(c, g, n, req);
-  const int64_t key[8] = {g.p, g.xreal, g.xcols, g.yreal, n, req, nsplit, gram_wave_slots(c)};
+// all of them repeat.  drain: a stream whose launches may still read the kept queue (the streamed
+// chunks' second stream); it is synchronised before the queue is rebuilt.
+int gram_queue(ppls_ctx* c, const GramShape& g, int64_t n, int req, int** q, int f32 = -1, hipStream_t drain = nullptr) {
+  const int nsplit = gram_nsplit(c, g, n, req, f32);
+  const int64_t key[8] = {g.p, g.xreal, g.xcols, g.yreal, n, req, nsplit, gram_wave_slots(c, f32)};
   if (c->gram_q && !memcmp(key, c->gq_key, sizeof key)) {
     *q = c->gram_q;
     return PPLS_OK;
@@ -726,8 +772,9 @@ int gram_queue(ppls_ctx* c, const GramShape& g, int64_t n, int req, int** q) {
   *q = nullptr;
   int rc;
   c->gq_key[0] = -1;
+  if (drain) HIPCHK(c, hipStreamSynchronize(drain));
   if ((rc = dalloc(c, &c->gram_q, (size_t)ppls_gram_queue_ints(g.p, nsplit)))) return rc;
-  HIPCHK(c, ppls_gram_queue_prepare(c->gram_q, g.p, g.xreal, g.xcols, g.yreal, n, gram_wave_slots(c), req, c->stream));
+  HIPCHK(c, ppls_gram_queue_prepare(c->gram_q, g.p, g.xreal, g.xcols, g.yreal, n, gram_wave_slots(c, f32), req, c->stream));
   memcpy(c->gq_key, key, sizeof key);
   *q = c->gram_q;
   return PPLS_OK;
@@ -992,6 +1039,7 @@ int xprod_setup(ppls_ctx* c) {
 // every rank of a sharded run takes the same path and issues the same collectives.  Memory gate:
 // S, its Gram partials and M (xprod_bytes) within the smallest free HBM less max(1 GiB, 5 %).
 bool xprod_choose(ppls_ctx* c, int max_steps, int r) {
+  if (c->st_state == 2) return true;   // streamed: S is all there is, whatever the option says
   if (c->xprod == 0) return false;
   if (c->xprod == 1) return true;   // forced: xprod_setup reports a failed allocation (all ranks alike)
   if (!c->xp_ready && xprod_bytes(c) > c->mem_free_min - std::max(1073741824.0, 0.05 * c->mem_free_min))
@@ -1013,7 +1061,7 @@ bool xprod_choose(ppls_ctx* c, int max_steps, int r) {
 // One statistics step from S: c->stats for theta[slot] (no collective: S is global).  fuse: a
 // finalize follows, which may form the Gram itself (its scalar block runs in the polar blocks'
 // slack: C3 ~2 us of it against the Gram kernel's 4 us + a launch boundary).
-int xprod_stats(ppls_ctx* c, int r, int slot, bool fuse = false) {
+int xprod_stats(ppls_ctx* c, int r, int slot, bool fuse) {
   int rc;
   const int P = c->ldx + c->ldy;
   if (!c->xp_ready && (rc = xprod_setup(c))) return rc;
@@ -1068,7 +1116,27 @@ int check_status(ppls_ctx* c) {
   return PPLS_OK;
 }
 
+// End a stream (open or finished): wait for its device work, free the staging buffers.  S itself is
+// xprod_free's.
+void stream_release(ppls_ctx* c) {
+  if (c->st_stream) (void)hipStreamSynchronize(c->st_stream);
+  (void)hipGetLastError();
+  for (int b = 0; b < 2; ++b) dfree(c->st_buf[b]);
+  dfree(c->st_cm);
+  dfree(c->st_vec);
+  dfree(c->st_part);
+  dfree(c->st_colpart);
+  c->st_cap = c->st_cm_len = c->st_part_len = c->st_colpart_len = 0;
+  c->st_state = 0;
+  c->st_failed = false;
+}
+
 void xprod_free(ppls_ctx* c) {
+  if (c->st_state) {   // S is all a streamed (or streaming) context has: without it there is no data
+    stream_release(c);
+    c->have_data = false;
+    c->em_active = false;
+  }
   c->xp_ready = false;
   c->xp_explicit = false;
   c->xp_active = false;
@@ -1150,6 +1218,7 @@ int check_fit_data(ppls_ctx* c) {
 int alloc_data(ppls_ctx* c, int64_t n_local, int p, int q, int64_t n_total) {
   int rc;
   c->em_active = false;
+  if (c->st_state) xprod_free(c);   // new data end a stream and the streamed state
   if (n_local < 0 || p < 1 || q < 1) return fail(c, PPLS_E_ARG, "bad shape n=%lld p=%d q=%d", (long long)n_local, p, q);
   c->n_local = n_local;
   c->n_total = n_total > 0 ? n_total : n_local;
@@ -1313,6 +1382,11 @@ void ppls_ctx_destroy(ppls_ctx* c) {
   if (c->ftrace) (void)hipFree(c->ftrace);
   if (c->strace) (void)hipFree(c->strace);
   dfree(c->stop_d);
+  c->st_state = 0;
+  stream_release(c);
+  for (int b = 0; b < 2; ++b)
+    if (c->st_done[b]) (void)hipEventDestroy(c->st_done[b]);
+  if (c->st_stream) (void)hipStreamDestroy(c->st_stream);
   dfree(c->xp_S);
   dfree(c->xp_M);
   oz_free(c);
@@ -1389,6 +1463,9 @@ int ppls_set_option(ppls_ctx* c, const char* key, int64_t value) {
   } else if (!strcmp(key, "dtype")) {
     if (value != 0 && value != 1) return fail(c, PPLS_E_ARG, "dtype must be 0 (fp64) or 1 (fp32 storage)");
     if (c->dtype != (int)value) {
+      // a change would ask for the rows again: a streamed context has none, an open stream's layout is fixed
+      if (c->st_state == 2) return fail(c, PPLS_E_STATE, PPLS_STREAMED_MSG);
+      if (c->st_state == 1) return fail(c, PPLS_E_STATE, "a stream is open: dtype cannot change before ppls_stream_end");
       c->dtype = (int)value;
       c->have_data = false;   // the data must be (re)loaded in the new storage type
     }
@@ -1399,7 +1476,7 @@ int ppls_set_option(ppls_ctx* c, const char* key, int64_t value) {
     if (value < -1 || value > 1) return fail(c, PPLS_E_ARG, "xprod must be -1 (auto), 0 (stream X, Y) or 1 (cross-products)");
     // the path of an ppls_em_begin session is fixed at em_begin: a session on S does not switch to
     // streaming under it -- xprod = 0 ends it (ppls_em_iterate then asks for ppls_em_begin)
-    if (value == 0 && c->em_active && c->xp_active) {
+    if (value == 0 && c->em_active && c->xp_active && c->st_state != 2) {
       c->em_active = false;
       c->xp_active = false;
     }
@@ -1407,7 +1484,7 @@ int ppls_set_option(ppls_ctx* c, const char* key, int64_t value) {
     c->xprod = (int)value;
     // streaming from now on: S's 8 (p+q)^2 bytes go back -- unless S came from ppls_xprod_prepare
     // (kept for variances() and later runs until ppls_xprod_release)
-    if (value == 0 && was != 0 && !c->xp_explicit) {
+    if (value == 0 && was != 0 && !c->xp_explicit && c->st_state == 0) {
       HIPCHK(c, hipStreamSynchronize(c->stream));
       xprod_free(c);
     }
@@ -1466,6 +1543,8 @@ int ppls_comm_unique_id(char id[128]) {
 int ppls_comm_init(ppls_ctx* c, int nranks, int rank, const char id[128]) {
   if (!c || nranks < 1 || rank < 0 || rank >= nranks) return PPLS_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
+  NEED_ROWS(c);   // ||X||^2, ||Y||^2 would be re-reduced from the rows
+  NOT_WHILE_OPEN(c, "the communicator");
   if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
   if (nranks > 1 && !id) return fail(c, PPLS_E_ARG, "nranks=%d needs the root's unique id", nranks);
   c->nranks = nranks;
@@ -1481,6 +1560,8 @@ int ppls_comm_init(ppls_ctx* c, int nranks, int rank, const char id[128]) {
 
 int ppls_set_reducer(ppls_ctx* c, ppls_reduce_fn fn, void* user) {
   if (!c) return PPLS_E_ARG;
+  NEED_ROWS(c);
+  NOT_WHILE_OPEN(c, "the reducer");
   HIPCHK(c, hipSetDevice(c->device));
   c->reducer = fn;
   c->reducer_user = user;
@@ -1611,6 +1692,7 @@ int ppls_philox4x32_10(ppls_ctx* c, const uint32_t* ctr, int64_t count, uint64_t
 int ppls_get_data_rows(ppls_ctx* c, double* X, double* Y, int64_t row_begin, int64_t nrows) {
   if (!c) return PPLS_E_ARG;
   if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
   if (row_begin < 0 || nrows < 0 || row_begin + nrows > c->n_local) return fail(c, PPLS_E_ARG, "bad row range");
   if (nrows == 0) return PPLS_OK;
   HIPCHK(c, hipSetDevice(c->device));
@@ -1647,6 +1729,7 @@ int ppls_get_data_rows(ppls_ctx* c, double* X, double* Y, int64_t row_begin, int
 int ppls_get_data(ppls_ctx* c, double* X, double* Y, int64_t row_begin, int64_t nrows) {
   if (!c) return PPLS_E_ARG;
   if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
   if (row_begin < 0 || nrows < 0 || row_begin + nrows > c->n_local) return fail(c, PPLS_E_ARG, "bad row range");
   if (nrows == 0) return PPLS_OK;
   HIPCHK(c, hipSetDevice(c->device));
@@ -1687,6 +1770,7 @@ int ppls_estep(ppls_ctx* c, const ppls_theta* th, int r, ppls_expect* out) {
   if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
   int rc;
   if ((rc = check_theta(c, th, r))) return rc;
+  if (out && (out->mu_T || out->mu_U)) NEED_ROWS(c);
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = ensure_r(c, r, 1))) return rc;
   if ((rc = upload_theta(c, th, r, 0))) return rc;
@@ -1705,6 +1789,7 @@ int ppls_em_step(ppls_ctx* c, const ppls_theta* in, int r, int type, ppls_theta*
   int rc;
   if ((rc = check_theta(c, in, r))) return rc;
   if (!out || !out->W || !out->C || !out->B || !out->sigT) return fail(c, PPLS_E_ARG, "NULL output theta");
+  if (fit && (fit->mu_T || fit->mu_U)) NEED_ROWS(c);
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = ensure_r(c, r, 1))) return rc;
   if ((rc = upload_theta(c, in, r, 0))) return rc;
@@ -1722,6 +1807,7 @@ int ppls_em_step(ppls_ctx* c, const ppls_theta* in, int r, int type, ppls_theta*
 int ppls_mstep(ppls_ctx* c, const ppls_expect* fit, int r, int type, ppls_theta* out) {
   if (!c) return PPLS_E_ARG;
   if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);   // X'mu_T and Y'mu_U of caller-supplied mu need the rows
   if (!fit || !fit->mu_T || !fit->mu_U || !fit->Ctt || !fit->Cut || !fit->Chh)
     return fail(c, PPLS_E_ARG, "Maximiz_M needs mu_T, mu_U, Ctt, Cut, Cee, Cff, Chh");
   if (!out || !out->W || !out->C || !out->B || !out->sigT) return fail(c, PPLS_E_ARG, "NULL output theta");
@@ -1808,6 +1894,7 @@ int ppls_em_run(ppls_ctx* c, ppls_theta* th, int r, int max_steps, double atol, 
   if ((rc = check_theta(c, th, r))) return rc;
   if (max_steps < 1) return fail(c, PPLS_E_ARG, "EMsteps must be >= 1");
   if (type != PPLS_ORTH_SVD && type != PPLS_ORTH_QR) return fail(c, PPLS_E_ARG, "type must be SVD (0) or QR (1)");
+  if (eout && (eout->mu_T || eout->mu_U)) NEED_ROWS(c);
   if ((rc = check_fit_data(c))) return rc;
   if (!theta_finite(th, c->p, c->q, r)) return fail(c, PPLS_E_ARG, "theta0 has non-finite entries");
   HIPCHK(c, hipSetDevice(c->device));
@@ -2255,9 +2342,10 @@ int ppls_ppls_ex(ppls_ctx* c, int a, int max_steps, double atol, int crit_abs, c
     }
     Wp.insert(Wp.end(), t.w.begin(), t.w.end());
     Cp.insert(Cp.end(), t.c.begin(), t.c.end());
-    if (k + 1 < a && ssqX < 1e-6 * c->ssq_host[0])
+    // (streamed data: no rows for the exact residual pass; the running difference stands)
+    if (k + 1 < a && ssqX < 1e-6 * c->ssq_host[0] && c->st_state != 2)
       if ((rc = deflated_ssq(c, Wp, k + 1, true, &ssqX))) return rc;
-    if (k + 1 < a && ssqY < 1e-6 * c->ssq_host[1])
+    if (k + 1 < a && ssqY < 1e-6 * c->ssq_host[1] && c->st_state != 2)
       if ((rc = deflated_ssq(c, Cp, k + 1, false, &ssqY))) return rc;
     out->ncomp = k + 1;
     // Other_output$Loglikelihoods[k] = logl_W(X, Y, W[,1:k], C[,1:k], diag(B[1:k]), sigX_k, sigY_k,
@@ -2661,6 +2749,7 @@ int ppls_meta_emstep(ppls_ctx* c, int npop, const int64_t* pop_local, const int6
                      double* Cxt, double* Cyu) {
   if (!c) return PPLS_E_ARG;
   if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
   if (!W || !C || !params_in || !W_out || !C_out || !params_out) return fail(c, PPLS_E_ARG, "NULL argument");
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
@@ -2691,6 +2780,7 @@ int ppls_meta_ppls(ppls_ctx* c, int npop, const int64_t* pop_local, const int64_
                    double atol, int crit_abs, const ppls_theta* init, ppls_meta_fit* out) {
   if (!c) return PPLS_E_ARG;
   if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
   if (!init || !init->W || !init->C || !init->B || !init->sigT || !out || !out->W || !out->C || !out->params)
     return fail(c, PPLS_E_ARG, "NULL argument");
   if (max_steps < 1) return fail(c, PPLS_E_ARG, "EMsteps must be >= 1");
@@ -2760,6 +2850,7 @@ int ppls_variances(ppls_ctx* c, const double* mu, const double* Cdiag, double si
                    double* B_exp, double* varMatrix, double* SSt_exp, double* SSt_star, double* seLoad) {
   if (!c) return PPLS_E_ARG;
   if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
   if ((!mu && c->n_local > 0) || !Cdiag || !W || !B_exp || !seLoad) return fail(c, PPLS_E_ARG, "NULL argument");
   if (a < 1 || a > 16) return fail(c, PPLS_E_ARG, "number of components %d outside [1, 16]", a);
   if (xory != 0 && xory != 1) return fail(c, PPLS_E_ARG, "XorY must be 0 (\"X\") or 1 (\"Y\")");
@@ -2997,6 +3088,7 @@ int ppls_spd_inverse(ppls_ctx* c, const double* A, int p, int a, int method, dou
 int ppls_gram(ppls_ctx* c, int xory, int nsplit, double* G, double* ms) {
   if (!c) return PPLS_E_ARG;
   if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
   if (xory < 0 || xory > 2) return fail(c, PPLS_E_ARG, "xory must be 0 (X'X), 1 (Y'Y) or 2 ([X Y]'[X Y])");
   HIPCHK(c, hipSetDevice(c->device));
   const GramShape g = xory == 2 ? gram_shape(c, true, 0) : gram_shape(c, false, xory);
@@ -3034,6 +3126,7 @@ int ppls_gram(ppls_ctx* c, int xory, int nsplit, double* G, double* ms) {
 int ppls_scores(ppls_ctx* c, const double* W, const double* C, int k, double* T, double* U) {
   if (!c) return PPLS_E_ARG;
   if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
   if (!W || !C || k < 1 || k > PPLS_RMAX) return fail(c, PPLS_E_ARG, "W, C must be given with 1 <= k <= %d", PPLS_RMAX);
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
@@ -3184,6 +3277,20 @@ int ppls_xprod_release(ppls_ctx* c) {
   return PPLS_OK;
 }
 
+int ppls_xprod_get(ppls_ctx* c, double* S, int* P, int* ldx) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data || !c->xp_ready || !c->xp_S) return fail(c, PPLS_E_STATE, "no cross-products S are ready");
+  const int PP = c->ldx + c->ldy;
+  if (P) *P = PP;
+  if (ldx) *ldx = c->ldx;
+  if (S) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(S, c->xp_S, sizeof(double) * PP * PP, hipMemcpyDeviceToHost));
+  }
+  return PPLS_OK;
+}
+
 int ppls_xprod_setup_times(ppls_ctx* c, double* gram_ms, double* allreduce_ms, double* total_ms) {
   if (!c) return PPLS_E_ARG;
   if (gram_ms) *gram_ms = c->xp_setup_ms;
@@ -3317,6 +3424,7 @@ int ppls_sweep_info(ppls_ctx* c, int r, int64_t* bytes_per_sweep, int* variant, 
 int ppls_gram_int8(ppls_ctx* c, int which, double* G, int* nmod, int* L, double* ms) {
   if (!c) return PPLS_E_ARG;
   if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
   if (which < 0 || which > 2) return fail(c, PPLS_E_ARG, "which must be 0 (X), 1 (Y) or 2 (joint [X Y])");
   if (c->n_local <= 0) return fail(c, PPLS_E_STATE, "no rows on this rank");
   HIPCHK(c, hipSetDevice(c->device));
@@ -3565,6 +3673,7 @@ int ppls_set_data_from(ppls_ctx* dst, ppls_ctx* src, const int64_t* rows, int64_
   if (!dst || !src) return dst ? fail(dst, PPLS_E_ARG, "NULL source context") : PPLS_E_ARG;
   if (dst == src) return fail(dst, PPLS_E_ARG, "source and destination are the same context");
   if (!src->have_data) return fail(dst, PPLS_E_ARG, "the source context has no data");
+  if (src->st_state == 2) return fail(dst, PPLS_E_STATE, PPLS_STREAMED_MSG);
   if (dst->device != src->device)
     return fail(dst, PPLS_E_ARG, "contexts on different devices (%d, %d)", dst->device, src->device);
   int rc;
@@ -3597,6 +3706,7 @@ int ppls_xprod_downdate(ppls_ctx* dst, ppls_ctx* src, const int64_t* out_rows, i
   if (!dst || !src) return dst ? fail(dst, PPLS_E_ARG, "NULL source context") : PPLS_E_ARG;
   if (dst == src) return fail(dst, PPLS_E_ARG, "source and destination are the same context");
   if (!src->have_data || !dst->have_data) return fail(dst, PPLS_E_STATE, "no data");
+  if (src->st_state == 2 || dst->st_state == 2) return fail(dst, PPLS_E_STATE, PPLS_STREAMED_MSG);
   if (dst->device != src->device)
     return fail(dst, PPLS_E_ARG, "contexts on different devices (%d, %d)", dst->device, src->device);
   if (dst->p != src->p || dst->q != src->q || dst->ldx != src->ldx || dst->ldy != src->ldy || dst->dtype != src->dtype)
@@ -3751,6 +3861,7 @@ int ppls_heldout_sse(ppls_ctx* c, const double* W, const double* C, const double
                      int64_t nrows, double* sse) {
   if (!c) return PPLS_E_ARG;
   if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
   if (!W || !C || !B || !sse || k < 1 || k > PPLS_RMAX)
     return fail(c, PPLS_E_ARG, "W, C, B, sse must be given with 1 <= k <= %d", PPLS_RMAX);
   int rc;
@@ -3786,6 +3897,7 @@ int ppls_cv_ppls(ppls_ctx* c, int a, int nfolds, const int32_t* fold_of_row, con
                  double atol, int crit_abs, const ppls_theta* init, double* rmsep, int* ncomp) {
   if (!c) return PPLS_E_ARG;
   if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
   if (!fold_total || !init || !rmsep || !ncomp || (c->n_local > 0 && !fold_of_row)) return fail(c, PPLS_E_ARG, "NULL argument");
   if (a < 1 || a > PPLS_RMAX) return fail(c, PPLS_E_ARG, "nr_comp=%d outside [1,%d]", a, PPLS_RMAX);
   if (nfolds < 2) return fail(c, PPLS_E_ARG, "Cross-validation with 1 fold does not make sense, use 2 folds or more");
@@ -3927,6 +4039,7 @@ extern "C" {
 int ppls_scale_data(ppls_ctx* c, int center, int scale) {
   if (!c) return PPLS_E_ARG;
   if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
   if (!center && !scale) return PPLS_OK;
   // n_total is the same on every rank, so this refusal needs no collective
   if (scale && c->n_total < 2)
@@ -4024,6 +4137,378 @@ int ppls_scale_timing(ppls_ctx* c, double* ms3, double* bytes3) {
     if (ms3) ms3[k] = c->scale_ms[k];
     if (bytes3) bytes3[k] = c->scale_bytes[k];
   }
+  return PPLS_OK;
+}
+
+}  // extern "C"
+
+// ============================================================================ streamed data
+// ppls_stream_begin / _rows / _rows_from / _end: S = [X Y]'[X Y] of the centred (and scaled) data from
+// row chunks.  Per chunk, on st_stream: column means (the fixed-order column sums of
+// ppls_scale.hip), the staged chunk centred about its own mean, its MFMA Gram into split partials, and
+// one pass over S that sums the partials in and adds Chan's pairwise term
+// (N n_c / (N + n_c)) delta delta', delta = chunk mean - running mean.  The scaling is applied to S
+// at the end: S_ij / (d_i d_j).
+namespace {
+
+int stream_fail(ppls_ctx* c, int rc) {
+  c->st_failed = true;
+  return rc;
+}
+
+#define STREAMCHK(c, call)                                                                              \
+  do {                                                                                                  \
+    hipError_t e_ = (call);                                                                             \
+    if (e_ != hipSuccess)                                                                               \
+      return stream_fail((c), fail((c), PPLS_E_HIP, "%s: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__)); \
+  } while (0)
+
+int stream_open_check(ppls_ctx* c) {
+  if (c->st_state != 1) return fail(c, PPLS_E_STATE, "no stream is open: call ppls_stream_begin first");
+  if (c->st_failed)
+    return fail(c, PPLS_E_STATE, "the stream failed earlier and is unusable until the next ppls_stream_begin");
+  return PPLS_OK;
+}
+
+// Grow a device buffer the chunk work uses: wait for that work first.
+int stream_grow(ppls_ctx* c, double** buf, int64_t* len, int64_t need) {
+  if (*buf && *len >= need) return PPLS_OK;
+  STREAMCHK(c, hipStreamSynchronize(c->st_stream));
+  *len = 0;
+  const int rc = dalloc(c, buf, (size_t)need);
+  if (rc) return stream_fail(c, rc);
+  *len = need;
+  return PPLS_OK;
+}
+
+// Room for a chunk of n rows in both staging buffers (and the column-major scratch); returns with the
+// buffer the chunk goes to free.
+int stream_reserve(ppls_ctx* c, int64_t n, bool colmajor) {
+  int rc;
+  if (n > c->st_cap) {
+    STREAMCHK(c, hipStreamSynchronize(c->st_stream));
+    c->st_cap = 0;
+    for (int b = 0; b < 2; ++b)
+      if ((rc = dalloc(c, &c->st_buf[b], (size_t)n * (c->ldx + c->ldy)))) return stream_fail(c, rc);
+    c->st_cap = n;
+  }
+  if (colmajor && (rc = stream_grow(c, &c->st_cm, &c->st_cm_len, n * std::max(c->p, c->q)))) return rc;
+  // an asynchronous failure of the chunk that last used this buffer surfaces here
+  STREAMCHK(c, hipEventSynchronize(c->st_done[c->st_next]));
+  return PPLS_OK;
+}
+
+// The device work of the chunk staged in buffer b (n rows), enqueued on st_stream.
+int stream_process(ppls_ctx* c, int b, int64_t n) {
+  int rc;
+  const int P = c->ldx + c->ldy;
+  hipStream_t s = c->st_stream;
+  double* Xs = c->st_buf[b];
+  double* Ys = Xs + c->st_cap * c->ldx;
+  double *sum = c->st_vec, *mc = sum + P, *delta = mc + P, *mean = delta + P, *ones = mean + P;
+  const double N = (double)c->st_rows, nc = (double)n;
+  if (c->st_center) {
+    const PplsScalePlan px = ppls_scale_plan(n, c->p, 0, c->num_cus), py = ppls_scale_plan(n, c->q, 0, c->num_cus);
+    const int64_t plen = std::max(px.nblocks * px.ldc, py.nblocks * py.ldc);
+    if ((rc = stream_grow(c, &c->st_colpart, &c->st_colpart_len, plen))) return rc;
+    STREAMCHK(c, ppls_launch_col_partials(Xs, c->ldx, n, 0, &px, nullptr, 0, 0, c->st_colpart, s));
+    STREAMCHK(c, ppls_launch_col_reduce(c->st_colpart, &px, c->p, sum, s));
+    STREAMCHK(c, ppls_launch_col_partials(Ys, c->ldy, n, 0, &py, nullptr, 0, 0, c->st_colpart, s));
+    STREAMCHK(c, ppls_launch_col_reduce(c->st_colpart, &py, c->q, sum + c->ldx, s));
+    STREAMCHK(c, ppls_launch_stream_mean(sum, P, c->p, c->ldx, c->q, nc, N, mc, delta, mean, s));
+    STREAMCHK(c, ppls_launch_col_apply(Xs, c->ldx, n, c->p, 0, &px, mc, ones, 0, s));
+    STREAMCHK(c, ppls_launch_col_apply(Ys, c->ldy, n, c->q, 0, &py, mc + c->ldx, ones + c->ldx, 0, s));
+  }
+  const GramShape g{P, c->p, c->ldx, c->q, Xs, c->ldx, Ys, c->ldy, c->ldy};
+  const int nsplit = gram_nsplit(c, g, n, 0, 0);   // the staged chunk is fp64
+  if ((rc = stream_grow(c, &c->st_part, &c->st_part_len, ppls_gram_part_doubles(P, nsplit)))) return rc;
+  int* q = nullptr;
+  if ((rc = gram_queue(c, g, n, 0, &q, 0, s))) return stream_fail(c, rc);
+  STREAMCHK(c, ppls_launch_gram_joint(Xs, c->ldx, c->ldx, c->p, Ys, c->ldy, c->ldy, c->q, 0, n, P, nsplit, c->st_part, q, s));
+  STREAMCHK(c, ppls_launch_stream_merge(c->xp_S, c->p, c->ldx, c->q, c->ldy, c->st_part, nsplit,
+                                        c->st_center ? delta : nullptr, N * nc / (N + nc), s));
+  STREAMCHK(c, hipEventRecord(c->st_done[b], s));
+  c->st_next = b ^ 1;
+  c->st_rows += n;
+  ++c->st_chunks;
+  return PPLS_OK;
+}
+
+// Drop a stream that ppls_stream_end refuses: no data afterwards.
+int stream_refuse(ppls_ctx* c, int rc) {
+  xprod_free(c);   // (st_state != 0: releases the stream, clears have_data)
+  c->have_data = false;
+  return rc;
+}
+
+bool st_collective(const ppls_ctx* c) { return c->nranks > 1 || c->reducer; }
+
+}  // namespace
+
+extern "C" {
+
+int ppls_stream_begin(ppls_ctx* c, int p, int q, int center, int scale) {
+  if (!c) return PPLS_E_ARG;
+  if ((center != 0 && center != 1) || (scale != 0 && scale != 1)) return fail(c, PPLS_E_ARG, "center and scale must be 0 or 1");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int rc;
+  if ((rc = alloc_data(c, 0, p, q, 0))) return rc;   // drops resident rows, a stream, an EM session
+  xprod_free(c);
+  if (!c->st_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->st_stream, hipStreamNonBlocking));
+  for (int b = 0; b < 2; ++b)
+    if (!c->st_done[b]) HIPCHK(c, hipEventCreateWithFlags(&c->st_done[b], hipEventDisableTiming));
+  const int P = c->ldx + c->ldy;
+  if ((rc = dalloc(c, &c->xp_S, (size_t)P * P))) return rc;
+  if ((rc = dalloc(c, &c->st_vec, (size_t)6 * P + 8))) { dfree(c->xp_S); return rc; }
+  std::vector<double> v((size_t)6 * P + 8, 0.0);
+  std::fill(v.begin() + (size_t)4 * P, v.begin() + (size_t)5 * P, 1.0);
+  hipError_t e = hipMemsetAsync(c->xp_S, 0, sizeof(double) * P * P, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(c->st_vec, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  for (int b = 0; b < 2 && e == hipSuccess; ++b) e = hipEventRecord(c->st_done[b], c->st_stream);
+  if (e != hipSuccess) {
+    dfree(c->xp_S);
+    dfree(c->st_vec);
+    return fail(c, PPLS_E_HIP, "ppls_stream_begin: %s", hipGetErrorString(e));
+  }
+  c->st_center = center;
+  c->st_scale = scale;
+  c->st_rows = c->st_chunks = 0;
+  c->st_next = 0;
+  c->st_failed = false;
+  c->st_state = 1;
+  return PPLS_OK;
+}
+
+int ppls_stream_rows(ppls_ctx* c, const double* X, const double* Y, int64_t nrows, int layout) {
+  if (!c) return PPLS_E_ARG;
+  int rc;
+  if ((rc = stream_open_check(c))) return rc;
+  if (nrows == 0) return PPLS_OK;
+  if (nrows < 0 || !X || !Y) return fail(c, PPLS_E_ARG, "a chunk needs nrows >= 1 and X, Y");
+  if (layout != PPLS_LAYOUT_COLMAJOR && layout != PPLS_LAYOUT_ROWMAJOR)
+    return fail(c, PPLS_E_ARG, "layout must be 0 (column-major) or 1 (row-major)");
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = stream_reserve(c, nrows, layout == PPLS_LAYOUT_COLMAJOR))) return rc;
+  const int b = c->st_next;
+  for (int m = 0; m < 2; ++m) {
+    const double* src = m == 0 ? X : Y;
+    const int cols = m == 0 ? c->p : c->q, ld = m == 0 ? c->ldx : c->ldy;
+    double* dst = c->st_buf[b] + (m == 0 ? 0 : c->st_cap * c->ldx);
+    if (layout == PPLS_LAYOUT_ROWMAJOR) {
+      if (ld != cols) STREAMCHK(c, hipMemset2DAsync(dst, sizeof(double) * ld, 0, sizeof(double) * ld, nrows, c->stream));
+      STREAMCHK(c, hipMemcpy2DAsync(dst, sizeof(double) * ld, src, sizeof(double) * cols, sizeof(double) * cols, nrows,
+                                    hipMemcpyHostToDevice, c->stream));
+    } else {
+      STREAMCHK(c, hipMemcpyAsync(c->st_cm, src, sizeof(double) * nrows * cols, hipMemcpyHostToDevice, c->stream));
+      STREAMCHK(c, ppls_launch_to_rowmajor(c->st_cm, nrows, cols, ld, dst, c->stream));
+    }
+  }
+  STREAMCHK(c, hipStreamSynchronize(c->stream));   // the chunk is on the device: the caller's buffers are free
+  return stream_process(c, b, nrows);
+}
+
+int ppls_stream_rows_from(ppls_ctx* c, ppls_ctx* src) {
+  if (!c || !src) return c ? fail(c, PPLS_E_ARG, "NULL source context") : PPLS_E_ARG;
+  int rc;
+  if ((rc = stream_open_check(c))) return rc;
+  if (src == c) return fail(c, PPLS_E_ARG, "the source must be another context");
+  if (src->device != c->device) return fail(c, PPLS_E_ARG, "the source context is on device %d, this one on %d", src->device, c->device);
+  if (!src->have_data) return fail(c, PPLS_E_ARG, "the source context has no data");
+  if (src->st_state == 2) return fail(c, PPLS_E_STATE, PPLS_STREAMED_MSG);
+  if (src->p != c->p || src->q != c->q)
+    return fail(c, PPLS_E_ARG, "the source holds p=%d q=%d, the stream was begun with p=%d q=%d", src->p, src->q, c->p, c->q);
+  const int64_t n = src->n_local;
+  if (n == 0) return PPLS_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(src->stream));
+  if ((rc = stream_reserve(c, n, false))) return rc;
+  const int b = c->st_next;
+  CvScratch tmp;
+  for (int m = 0; m < 2; ++m) {
+    const void* sp = m == 0 ? src->X : src->Y;
+    const int cols = m == 0 ? c->p : c->q, ld = m == 0 ? c->ldx : c->ldy, sld = m == 0 ? src->ldx : src->ldy;
+    double* dst = c->st_buf[b] + (m == 0 ? 0 : c->st_cap * c->ldx);
+    if (src->dtype) {   // fp32 storage: widen the rows, then lay them out at this context's stride
+      double* wide = nullptr;
+      if ((rc = tmp.get(c, &wide, (size_t)n * sld))) return stream_fail(c, rc);
+      STREAMCHK(c, ppls_launch_convert(sp, 1, wide, 0, n * sld, c->stream));
+      sp = wide;
+    }
+    if (ld != cols) STREAMCHK(c, hipMemset2DAsync(dst, sizeof(double) * ld, 0, sizeof(double) * ld, n, c->stream));
+    STREAMCHK(c, hipMemcpy2DAsync(dst, sizeof(double) * ld, sp, sizeof(double) * sld, sizeof(double) * cols, n,
+                                  hipMemcpyDeviceToDevice, c->stream));
+  }
+  STREAMCHK(c, hipStreamSynchronize(c->stream));
+  return stream_process(c, b, n);
+}
+
+int ppls_stream_end(ppls_ctx* c) {
+  if (!c) return PPLS_E_ARG;
+  if (c->st_state != 1) return fail(c, PPLS_E_STATE, "no stream is open: call ppls_stream_begin first");
+  HIPCHK(c, hipSetDevice(c->device));
+  // Every return from here drops the stream (stream_refuse) or leaves the context streamed.  A HIP
+  // error in this rank's own work between the collectives goes into a flag the ranks all-reduce, so
+  // every rank returns and none waits alone; only a failed copy of a collective's own buffer returns
+  // at once (that rank cannot take part in a collective over device buffers at all).
+#define ENDCHK(call)                                                                                              \
+  do {                                                                                                            \
+    hipError_t e_ = (call);                                                                                       \
+    if (e_ != hipSuccess)                                                                                         \
+      return stream_refuse(c, fail(c, PPLS_E_HIP, "%s: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__)); \
+  } while (0)
+  int rc;
+  const int p = c->p, q = c->q, ldx = c->ldx, P = c->ldx + c->ldy;
+  // wait for the pending chunk work; a failure (now or earlier) is agreed on below when sharded
+  if (hipStreamSynchronize(c->st_stream) != hipSuccess) c->st_failed = true;
+  double* vec = c->st_vec;
+  double *delta = vec + 2 * P, *mean = vec + 3 * P, *red = vec + 5 * P;
+  std::vector<double> m((size_t)P, 0.0), h((size_t)P + 2, 0.0);
+  if (!c->st_failed && hipMemcpy(m.data(), mean, sizeof(double) * P, hipMemcpyDeviceToHost) != hipSuccess) c->st_failed = true;
+  double N = (double)c->st_rows;
+  if (st_collective(c)) {
+    // {failed, N_r, N_r m_r}: the global N and mean, and the agreement that nobody failed, in one all-reduce
+    const double Nr = N;
+    h[0] = c->st_failed ? 1.0 : 0.0;
+    h[1] = Nr;
+    for (int j = 0; j < P; ++j) h[(size_t)2 + j] = c->st_failed ? 0.0 : Nr * m[(size_t)j];
+    ENDCHK(hipMemcpyAsync(red, h.data(), sizeof(double) * (P + 2), hipMemcpyHostToDevice, c->stream));
+    if ((rc = allreduce(c, red, (size_t)P + 2))) return stream_refuse(c, rc);
+    ENDCHK(hipMemcpyAsync(h.data(), red, sizeof(double) * (P + 2), hipMemcpyDeviceToHost, c->stream));
+    ENDCHK(hipStreamSynchronize(c->stream));
+    if (h[0] > 0.0)
+      return stream_refuse(c, fail(c, PPLS_E_STATE, "the stream failed on %d rank(s) before ppls_stream_end", (int)h[0]));
+    N = h[1];
+    std::vector<double> d((size_t)P, 0.0);
+    for (int j = 0; j < P; ++j) {
+      const double mg = N > 0.0 ? h[(size_t)2 + j] / N : 0.0;
+      d[(size_t)j] = m[(size_t)j] - mg;   // m_r - m
+      m[(size_t)j] = mg;
+    }
+    // each rank's S is centred about its own mean: + N_r (m_r - m)(m_r - m)', the merge with no partials
+    hipError_t e = hipSuccess;
+    if (c->st_center && Nr > 0.0) {
+      e = hipMemcpyAsync(delta, d.data(), sizeof(double) * P, hipMemcpyHostToDevice, c->stream);
+      if (e == hipSuccess) e = ppls_launch_stream_merge(c->xp_S, p, ldx, q, c->ldy, nullptr, 0, delta, Nr, c->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
+    // nobody enters the all-reduce of S alone (the pattern of xprod_setup)
+    const double f = e == hipSuccess ? 0.0 : 1.0;
+    double tot = 0.0;
+    ENDCHK(hipMemcpyAsync(c->flag, &f, sizeof f, hipMemcpyHostToDevice, c->stream));
+    if ((rc = allreduce(c, c->flag, 1))) return stream_refuse(c, rc);
+    ENDCHK(hipMemcpyAsync(&tot, c->flag, sizeof tot, hipMemcpyDeviceToHost, c->stream));
+    ENDCHK(hipStreamSynchronize(c->stream));
+    if (tot > 0.0)
+      return stream_refuse(c, fail(c, PPLS_E_HIP, "the cross-rank merge of S failed on %d rank(s)", (int)tot));
+    if ((rc = allreduce(c, c->xp_S, (size_t)P * P))) return stream_refuse(c, rc);
+    ENDCHK(hipStreamSynchronize(c->stream));
+  } else if (c->st_failed) {
+    return stream_refuse(c, fail(c, PPLS_E_STATE, "the stream failed before ppls_stream_end"));
+  }
+  // From here every rank holds the same S, N and mean.  The steps on them run on this rank alone;
+  // their outcome is PPLS_OK, a refusal decided from those shared values (PPLS_E_ARG: the same on
+  // every rank) or a HIP error of this rank, which the last collective below makes everybody's.
+  std::vector<double> diag((size_t)P), cen((size_t)p + q, 0.0), scl((size_t)p + q, 1.0);
+  double s2[2] = {0.0, 0.0};
+  auto hip_failed = [&](hipError_t e, const char* what) -> int {
+    return e == hipSuccess ? PPLS_OK : fail(c, PPLS_E_HIP, "ppls_stream_end, %s: %s", what, hipGetErrorString(e));
+  };
+  auto get_diag = [&]() -> int {
+    return hip_failed(hipMemcpy2D(diag.data(), sizeof(double), c->xp_S, sizeof(double) * ((size_t)P + 1), sizeof(double),
+                                  (size_t)P, hipMemcpyDeviceToHost), "the diagonal of S");
+  };
+  auto ssq_of = [&]() -> int {   // ||X||^2, ||Y||^2 = the traces of S's diagonal blocks, in column order
+    s2[0] = s2[1] = 0.0;
+    for (int j = 0; j < p; ++j) s2[0] += diag[(size_t)j];
+    for (int j = 0; j < q; ++j) s2[1] += diag[(size_t)ldx + j];
+    for (int k = 0; k < 2; ++k)
+      if (!std::isfinite(s2[k]))
+        return fail(c, PPLS_E_ARG,
+                    "%c contains NaN or Inf (the trace of its streamed cross-products is %g; values beyond 1.3e154 "
+                    "also overflow it): the reference's svd() in orth() stops on non-finite data (EM_W_multi.R:732-733)",
+                    k ? 'Y' : 'X', s2[k]);
+    return PPLS_OK;
+  };
+  auto finish_S = [&]() -> int {
+    int r;
+    if (!(N >= 1.0)) return fail(c, PPLS_E_ARG, "no rows were streamed (over all ranks)");
+    if ((r = get_diag()) || (r = ssq_of())) return r;
+    for (int j = 0; j < p + q; ++j) cen[(size_t)j] = c->st_center ? m[(size_t)(j < p ? j : ldx + j - p)] : 0.0;
+    if (c->st_scale) {
+      if (N < 2.0)
+        return fail(c, PPLS_E_ARG, "scale = TRUE needs at least 2 rows (over all ranks: %lld): the standard deviation "
+                                   "divides by n - 1", (long long)N);
+      std::vector<double> d((size_t)P, 1.0);
+      for (int j = 0; j < p + q; ++j) {
+        const int jj = j < p ? j : ldx + j - p;
+        const double dj = std::sqrt(diag[(size_t)jj] / (N - 1.0));
+        if (!(dj > 0.0) || !std::isfinite(dj))
+          return fail(c, PPLS_E_ARG, "%c column %d has standard deviation %g (over all ranks): scale = TRUE would fill it "
+                                     "with NaN or Inf, as R's scale() does; the stream is dropped",
+                      j < p ? 'X' : 'Y', (j < p ? j : j - p) + 1, dj);
+        d[(size_t)jj] = scl[(size_t)j] = dj;
+      }
+      hipError_t e = hipMemcpyAsync(vec, d.data(), sizeof(double) * P, hipMemcpyHostToDevice, c->stream);
+      if (e == hipSuccess) e = ppls_launch_stream_standardise(c->xp_S, p, ldx, q, c->ldy, vec, c->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+      if ((r = hip_failed(e, "standardising S")) || (r = get_diag()) || (r = ssq_of())) return r;
+    }
+    return hip_failed(hipMemcpy(c->ssq, s2, sizeof s2, hipMemcpyHostToDevice), "||X||^2, ||Y||^2");
+  };
+  int local = finish_S();
+  const std::string local_err = c->err;
+  // the staging buffers and partials go back before the free memory is read: the smallest free HBM
+  // over all ranks, as compute_ssq records it, beside the agreement on the steps above
+  const int64_t rows = c->st_rows, chunks = c->st_chunks;
+  stream_release(c);   // (st_state = 0: stream_refuse below still clears S and have_data)
+  size_t mfree = 0, mtot = 0;
+  if (!local) local = hip_failed(hipMemGetInfo(&mfree, &mtot), "hipMemGetInfo");
+  c->mem_free_min = (double)mfree;
+  if (st_collective(c)) {
+    CvScratch tmp;
+    double* slots_d = nullptr;
+    if ((rc = tmp.get(c, &slots_d, (size_t)c->nranks + 1))) return stream_refuse(c, rc);
+    std::vector<double> slots((size_t)c->nranks + 1, 0.0);   // {HIP failures, free HBM of rank 0, 1, ...}
+    slots[0] = local == PPLS_OK || local == PPLS_E_ARG ? 0.0 : 1.0;
+    slots[(size_t)c->rank + 1] = (double)mfree;
+    ENDCHK(hipMemcpy(slots_d, slots.data(), sizeof(double) * slots.size(), hipMemcpyHostToDevice));
+    if ((rc = allreduce(c, slots_d, slots.size()))) return stream_refuse(c, rc);
+    ENDCHK(hipStreamSynchronize(c->stream));
+    ENDCHK(hipMemcpy(slots.data(), slots_d, sizeof(double) * slots.size(), hipMemcpyDeviceToHost));
+    if (slots[0] > 0.0 && (local == PPLS_OK || local == PPLS_E_ARG))
+      local = fail(c, PPLS_E_HIP, "ppls_stream_end failed on %d other rank(s)", (int)slots[0]);
+    else if (local)
+      c->err = local_err;
+    for (size_t k = 1; k < slots.size(); ++k) c->mem_free_min = std::min(c->mem_free_min, slots[k]);
+  }
+  if (local) return stream_refuse(c, local);
+#undef ENDCHK
+  c->ssq_host[0] = s2[0];
+  c->ssq_host[1] = s2[1];
+  c->sc_center = cen;
+  c->sc_scale = scl;
+  // streamed: no rows resident, S ready and kept until the data change or ppls_xprod_release
+  c->st_rows = rows;
+  c->st_chunks = chunks;
+  c->st_state = 2;
+  c->n_local = 0;
+  c->n_total = (int64_t)N;
+  c->xp_ready = true;
+  c->xp_explicit = true;
+  c->xp_active = false;
+  c->em_active = false;
+  c->have_data = true;
+  return PPLS_OK;
+}
+
+int ppls_stream_info(ppls_ctx* c, int* state, int64_t* rows_local, int64_t* n_total, int64_t* chunks) {
+  if (!c) return PPLS_E_ARG;
+  if (state) *state = c->st_state;
+  if (rows_local) *rows_local = c->st_state ? c->st_rows : 0;
+  if (n_total) *n_total = c->st_state == 2 ? c->n_total : c->st_state == 1 ? c->st_rows : 0;
+  if (chunks) *chunks = c->st_state ? c->st_chunks : 0;
   return PPLS_OK;
 }
 
