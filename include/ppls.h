@@ -423,6 +423,66 @@ int ppls_stream_end(ppls_ctx* ctx);
  * ranks once streamed (while open: this rank's so far).  All nullable. */
 int ppls_stream_info(ppls_ctx* ctx, int* state, int64_t* rows_local, int64_t* n_total, int64_t* chunks);
 
+/* ---- cross-validation from row chunks: one cross-product matrix per fold ------------------------
+ * A fold's training cross-products are the sum of the other folds' cross-products, and the held-out
+ * error sum_i ||y_i - x_i W diag(B) C'||^2 is a quadratic form in the held-out fold's own: K-fold
+ * cross-validation needs no rows and no second pass, only (K + 1) 8 P^2 bytes of device memory.  The
+ * data are centred and scaled once, as a whole (R: scale() on all rows, then folds taken without
+ * re-centring, crossval_PPLS.R:40-52); ppls_scale_data followed by ppls_cv_ppls on resident rows
+ * computes the same.  A stream opened with ppls_stream_begin has no folds and behaves as before; on it
+ * the labelled calls and the calls below return PPLS_E_STATE, as do the unlabelled ppls_stream_rows /
+ * _rows_from on a fold stream.  A context streamed with folds is "streamed" (everything that needs
+ * rows keeps its refusal) and additionally serves ppls_stream_fold_info, ppls_stream_select,
+ * ppls_heldout_sse_fold and ppls_cv_ppls_stream; what ends the streamed state frees the fold matrices. */
+
+/* ppls_stream_begin with nfolds >= 2 Chan states (N_k, mean_k, S_k) instead of one; the nfolds fold
+ * matrices are allocated up front, contiguously (PPLS_E_NOMEM: the stream is not opened). */
+int ppls_stream_begin_folds(ppls_ctx* ctx, int p, int q, int center, int scale, int nfolds);
+/* ppls_stream_rows / ppls_stream_rows_from with the fold (0 .. nfolds-1) of every row of the chunk
+ * (of src's resident rows).  A label out of range: PPLS_E_ARG before any device work, the stream stays
+ * usable.  The host builds the chunk's stable fold order (a counting sort), the staged rows are
+ * gathered into it on the device, and every fold present in the chunk runs the plain stream's four
+ * steps on its segment against its own state, in fold order; a fold absent from the chunk launches
+ * nothing.  The same chunks and labels give the same bits in any context. */
+int ppls_stream_rows_folds(ppls_ctx* ctx, const double* X, const double* Y, int64_t nrows, int layout,
+                           const int32_t* fold /* nrows */);
+int ppls_stream_rows_from_folds(ppls_ctx* ctx, ppls_ctx* src, const int32_t* fold /* src's n_local */);
+/* ppls_stream_end on a fold stream (collective when sharded, like the plain one: one all-reduce of
+ * {failed, N_rk, N_rk mean_rk}, each rank's S_k recentred to the global fold mean, the agreement, one
+ * all-reduce of all fold matrices) then, on every rank alone and with identical bits: N = sum N_k and
+ * m = sum N_k mean_k / N in fold order; S_k <- S_k + N_k (mean_k - m)(mean_k - m)'; scale = 1:
+ * d_j = sqrt(sum_k S_k,jj / (N - 1)) in fold order and S_k,ij <- S_k,ij / (d_i d_j), in the same pass.
+ * The plain stream's refusals hold; a fold without a row over all ranks is PPLS_E_ARG with a message
+ * naming the fold, the stream dropped.  Leaves the context selected on all folds (-1). */
+
+/* nfolds: 0 for a context that is not (being) streamed with folds; fold_total (nfolds values): rows
+ * per fold over all ranks once streamed (while open: this rank's so far); selected: the fold the
+ * working cross-products leave out, -1 none.  All nullable. */
+int ppls_stream_fold_info(ppls_ctx* ctx, int* nfolds, int64_t* fold_total, int* selected);
+/* The working cross-products S <- the sum of the fold matrices l != fold, added in fold order (fold
+ * = -1: all of them) -- by addition, never S_all - S_fold, so an entry carries the rounding of the
+ * selected rows only and no fold size is refused -- with n_total and ||X||^2, ||Y||^2 (the traces) to
+ * match: every fit entry point then works on the selected rows.  PPLS_E_STATE while an ppls_em_begin
+ * session is active. */
+int ppls_stream_select(ppls_ctx* ctx, int fold);
+/* Held-out error of a fit from fold `fold`'s cross-products S_k alone: with A = W' S_k,xx W,
+ * D_m = w_m' S_k,xy c_m and G = C'C, for every prefix j = 1..k
+ *   sse[j-1] = tr(S_k,yy) - 2 sum_{m<=j} b_m D_m + sum_{m,l<=j} b_m b_l A_ml G_ml.
+ * mag[j-1] (nullable) is the same sum with every elementary product replaced by its absolute value:
+ * the rounding error of sse_j is bounded by a small multiple of gamma_n mag_j, so mag_j / sse_j tells
+ * how many digits survive (the expansion cancels when the fit is good; with no rows there is no
+ * direct residual to form instead).  One read of the X rows of S_k; fixed-order sums, identical on
+ * every rank (no collective).  W: p x k, C: q x k column-major, k <= 16 as for ppls_heldout_sse. */
+int ppls_heldout_sse_fold(ppls_ctx* ctx, const double* W, const double* C, const double* B, int k, int fold,
+                          double* sse /* k */, double* mag /* k, nullable */);
+/* cv_PPLS's loop on the stream's folds: per fold ppls_stream_select, ppls_ppls_ex with a components
+ * from init[f*a .. f*a+a), ppls_heldout_sse_fold.  rmsep[f*a + j] = sqrt(sse_j / (N_f q)) and ncomp
+ * as for ppls_cv_ppls; cond (nullable, nfolds x a) = mag_j / sse_j.  Ends selected on -1, also on an
+ * error return. */
+int ppls_cv_ppls_stream(ppls_ctx* ctx, int a, int max_steps, double atol, int crit_abs,
+                        const ppls_theta* init /* nfolds x a */, double* rmsep /* nfolds x a */,
+                        int* ncomp /* nfolds */, double* cond /* nfolds x a, nullable */);
+
 /* ---- host-side algebra (no GPU; the same code the device finalize runs) ------------------------ */
 /* From the all-reduced sufficient statistics of one sweep with theta (stats = [X'mu_T p x r |
  * Y'mu_U q x r | Gram 2r x 2r], all column-major) compute Expect_M's moments, logl_W(theta) and

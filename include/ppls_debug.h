@@ -109,6 +109,12 @@ int ppls_xprod_get(ppls_ctx* ctx, double* S, int* P, int* ldx);
  * bytes3 the bytes the pass read (the apply pass: read + written) on this rank. */
 int ppls_scale_timing(ppls_ctx* ctx, double* ms3, double* bytes3);
 
+/* One fold of a context streamed with folds (ppls_stream_begin_folds): S (nullable) the P x P doubles
+ * of the fold's cross-products as finished (about the global mean, standardised; row-major, padding
+ * included), mean (nullable, P doubles, joint padded layout) the fold's own mean of the loaded values,
+ * *n the fold's rows over all ranks. */
+int ppls_stream_fold_get(ppls_ctx* ctx, int fold, double* S, double* mean, int64_t* n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,15 @@ SIGNATURES = {
     "ppls_stream_rows_from": (ct.c_int, [ct.c_void_p, ct.c_void_p]),
     "ppls_stream_end": (ct.c_int, [ct.c_void_p]),
     "ppls_stream_info": (ct.c_int, [ct.c_void_p, ct.POINTER(ct.c_int), _i64p, _i64p, _i64p]),
+    "ppls_stream_begin_folds": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int]),
+    "ppls_stream_rows_folds": (ct.c_int, [ct.c_void_p, _dp, _dp, ct.c_int64, ct.c_int, ct.POINTER(ct.c_int32)]),
+    "ppls_stream_rows_from_folds": (ct.c_int, [ct.c_void_p, ct.c_void_p, ct.POINTER(ct.c_int32)]),
+    "ppls_stream_fold_info": (ct.c_int, [ct.c_void_p, ct.POINTER(ct.c_int), _i64p, ct.POINTER(ct.c_int)]),
+    "ppls_stream_select": (ct.c_int, [ct.c_void_p, ct.c_int]),
+    "ppls_heldout_sse_fold": (ct.c_int, [ct.c_void_p, _dp, _dp, _dp, ct.c_int, ct.c_int, _dp, _dp]),
+    "ppls_cv_ppls_stream": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.c_double, ct.c_int, ct.POINTER(PplsTheta),
+                                       _dp, ct.POINTER(ct.c_int), _dp]),
+    "ppls_stream_fold_get": (ct.c_int, [ct.c_void_p, ct.c_int, _dp, _dp, _i64p]),
 }
 
 

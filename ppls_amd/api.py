@@ -56,6 +56,7 @@ class Context:
         self.p = self.q = None
         self.n_local = self.n_total = None
         self.row0 = 0
+        self._stream_folds = None     # K while the context is (being) streamed with folds
 
     # -- plumbing
     def _chk(self, rc):
@@ -141,6 +142,7 @@ class Context:
         nt = n if n_total is None else int(n_total)
         self._chk(self._L.ppls_set_data(self.h, dptr(X), dptr(Y), n, p, q, layout, nt))
         self.p, self.q, self.n_local, self.n_total = p, q, n, nt
+        self._stream_folds = None
 
     def generate_synthetic(self, n_total, p, q, truth: Theta, seed: int, row0=0, n_local=None):
         nl = n_total - row0 if n_local is None else int(n_local)
@@ -148,6 +150,7 @@ class Context:
         self._chk(self._L.ppls_generate_synthetic(self.h, int(n_total), int(row0), nl, int(p), int(q),
                                                   truth.r, ct.byref(t), ct.c_uint64(int(seed))))
         self.p, self.q, self.n_local, self.n_total, self.row0 = p, q, nl, int(n_total), int(row0)
+        self._stream_folds = None
 
     def get_data(self, row_begin=0, nrows=None):
         nrows = self.n_local - row_begin if nrows is None else nrows
@@ -203,30 +206,116 @@ class Context:
         return dict(ms=ms, bytes=by)
 
     # -- streamed data: S from row chunks, no rows resident
-    def stream_begin(self, p, q, center=False, scale=False):
+    def stream_begin(self, p, q, center=False, scale=False, nr_folds=None):
         """Open a stream of ``p + q`` columns (ppls_stream_begin): drops resident data and S.
-        ``center`` / ``scale`` as in R's ``scale()``, applied to the streamed rows as a whole."""
-        self._chk(self._L.ppls_stream_begin(self.h, int(p), int(q), int(bool(center)), int(bool(scale))))
+        ``center`` / ``scale`` as in R's ``scale()``, applied to the streamed rows as a whole.
+        ``nr_folds=K``: one cross-product matrix per fold is kept (ppls_stream_begin_folds), every
+        chunk then comes with a fold label per row, and the streamed context can cross-validate."""
+        if nr_folds is None:
+            self._chk(self._L.ppls_stream_begin(self.h, int(p), int(q), int(bool(center)), int(bool(scale))))
+        else:
+            if int(nr_folds) < 2:
+                raise ValueError("Cross-validation with 1 fold does not make sense, use 2 folds or more")
+            self._chk(self._L.ppls_stream_begin_folds(self.h, int(p), int(q), int(bool(center)), int(bool(scale)),
+                                                      int(nr_folds)))
         self.p, self.q, self.n_local, self.n_total, self.row0 = int(p), int(q), 0, 0, 0
+        self._stream_folds = None if nr_folds is None else int(nr_folds)
 
-    def stream_rows(self, X, Y):
+    def stream_rows(self, X, Y, fold=None):
         """One chunk of rows (ppls_stream_rows): float64 matrices, C- or F-contiguous (both in the
-        same order are passed without a copy).  Returns once the chunk is on the device."""
+        same order are passed without a copy).  Returns once the chunk is on the device.  ``fold``:
+        the fold (0 .. K-1) of every row, for a stream opened with ``nr_folds=K``."""
         X, Y, layout = _chunk_arrays(X, Y, self.p, self.q)
-        self._chk(self._L.ppls_stream_rows(self.h, dptr(X), dptr(Y), X.shape[0], layout))
+        if fold is None:
+            self._chk(self._L.ppls_stream_rows(self.h, dptr(X), dptr(Y), X.shape[0], layout))
+            return
+        fold = _fold_array(fold, X.shape[0], self._stream_folds)
+        self._chk(self._L.ppls_stream_rows_folds(self.h, dptr(X), dptr(Y), X.shape[0], layout,
+                                                 fold.ctypes.data_as(ct.POINTER(ct.c_int32))))
 
-    def stream_rows_from(self, src: "Context"):
-        """All resident rows of ``src`` as one chunk, device to device; ``src`` is left untouched."""
-        self._chk(self._L.ppls_stream_rows_from(self.h, src.h))
+    def stream_rows_from(self, src: "Context", fold=None):
+        """All resident rows of ``src`` as one chunk, device to device; ``src`` is left untouched.
+        ``fold``: the fold of every resident row of ``src``, for a stream opened with folds."""
+        if fold is None:
+            self._chk(self._L.ppls_stream_rows_from(self.h, src.h))
+            return
+        fold = _fold_array(fold, src.n_local, self._stream_folds)
+        self._chk(self._L.ppls_stream_rows_from_folds(self.h, src.h, fold.ctypes.data_as(ct.POINTER(ct.c_int32))))
 
     def stream_end(self):
         """Close the stream (ppls_stream_end; collective when sharded).  Returns ``dict(n, centerX,
-        scaleX, centerY, scaleY)``: the rows over all ranks and the transform S carries."""
-        self._chk(self._L.ppls_stream_end(self.h))
+        scaleX, centerY, scaleY)``: the rows over all ranks and the transform S carries; a stream
+        with folds adds ``fold_total``, the rows per fold over all ranks."""
+        try:
+            self._chk(self._L.ppls_stream_end(self.h))
+        except PplsError:
+            self._stream_folds = None      # every error return drops the stream
+            raise
         self.n_local, self.n_total = 0, self.stream_info()["n_total"]
         out = dict(n=self.n_total)
         out.update(self.scaling())
+        info = self.stream_fold_info()
+        if info["nr_folds"]:
+            out["fold_total"] = info["fold_total"]
         return out
+
+    def stream_fold_info(self):
+        """``dict(nr_folds, fold_total, selected)`` (ppls_stream_fold_info): 0 folds for a context
+        not streamed with folds; ``selected`` is the fold the working cross-products leave out."""
+        K, sel = ct.c_int(), ct.c_int()
+        self._chk(self._L.ppls_stream_fold_info(self.h, ct.byref(K), None, None))
+        tot = np.zeros(K.value, dtype=np.int64)
+        self._chk(self._L.ppls_stream_fold_info(self.h, ct.byref(K), tot.ctypes.data_as(_lib._i64p), ct.byref(sel)))
+        return dict(nr_folds=K.value, fold_total=tot, selected=sel.value)
+
+    def stream_select(self, fold=-1):
+        """The working cross-products become the sum of all folds but ``fold`` (-1: all), with
+        ``n_total`` and the sums of squares to match (ppls_stream_select): the fits then see the
+        selected rows."""
+        self._chk(self._L.ppls_stream_select(self.h, int(fold)))
+        self.n_total = self.stream_info()["n_total"]
+
+    def heldout_sse_fold(self, W, C, B, fold):
+        """(sse, mag) of fold ``fold`` from its cross-products, for every prefix of the components
+        (ppls_heldout_sse_fold): ``mag / sse`` tells how many digits of ``sse`` survive."""
+        W, C, B = self._fit_arrays(W, C, B)
+        if W.shape[0] != self.p or C.shape[0] != self.q:
+            raise ValueError(f"the fit is {W.shape[0]} x {C.shape[0]}, the context's data {self.p} x {self.q}")
+        sse, mag = np.zeros(W.shape[1]), np.zeros(W.shape[1])
+        self._chk(self._L.ppls_heldout_sse_fold(self.h, dptr(W), dptr(C), dptr(B), W.shape[1], int(fold), dptr(sse),
+                                                dptr(mag)))
+        return sse, mag
+
+    def stream_fold_get(self, fold, padded=False):
+        """(S, mean, n) of one fold of a context streamed with folds (ppls_stream_fold_get), S and the
+        mean over the p + q real columns unless ``padded``."""
+        P, ldx = ct.c_int(), ct.c_int()
+        self._chk(self._L.ppls_xprod_get(self.h, None, ct.byref(P), ct.byref(ldx)))
+        S, mean, n = np.zeros((P.value, P.value)), np.zeros(P.value), ct.c_int64()
+        self._chk(self._L.ppls_stream_fold_get(self.h, int(fold), dptr(S), dptr(mean), ct.byref(n)))
+        if not padded:
+            idx = np.r_[np.arange(self.p), ldx.value + np.arange(self.q)]
+            S, mean = S[np.ix_(idx, idx)], mean[idx]
+        return S, mean, n.value
+
+    def cv_ppls_stream(self, a: int, max_steps: int, atol: float, inits, crit_abs=False):
+        """cv_PPLS's loop on the folds of a context streamed with folds (ppls_cv_ppls_stream).
+        ``inits`` as for ``cv_ppls``.  Returns (rmsep K x a, ncomp K, cond K x a = mag / sse)."""
+        p, q = self.p, self.q
+        K = self.stream_fold_info()["nr_folds"]
+        if len(inits) != K or any(len(f) != a for f in inits):
+            raise ValueError(f"starting values: one list of {a} per fold ({K} folds)")
+        ths = [Theta(np.reshape(t["W"], (p, 1)), np.reshape(t["C"], (q, 1)), float(np.ravel(t["B"])[0]),
+                     t["sigE"], t["sigF"], t["sigH"], float(np.ravel(t["sigT"])[0])) for f in inits for t in f]
+        arr = (_lib.PplsTheta * (K * a))(*[t.struct() for t in ths])
+        rmsep, cond = np.full((K, a), np.nan), np.full((K, a), np.nan)
+        ncomp = np.zeros(K, dtype=np.int32)
+        try:
+            self._chk(self._L.ppls_cv_ppls_stream(self.h, int(a), int(max_steps), float(atol), int(bool(crit_abs)), arr,
+                                                  dptr(rmsep), ncomp.ctypes.data_as(ct.POINTER(ct.c_int)), dptr(cond)))
+        finally:
+            self.n_total = self.stream_info()["n_total"]
+        return rmsep, ncomp, cond
 
     def stream_info(self):
         st = ct.c_int()
@@ -488,6 +577,7 @@ class Context:
         """Free the cross-products S now (ppls_xprod_release; 8 (p+q)^2 bytes of HBM); the next run
         that reads S forms it again."""
         self._chk(self._L.ppls_xprod_release(self.h))
+        self._stream_folds = None
 
     def xprod_matrix(self, padded=False):
         """The cross-products S the context holds (formed, prepared, downdated or streamed):
@@ -558,6 +648,7 @@ class Context:
         nt = rows.shape[0] if n_total is None else int(n_total)
         self._chk(self._L.ppls_set_data_from(self.h, src.h, rp, rows.shape[0], nt))
         self.p, self.q, self.n_local, self.n_total, self.row0 = src.p, src.q, rows.shape[0], nt, 0
+        self._stream_folds = None
 
     def xprod_downdate(self, src: "Context", out_rows):
         """This context's cross-products S := ``src``'s S minus the Gram of ``src``'s rows
@@ -1350,28 +1441,50 @@ def _chunk_arrays(X, Y, p=None, q=None):
     return np.ascontiguousarray(X), np.ascontiguousarray(Y), _lib.PPLS_LAYOUT_ROWMAJOR
 
 
-def stream_data(chunks, center=True, scale=True, ctx=None):
+def _fold_array(fold, n, K=None):
+    """The fold labels of a chunk of ``n`` rows as int32, checked on the host: integers, one per row,
+    in 0 .. K-1."""
+    f = np.asarray(fold)
+    if f.ndim != 1 or f.shape[0] != n:
+        raise ValueError(f"fold labels: {f.shape} for a chunk of {n} rows (one label per row)")
+    if f.dtype.kind not in "iu":
+        raise TypeError(f"fold labels must be integers, not {f.dtype}")
+    if n and (int(f.min()) < 0 or (K is not None and int(f.max()) >= K) or int(f.max()) > np.iinfo(np.int32).max):
+        raise ValueError(f"fold labels must lie in 0 .. {'K-1' if K is None else K - 1}: found "
+                         f"{int(f.min())} .. {int(f.max())}")
+    return np.ascontiguousarray(f, dtype=np.int32)
+
+
+def stream_data(chunks, center=True, scale=True, ctx=None, nr_folds=None):
     """Load data too large to hold at once: ``chunks`` is an iterable of ``(X, Y)`` row blocks (numpy
     matrices, e.g. slices of a memory-mapped file).  Their cross-products -- of the rows centred and
     scaled as R's ``scale()`` would the whole matrix -- are accumulated on the device; no rows stay
     resident.  Returns ``dict(n, centerX, scaleX, centerY, scaleY)``.  Afterwards
-    ``PPLS(None, None, a, ctx=ctx)`` and ``PPLS_simult(None, None, a, ctx=ctx)`` fit from them."""
+    ``PPLS(None, None, a, ctx=ctx)`` and ``PPLS_simult(None, None, a, ctx=ctx)`` fit from them.
+    ``nr_folds=K``: every chunk is an ``(X, Y, fold)`` triple with the fold (0 .. K-1) of each row
+    (``fold_labels`` gives cv_PPLS's); one cross-product matrix per fold is kept, the result gains
+    ``fold_total``, and ``cv_PPLS(None, None, a, K, ctx=ctx)`` / ``crossval_PPLS`` run on them."""
+    want = 2 if nr_folds is None else 3
+    what = "(X, Y) pair" if nr_folds is None else "(X, Y, fold) triple"
+    if nr_folds is not None and int(nr_folds) < 2:
+        raise ValueError("Cross-validation with 1 fold does not make sense, use 2 folds or more")
     if isinstance(chunks, np.ndarray) or not hasattr(chunks, "__iter__"):
-        raise TypeError("chunks must be an iterable of (X, Y) pairs")
+        raise TypeError(f"chunks must be an iterable of {what}s")
     it = iter(chunks)
     first = next(it, None)
     if first is None:
         raise ValueError("chunks is empty: no rows to stream")
     p = q = None
     for pair in itertools.chain([first], it):
-        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
-            raise TypeError("every chunk must be an (X, Y) pair")
+        if not isinstance(pair, (tuple, list)) or len(pair) != want:
+            raise TypeError(f"every chunk must be an {what}")
         X, Y, _ = _chunk_arrays(pair[0], pair[1], p, q)   # (checked before a device is touched)
+        fold = None if nr_folds is None else _fold_array(pair[2], X.shape[0], int(nr_folds))
         if p is None:
             p, q = X.shape[1], Y.shape[1]
             ctx = ctx or default_context()
-            ctx.stream_begin(p, q, center, scale)
-        ctx.stream_rows(X, Y)
+            ctx.stream_begin(p, q, center, scale, nr_folds)
+        ctx.stream_rows(X, Y, fold)
     return ctx.stream_end()
 
 
@@ -1469,11 +1582,12 @@ def _cv_args(ppls_args):
             _crit_abs(ppls_args.get("critfunc")))
 
 
-def _cv_run(ctx, a, nr_folds, folds, rng, ppls_args):
-    """The folds of cv_PPLS (:42-44) and one ppls_cv_ppls call with ``a`` components:
-    (rmsep nr_folds x a, ncomp)."""
-    kind, custom, steps, atol, crit_abs = _cv_args(ppls_args)
-    N, K = int(ctx.n_total), int(nr_folds)
+def fold_labels(N, K, folds=None, rng=None):
+    """The fold (0 .. K-1, int32) of each of N rows as cv_PPLS assigns it (crossval_PPLS.R:42-44):
+    ``folds`` is the permutation R's ``sample(N)`` would give, 0-based (default
+    ``rng.permutation(N)``), and fold i holds rows ``folds[cv_blocks(N, K) == i + 1]``.  For callers
+    who stream rows with ``nr_folds=K`` and know N beforehand."""
+    N, K = int(N), int(K)
     if K < 2:
         raise ValueError("Cross-validation with 1 fold does not make sense, use 2 folds or more")
     if N < K:
@@ -1487,17 +1601,51 @@ def _cv_run(ctx, a, nr_folds, folds, rng, ppls_args):
         raise ValueError("folds must be a permutation of 0..N-1")
     fold_of = np.empty(N, dtype=np.int32)
     fold_of[folds] = blocks - 1                    # fold i holds rows folds[blocks == i]
-    fold_total = np.bincount(fold_of, minlength=K).astype(np.int64)
+    return fold_of
+
+
+def _cv_inits(ctx, a, K, kind, custom, rng):
     if kind == "custom":
         one = list(custom) if isinstance(custom, (list, tuple)) else [custom] * a
-        inits = [one] * K
-    elif kind == "equal":
-        inits = [[initial_guess(ctx.p, ctx.q, "equal") for _ in range(a)]] * K
-    else:                                          # fold by fold, component by component
-        rng = rng if rng is not None else np.random.default_rng()
-        inits = [[initial_guess(ctx.p, ctx.q, "random", rng) for _ in range(a)] for _ in range(K)]
+        return [one] * K
+    if kind == "equal":
+        return [[initial_guess(ctx.p, ctx.q, "equal") for _ in range(a)]] * K
+    rng = rng if rng is not None else np.random.default_rng()   # fold by fold, component by component
+    return [[initial_guess(ctx.p, ctx.q, "random", rng) for _ in range(a)] for _ in range(K)]
+
+
+def _cv_run(ctx, a, nr_folds, folds, rng, ppls_args):
+    """The folds of cv_PPLS (:42-44) and one ppls_cv_ppls call with ``a`` components:
+    (rmsep nr_folds x a, ncomp)."""
+    kind, custom, steps, atol, crit_abs = _cv_args(ppls_args)
+    N, K = int(ctx.n_total), int(nr_folds)
+    fold_of = fold_labels(N, K, folds, rng)
+    fold_total = np.bincount(fold_of, minlength=K).astype(np.int64)
+    inits = _cv_inits(ctx, a, K, kind, custom, rng)
     lo = int(ctx.row0)
     return ctx.cv_ppls(a, fold_of[lo: lo + ctx.n_local], fold_total, steps, atol, inits, crit_abs)
+
+
+_COND_LIMIT = 1e-6     # lost digits, not a tolerance: warn where cond 64 u exceeds it
+
+
+def _cv_run_stream(ctx, a, nr_folds, folds, rng, ppls_args):
+    """cv_PPLS's loop on the folds a context was streamed with (ppls_cv_ppls_stream):
+    (rmsep K x a, ncomp).  The arguments are checked before any device call."""
+    kind, custom, steps, atol, crit_abs = _cv_args(ppls_args)
+    K = int(ctx._stream_folds)
+    if int(nr_folds) != K:
+        raise ValueError(f"nr_folds={int(nr_folds)}, but the rows were streamed with {K} folds")
+    if folds is not None:
+        raise ValueError("folds= cannot be given: the folds are those the rows were streamed with")
+    inits = _cv_inits(ctx, a, K, kind, custom, rng)
+    rmsep, ncomp, cond = ctx.cv_ppls_stream(a, steps, atol, inits, crit_abs)
+    with np.errstate(invalid="ignore"):
+        bad = np.argwhere(np.abs(cond) * 64 * 2.0 ** -53 > _COND_LIMIT)
+    for f, j in bad:
+        warnings.warn(f"fold {int(f)}, {int(j) + 1} component(s): the held-out error from cross-products keeps "
+                      f"few digits (mag / sse = {cond[f, j]:.3g})")
+    return rmsep, ncomp
 
 
 def _cv_err(rmsep, ncomp, nr_comp):
@@ -1517,12 +1665,19 @@ def cv_PPLS(X, Y, nr_comp, nr_folds, folds=None, rng=None, ctx=None, per_fold=Fa
     give, 0-based (default ``rng.permutation(N)``); fold i holds ``folds[cv_blocks(N, K) == i]``.
     ``ppls_args``: PPLS's EMsteps, atol, initialGuess ('equal', 'random', 'custom'), customGuess,
     critfunc; 'random' starts are drawn from ``rng`` fold by fold, component by component.  The folds
-    run on the device (ppls_cv_ppls).  mse(x, y) = mean((x - y)^2) as in OmicsPLS."""
+    run on the device (ppls_cv_ppls).  mse(x, y) = mean((x - y)^2) as in OmicsPLS.
+    ``cv_PPLS(None, None, nr_comp, K, ctx=ctx)`` on a context streamed with ``nr_folds=K`` runs on
+    the stream's folds from their cross-products (ppls_cv_ppls_stream): ``nr_folds`` must be that K
+    and ``folds`` None (ValueError otherwise); a warning names every fold and prefix whose held-out
+    error lost digits to cancellation (mag / sse 64 u > 1e-6)."""
     _cv_args(ppls_args)
     if int(nr_folds) < 2:
         raise ValueError("Cross-validation with 1 fold does not make sense, use 2 folds or more")
-    ctx = _ctx_with(X, Y, ctx)
-    rmsep, ncomp = _cv_run(ctx, int(nr_comp), nr_folds, folds, rng, ppls_args)
+    if X is None and ctx is not None and ctx._stream_folds:
+        rmsep, ncomp = _cv_run_stream(ctx, int(nr_comp), nr_folds, folds, rng, ppls_args)
+    else:
+        ctx = _ctx_with(X, Y, ctx)
+        rmsep, ncomp = _cv_run(ctx, int(nr_comp), nr_folds, folds, rng, ppls_args)
     err = _cv_err(rmsep, ncomp, int(nr_comp))
     return (float(np.mean(err)), err) if per_fold else float(np.mean(err))
 
@@ -1534,7 +1689,10 @@ def crossval_PPLS(X, Y, a, nr_folds, nr_cores=1, shared_folds=False, ctx=None, *
     in R and otherwise ignored: the folds run on the one device.  Default: a fresh fold permutation
     per entry of ``a`` as in R, one device loop per entry.  ``shared_folds=True``: one permutation and
     one loop with max(a) components whose prefixes give every entry (PPLS is sequential): K fits
-    instead of K * len(a).  ``rng`` / ``folds`` are passed on as for cv_PPLS."""
+    instead of K * len(a).  ``rng`` / ``folds`` are passed on as for cv_PPLS.  On a context streamed
+    with folds the folds are the stream's for every entry of ``a`` (R's fresh permutation per entry
+    is impossible once the rows are gone): ``shared_folds=True`` makes K fits of max(a) components,
+    ``False`` K * len(a) fits on the same folds."""
     tic = time.perf_counter()
     a = [int(v) for v in np.atleast_1d(a)]
     rng = ppls_args.pop("rng", None)
@@ -1560,9 +1718,16 @@ def crossval_PPLS(X, Y, a, nr_folds, nr_cores=1, shared_folds=False, ctx=None, *
         raise ValueError("nr_cores == abs(round(nr_cores)) is not TRUE")
     if nr_folds == 1:
         raise ValueError("Cross-validation with 1 fold does not make sense, use 2 folds or more")
+    streamed = X is None and ctx is not None and bool(ctx._stream_folds)
+    if streamed:     # the arguments are checked before any device call
+        if int(nr_folds) != int(ctx._stream_folds):
+            raise ValueError(f"nr_folds={int(nr_folds)}, but the rows were streamed with {ctx._stream_folds} folds")
+        if folds is not None:
+            raise ValueError("folds= cannot be given: the folds are those the rows were streamed with")
     ctx = _ctx_with(X, Y, ctx)
     if shared_folds:
-        rmsep, ncomp = _cv_run(ctx, max(a), nr_folds, folds, rng, ppls_args)
+        run = _cv_run_stream if streamed else _cv_run
+        rmsep, ncomp = run(ctx, max(a), nr_folds, folds, rng, ppls_args)
         errors = [float(np.mean(_cv_err(rmsep, ncomp, e))) for e in a]
     else:
         rng = rng if rng is not None else np.random.default_rng()

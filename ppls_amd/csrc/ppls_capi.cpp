@@ -26,6 +26,7 @@
 #include "ppls_math.h"
 #include "ppls_cv.h"
 #include "ppls_scale.h"
+#include "ppls_cvstream.h"
 #include "ppls_stream.h"
 #include "ppls_xprod.h"
 
@@ -203,6 +204,21 @@ struct ppls_ctx {
   int64_t st_part_len = 0;
   double* st_colpart = nullptr;   // the column sums' row-block partials
   int64_t st_colpart_len = 0;
+  // a stream opened with folds (ppls_stream_begin_folds): one Chan state (N_k, mean_k,
+  // S_k) per fold; once streamed, the fold matrices stay and xp_S is the working selection of them
+  int st_nfolds = 0;              // 0: a plain stream
+  double* st_fS = nullptr;        // the st_nfolds fold matrices, P x P each, contiguous
+  double* st_fmean = nullptr;     // st_nfolds x P running fold means (while the stream is open)
+  double* st_gbuf = nullptr;      // the staged chunk in fold order (the layout of st_buf)
+  int64_t st_gbuf_len = 0;
+  int64_t* st_idx[2] = {nullptr, nullptr};   // per staging buffer: the chunk's stable fold order
+  int64_t st_idx_len[2] = {0, 0};
+  std::vector<int64_t> st_fN;     // rows per fold: this rank's while open, over all ranks once streamed
+  std::vector<double> st_fmean_h; // once streamed: the folds' means (st_nfolds x P, joint layout)
+  std::vector<int64_t> st_seg;    // the current chunk's st_nfolds + 1 segment offsets
+  std::vector<int*> st_fq;        // per staging buffer and fold: the segment Gram's work queue (device)
+  std::vector<int64_t> st_fq_len;
+  int st_sel = -1;                // the fold xp_S leaves out (-1: none)
 };
 
 namespace {
@@ -1126,9 +1142,27 @@ void stream_release(ppls_ctx* c) {
   dfree(c->st_vec);
   dfree(c->st_part);
   dfree(c->st_colpart);
-  c->st_cap = c->st_cm_len = c->st_part_len = c->st_colpart_len = 0;
+  dfree(c->st_gbuf);
+  dfree(c->st_fmean);
+  for (int b = 0; b < 2; ++b) {
+    dfree(c->st_idx[b]);
+    c->st_idx_len[b] = 0;
+  }
+  for (int*& q : c->st_fq) dfree(q);
+  c->st_fq.clear();
+  c->st_fq_len.clear();
+  c->st_cap = c->st_cm_len = c->st_part_len = c->st_colpart_len = c->st_gbuf_len = 0;
   c->st_state = 0;
   c->st_failed = false;
+}
+
+// The fold matrices of a stream opened with folds go with S.
+void fold_free(ppls_ctx* c) {
+  dfree(c->st_fS);
+  c->st_nfolds = 0;
+  c->st_sel = -1;
+  c->st_fN.clear();
+  c->st_fmean_h.clear();
 }
 
 void xprod_free(ppls_ctx* c) {
@@ -1142,6 +1176,7 @@ void xprod_free(ppls_ctx* c) {
   c->xp_active = false;
   dfree(c->xp_S);
   dfree(c->xp_M);
+  fold_free(c);
   // (the int8 Gram's residue planes are a workspace, not S: kept until gram_int8 = 0, the context's
   // end or an allocation that needs the room -- freeing and re-allocating tens of GB per formation
   // cost 1-5 s per call on some boxes, profiles/r6_gram_int8_percol_c3.jsonl)
@@ -1384,6 +1419,7 @@ void ppls_ctx_destroy(ppls_ctx* c) {
   dfree(c->stop_d);
   c->st_state = 0;
   stream_release(c);
+  fold_free(c);
   for (int b = 0; b < 2; ++b)
     if (c->st_done[b]) (void)hipEventDestroy(c->st_done[b]);
   if (c->st_stream) (void)hipStreamDestroy(c->st_stream);
@@ -4198,15 +4234,17 @@ int stream_reserve(ppls_ctx* c, int64_t n, bool colmajor) {
   return PPLS_OK;
 }
 
-// The device work of the chunk staged in buffer b (n rows), enqueued on st_stream.
-int stream_process(ppls_ctx* c, int b, int64_t n) {
+// The four steps of one chunk (or of one fold segment of a chunk): n staged rows Xs, Ys merged into the
+// Chan state (Nprev rows, mean, S), enqueued on st_stream.  qslot: where the Gram's work queue goes (null:
+// the context's kept queue, rebuilt behind a drain of st_stream when the row count changes -- a fold
+// stream's segments differ in length every time, and that drain would undo the overlap with the next upload).
+int stream_merge_rows(ppls_ctx* c, double* Xs, double* Ys, int64_t n, double* S, double* mean, int64_t Nprev,
+                      int** qslot = nullptr, int64_t* qlen = nullptr) {
   int rc;
   const int P = c->ldx + c->ldy;
   hipStream_t s = c->st_stream;
-  double* Xs = c->st_buf[b];
-  double* Ys = Xs + c->st_cap * c->ldx;
-  double *sum = c->st_vec, *mc = sum + P, *delta = mc + P, *mean = delta + P, *ones = mean + P;
-  const double N = (double)c->st_rows, nc = (double)n;
+  double *sum = c->st_vec, *mc = sum + P, *delta = mc + P, *ones = delta + 2 * P;
+  const double N = (double)Nprev, nc = (double)n;
   if (c->st_center) {
     const PplsScalePlan px = ppls_scale_plan(n, c->p, 0, c->num_cus), py = ppls_scale_plan(n, c->q, 0, c->num_cus);
     const int64_t plen = std::max(px.nblocks * px.ldc, py.nblocks * py.ldc);
@@ -4223,14 +4261,89 @@ int stream_process(ppls_ctx* c, int b, int64_t n) {
   const int nsplit = gram_nsplit(c, g, n, 0, 0);   // the staged chunk is fp64
   if ((rc = stream_grow(c, &c->st_part, &c->st_part_len, ppls_gram_part_doubles(P, nsplit)))) return rc;
   int* q = nullptr;
-  if ((rc = gram_queue(c, g, n, 0, &q, 0, s))) return stream_fail(c, rc);
+  if (qslot) {   // a fold segment: its own queue, free since st_done of its staging buffer was waited for
+    const int64_t need = ppls_gram_queue_ints(g.p, nsplit);
+    if (*qlen < need) {
+      *qlen = 0;
+      if ((rc = dalloc(c, qslot, (size_t)need))) return stream_fail(c, rc);
+      *qlen = need;
+    }
+    STREAMCHK(c, ppls_gram_queue_prepare(*qslot, g.p, g.xreal, g.xcols, g.yreal, n, gram_wave_slots(c, 0), 0, c->stream));
+    q = *qslot;
+  } else if ((rc = gram_queue(c, g, n, 0, &q, 0, s))) {
+    return stream_fail(c, rc);
+  }
   STREAMCHK(c, ppls_launch_gram_joint(Xs, c->ldx, c->ldx, c->p, Ys, c->ldy, c->ldy, c->q, 0, n, P, nsplit, c->st_part, q, s));
-  STREAMCHK(c, ppls_launch_stream_merge(c->xp_S, c->p, c->ldx, c->q, c->ldy, c->st_part, nsplit,
+  STREAMCHK(c, ppls_launch_stream_merge(S, c->p, c->ldx, c->q, c->ldy, c->st_part, nsplit,
                                         c->st_center ? delta : nullptr, N * nc / (N + nc), s));
+  return PPLS_OK;
+}
+
+// The device work of the chunk staged in buffer b (n rows), enqueued on st_stream.  A fold stream
+// (the chunk's stable fold order is in st_idx[b], its segment offsets in st_seg): the rows are
+// gathered into fold order, then every non-empty segment is merged into its fold's state, in fold
+// order; a fold absent from the chunk launches nothing.
+int stream_process(ppls_ctx* c, int b, int64_t n) {
+  int rc;
+  const int P = c->ldx + c->ldy;
+  hipStream_t s = c->st_stream;
+  double* Xs = c->st_buf[b];
+  double* Ys = Xs + c->st_cap * c->ldx;
+  if (c->st_nfolds > 0) {
+    if ((rc = stream_grow(c, &c->st_gbuf, &c->st_gbuf_len, c->st_cap * P))) return rc;
+    double* Xg = c->st_gbuf;
+    double* Yg = Xg + c->st_cap * c->ldx;
+    STREAMCHK(c, ppls_launch_gather_rows(Xs, c->ldx / 2, Xg, c->ldx / 2, c->ldx / 2, c->st_idx[b], n, s));
+    STREAMCHK(c, ppls_launch_gather_rows(Ys, c->ldy / 2, Yg, c->ldy / 2, c->ldy / 2, c->st_idx[b], n, s));
+    for (int k = 0; k < c->st_nfolds; ++k) {
+      const int64_t lo = c->st_seg[(size_t)k], ns = c->st_seg[(size_t)k + 1] - lo;
+      if (ns == 0) continue;
+      if ((rc = stream_merge_rows(c, Xg + lo * c->ldx, Yg + lo * c->ldy, ns, c->st_fS + (size_t)k * P * P,
+                                  c->st_fmean + (size_t)k * P, c->st_fN[(size_t)k], &c->st_fq[(size_t)b * c->st_nfolds + k],
+                                  &c->st_fq_len[(size_t)b * c->st_nfolds + k])))
+        return rc;
+      c->st_fN[(size_t)k] += ns;
+    }
+  } else if ((rc = stream_merge_rows(c, Xs, Ys, n, c->xp_S, c->st_vec + 3 * P, c->st_rows))) {
+    return rc;
+  }
   STREAMCHK(c, hipEventRecord(c->st_done[b], s));
   c->st_next = b ^ 1;
   c->st_rows += n;
   ++c->st_chunks;
+  return PPLS_OK;
+}
+
+// The stable fold order of a chunk's rows (a counting sort) into st_idx[b] and st_seg, uploaded on
+// the context's stream with the chunk.  The labels were checked.
+int stream_fold_order(ppls_ctx* c, int b, const int32_t* fold, int64_t n) {
+  const int K = c->st_nfolds;
+  std::vector<int64_t>& seg = c->st_seg;
+  seg.assign((size_t)K + 1, 0);
+  for (int64_t i = 0; i < n; ++i) ++seg[(size_t)fold[i] + 1];
+  for (int k = 0; k < K; ++k) seg[(size_t)k + 1] += seg[(size_t)k];
+  std::vector<int64_t> at(seg.begin(), seg.end() - 1), idx((size_t)n);
+  for (int64_t i = 0; i < n; ++i) idx[(size_t)at[(size_t)fold[i]]++] = i;
+  if (c->st_idx_len[b] < n) {   // (st_done[b] was waited for: nothing reads the old list)
+    c->st_idx_len[b] = 0;
+    int rc = dalloc(c, &c->st_idx[b], (size_t)n);
+    if (rc) return stream_fail(c, rc);
+    c->st_idx_len[b] = n;
+  }
+  STREAMCHK(c, hipMemcpy(c->st_idx[b], idx.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice));
+  return PPLS_OK;
+}
+
+// The calls with fold labels belong to a fold stream, those without to a plain one; labels in range.
+int stream_fold_check(ppls_ctx* c, const int32_t* fold, bool labelled, int64_t n) {
+  if (labelled != (c->st_nfolds > 0))
+    return fail(c, PPLS_E_STATE, labelled ? "the stream was opened without folds: use the calls without fold labels"
+                                          : "the stream was opened with %d folds: every chunk needs fold labels", c->st_nfolds);
+  if (!labelled || n == 0) return PPLS_OK;
+  if (!fold) return fail(c, PPLS_E_ARG, "NULL fold labels");
+  for (int64_t i = 0; i < n; ++i)
+    if (fold[i] < 0 || fold[i] >= c->st_nfolds)
+      return fail(c, PPLS_E_ARG, "fold label %d of row %lld outside [0, %d)", fold[i], (long long)i, c->st_nfolds);
   return PPLS_OK;
 }
 
@@ -4243,11 +4356,8 @@ int stream_refuse(ppls_ctx* c, int rc) {
 
 bool st_collective(const ppls_ctx* c) { return c->nranks > 1 || c->reducer; }
 
-}  // namespace
-
-extern "C" {
-
-int ppls_stream_begin(ppls_ctx* c, int p, int q, int center, int scale) {
+// ppls_stream_begin (nfolds = 0) and ppls_stream_begin_folds.
+int stream_begin(ppls_ctx* c, int p, int q, int center, int scale, int nfolds) {
   if (!c) return PPLS_E_ARG;
   if ((center != 0 && center != 1) || (scale != 0 && scale != 1)) return fail(c, PPLS_E_ARG, "center and scale must be 0 or 1");
   HIPCHK(c, hipSetDevice(c->device));
@@ -4259,19 +4369,37 @@ int ppls_stream_begin(ppls_ctx* c, int p, int q, int center, int scale) {
   for (int b = 0; b < 2; ++b)
     if (!c->st_done[b]) HIPCHK(c, hipEventCreateWithFlags(&c->st_done[b], hipEventDisableTiming));
   const int P = c->ldx + c->ldy;
+  const size_t nvec = (size_t)6 * P + 8 + (size_t)nfolds;   // (a fold stream: + the folds' weights at the end)
+  auto drop = [&]() {
+    dfree(c->xp_S);
+    dfree(c->st_vec);
+    dfree(c->st_fS);
+    dfree(c->st_fmean);
+  };
   if ((rc = dalloc(c, &c->xp_S, (size_t)P * P))) return rc;
-  if ((rc = dalloc(c, &c->st_vec, (size_t)6 * P + 8))) { dfree(c->xp_S); return rc; }
-  std::vector<double> v((size_t)6 * P + 8, 0.0);
+  if ((rc = dalloc(c, &c->st_vec, nvec))) { drop(); return rc; }
+  // the fold matrices up front, in one allocation (one collective at the end), and the fold means
+  if (nfolds > 0 && ((rc = dalloc(c, &c->st_fS, (size_t)nfolds * P * P)) || (rc = dalloc(c, &c->st_fmean, (size_t)nfolds * P)))) {
+    drop();
+    return rc;
+  }
+  std::vector<double> v(nvec, 0.0);
   std::fill(v.begin() + (size_t)4 * P, v.begin() + (size_t)5 * P, 1.0);
   hipError_t e = hipMemsetAsync(c->xp_S, 0, sizeof(double) * P * P, c->stream);
+  if (e == hipSuccess && nfolds > 0) e = hipMemsetAsync(c->st_fS, 0, sizeof(double) * nfolds * P * P, c->stream);
+  if (e == hipSuccess && nfolds > 0) e = hipMemsetAsync(c->st_fmean, 0, sizeof(double) * nfolds * P, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(c->st_vec, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   for (int b = 0; b < 2 && e == hipSuccess; ++b) e = hipEventRecord(c->st_done[b], c->st_stream);
   if (e != hipSuccess) {
-    dfree(c->xp_S);
-    dfree(c->st_vec);
+    drop();
     return fail(c, PPLS_E_HIP, "ppls_stream_begin: %s", hipGetErrorString(e));
   }
+  c->st_nfolds = nfolds;
+  c->st_fN.assign((size_t)nfolds, 0);
+  c->st_fq.assign((size_t)2 * nfolds, nullptr);
+  c->st_fq_len.assign((size_t)2 * nfolds, 0);
+  c->st_sel = -1;
   c->st_center = center;
   c->st_scale = scale;
   c->st_rows = c->st_chunks = 0;
@@ -4281,10 +4409,11 @@ int ppls_stream_begin(ppls_ctx* c, int p, int q, int center, int scale) {
   return PPLS_OK;
 }
 
-int ppls_stream_rows(ppls_ctx* c, const double* X, const double* Y, int64_t nrows, int layout) {
+int stream_rows(ppls_ctx* c, const double* X, const double* Y, int64_t nrows, int layout, const int32_t* fold, bool labelled) {
   if (!c) return PPLS_E_ARG;
   int rc;
   if ((rc = stream_open_check(c))) return rc;
+  if ((rc = stream_fold_check(c, fold, labelled, nrows < 0 ? 0 : nrows))) return rc;
   if (nrows == 0) return PPLS_OK;
   if (nrows < 0 || !X || !Y) return fail(c, PPLS_E_ARG, "a chunk needs nrows >= 1 and X, Y");
   if (layout != PPLS_LAYOUT_COLMAJOR && layout != PPLS_LAYOUT_ROWMAJOR)
@@ -4292,6 +4421,7 @@ int ppls_stream_rows(ppls_ctx* c, const double* X, const double* Y, int64_t nrow
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = stream_reserve(c, nrows, layout == PPLS_LAYOUT_COLMAJOR))) return rc;
   const int b = c->st_next;
+  if (labelled && (rc = stream_fold_order(c, b, fold, nrows))) return rc;
   for (int m = 0; m < 2; ++m) {
     const double* src = m == 0 ? X : Y;
     const int cols = m == 0 ? c->p : c->q, ld = m == 0 ? c->ldx : c->ldy;
@@ -4309,7 +4439,7 @@ int ppls_stream_rows(ppls_ctx* c, const double* X, const double* Y, int64_t nrow
   return stream_process(c, b, nrows);
 }
 
-int ppls_stream_rows_from(ppls_ctx* c, ppls_ctx* src) {
+int stream_rows_from(ppls_ctx* c, ppls_ctx* src, const int32_t* fold, bool labelled) {
   if (!c || !src) return c ? fail(c, PPLS_E_ARG, "NULL source context") : PPLS_E_ARG;
   int rc;
   if ((rc = stream_open_check(c))) return rc;
@@ -4320,11 +4450,13 @@ int ppls_stream_rows_from(ppls_ctx* c, ppls_ctx* src) {
   if (src->p != c->p || src->q != c->q)
     return fail(c, PPLS_E_ARG, "the source holds p=%d q=%d, the stream was begun with p=%d q=%d", src->p, src->q, c->p, c->q);
   const int64_t n = src->n_local;
+  if ((rc = stream_fold_check(c, fold, labelled, n))) return rc;
   if (n == 0) return PPLS_OK;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(src->stream));
   if ((rc = stream_reserve(c, n, false))) return rc;
   const int b = c->st_next;
+  if (labelled && (rc = stream_fold_order(c, b, fold, n))) return rc;
   CvScratch tmp;
   for (int m = 0; m < 2; ++m) {
     const void* sp = m == 0 ? src->X : src->Y;
@@ -4342,6 +4474,213 @@ int ppls_stream_rows_from(ppls_ctx* c, ppls_ctx* src) {
   }
   STREAMCHK(c, hipStreamSynchronize(c->stream));
   return stream_process(c, b, n);
+}
+
+// xp_S = the sum of the fold matrices but `fold` (-1: all), with n_total and ||X||^2, ||Y||^2 (the
+// traces of S's diagonal blocks, in column order) to match.  No state checks.
+int fold_select(ppls_ctx* c, int fold) {
+  const int p = c->p, q = c->q, ldx = c->ldx, P = c->ldx + c->ldy;
+  HIPCHK(c, ppls_launch_cvs_select(c->st_fS, c->st_nfolds, fold, (int64_t)P * P, c->xp_S, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<double> diag((size_t)P);
+  HIPCHK(c, hipMemcpy2D(diag.data(), sizeof(double), c->xp_S, sizeof(double) * ((size_t)P + 1), sizeof(double), (size_t)P,
+                        hipMemcpyDeviceToHost));
+  double s2[2] = {0.0, 0.0};
+  for (int j = 0; j < p; ++j) s2[0] += diag[(size_t)j];
+  for (int j = 0; j < q; ++j) s2[1] += diag[(size_t)ldx + j];
+  HIPCHK(c, hipMemcpy(c->ssq, s2, sizeof s2, hipMemcpyHostToDevice));
+  c->ssq_host[0] = s2[0];
+  c->ssq_host[1] = s2[1];
+  int64_t N = 0;
+  for (int k = 0; k < c->st_nfolds; ++k)
+    if (k != fold) N += c->st_fN[(size_t)k];
+  c->n_total = N;
+  c->st_sel = fold;
+  return PPLS_OK;
+}
+
+// The calls that read the fold matrices: a context streamed with folds.
+int fold_state_check(ppls_ctx* c) {
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  if (c->st_state != 2 || c->st_nfolds < 1)
+    return fail(c, PPLS_E_STATE, "the context holds no fold cross-products: stream the rows with ppls_stream_begin_folds");
+  return PPLS_OK;
+}
+
+// ppls_stream_end of a fold stream, up to and including the finish.  Returns with
+// *left = true where the caller must return at once (the stream is dropped already: a collective
+// failed, or a failure every rank agreed on), else this rank's verdict on the finish, which the
+// caller's last collective shares.  On PPLS_OK: *N_out rows over all ranks, the transform in cen / scl,
+// ||X||^2, ||Y||^2 in s2, and the context selected on all folds.
+int fold_end(ppls_ctx* c, double* N_out, std::vector<double>& cen, std::vector<double>& scl, double s2[2], bool* left) {
+  *left = true;
+#define FENDCHK(call)                                                                                             \
+  do {                                                                                                            \
+    hipError_t e_ = (call);                                                                                       \
+    if (e_ != hipSuccess)                                                                                         \
+      return stream_refuse(c, fail(c, PPLS_E_HIP, "%s: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__)); \
+  } while (0)
+  int rc;
+  const int K = c->st_nfolds, p = c->p, q = c->q, ldx = c->ldx, P = c->ldx + c->ldy;
+  const size_t PP = (size_t)P * P, KP = (size_t)K * P;
+  std::vector<double> fm(KP, 0.0), Nk((size_t)K);
+  for (int k = 0; k < K; ++k) Nk[(size_t)k] = (double)c->st_fN[(size_t)k];
+  if (!c->st_failed && hipMemcpy(fm.data(), c->st_fmean, sizeof(double) * KP, hipMemcpyDeviceToHost) != hipSuccess)
+    c->st_failed = true;
+  if (st_collective(c)) {
+    // {failed, N_rk, N_rk m_rk for all k}: the global fold counts and fold means, and the agreement
+    // that nobody failed, in one all-reduce
+    const size_t nred = 1 + (size_t)K + KP;
+    CvScratch tmp;
+    double* red = nullptr;
+    if ((rc = tmp.get(c, &red, nred))) return stream_refuse(c, rc);
+    std::vector<double> h(nred, 0.0);
+    h[0] = c->st_failed ? 1.0 : 0.0;
+    for (int k = 0; k < K; ++k) {
+      h[(size_t)1 + k] = Nk[(size_t)k];
+      for (int j = 0; j < P; ++j)
+        h[1 + (size_t)K + (size_t)k * P + j] = c->st_failed ? 0.0 : Nk[(size_t)k] * fm[(size_t)k * P + j];
+    }
+    FENDCHK(hipMemcpyAsync(red, h.data(), sizeof(double) * nred, hipMemcpyHostToDevice, c->stream));
+    if ((rc = allreduce(c, red, nred))) return stream_refuse(c, rc);
+    FENDCHK(hipMemcpyAsync(h.data(), red, sizeof(double) * nred, hipMemcpyDeviceToHost, c->stream));
+    FENDCHK(hipStreamSynchronize(c->stream));
+    if (h[0] > 0.0)
+      return stream_refuse(c, fail(c, PPLS_E_STATE, "the stream failed on %d rank(s) before ppls_stream_end", (int)h[0]));
+    // each rank's S_k is centred about its own fold mean: + N_rk (m_rk - m_k)(m_rk - m_k)', the merge
+    // with no partials, fold by fold
+    std::vector<double> d(KP, 0.0);
+    for (int k = 0; k < K; ++k)
+      for (int j = 0; j < P; ++j) {
+        const size_t at = (size_t)k * P + j;
+        const double mg = h[(size_t)1 + k] > 0.0 ? h[1 + (size_t)K + at] / h[(size_t)1 + k] : 0.0;
+        d[at] = fm[at] - mg;
+        fm[at] = mg;
+      }
+    hipError_t e = hipSuccess;
+    if (c->st_center) {
+      e = hipMemcpyAsync(c->st_fmean, d.data(), sizeof(double) * KP, hipMemcpyHostToDevice, c->stream);
+      for (int k = 0; k < K && e == hipSuccess; ++k)
+        if (Nk[(size_t)k] > 0.0)
+          e = ppls_launch_stream_merge(c->st_fS + (size_t)k * PP, p, ldx, q, c->ldy, nullptr, 0, c->st_fmean + (size_t)k * P,
+                                       Nk[(size_t)k], c->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
+    for (int k = 0; k < K; ++k) Nk[(size_t)k] = h[(size_t)1 + k];
+    // nobody enters the all-reduce of the fold matrices alone
+    const double f = e == hipSuccess ? 0.0 : 1.0;
+    double tot = 0.0;
+    FENDCHK(hipMemcpyAsync(c->flag, &f, sizeof f, hipMemcpyHostToDevice, c->stream));
+    if ((rc = allreduce(c, c->flag, 1))) return stream_refuse(c, rc);
+    FENDCHK(hipMemcpyAsync(&tot, c->flag, sizeof tot, hipMemcpyDeviceToHost, c->stream));
+    FENDCHK(hipStreamSynchronize(c->stream));
+    if (tot > 0.0)
+      return stream_refuse(c, fail(c, PPLS_E_HIP, "the cross-rank merge of the fold matrices failed on %d rank(s)", (int)tot));
+    if ((rc = allreduce(c, c->st_fS, (size_t)K * PP))) return stream_refuse(c, rc);
+    FENDCHK(hipStreamSynchronize(c->stream));
+  } else if (c->st_failed) {
+    return stream_refuse(c, fail(c, PPLS_E_STATE, "the stream failed before ppls_stream_end"));
+  }
+#undef FENDCHK
+  // From here every rank holds the same fold matrices, counts and fold means; the steps below run on
+  // this rank alone and give the same bits on every rank.
+  *left = false;
+  auto hip_failed = [&](hipError_t e, const char* what) -> int {
+    return e == hipSuccess ? PPLS_OK : fail(c, PPLS_E_HIP, "ppls_stream_end, %s: %s", what, hipGetErrorString(e));
+  };
+  double N = 0.0;
+  for (int k = 0; k < K; ++k) {
+    if (!(Nk[(size_t)k] >= 1.0))
+      return fail(c, PPLS_E_ARG, "fold %d holds no row (over all ranks): every fold needs at least one; the stream is dropped", k);
+    N += Nk[(size_t)k];
+  }
+  // the global mean, summed in fold order, and the folds' offsets from it
+  std::vector<double> m((size_t)P, 0.0), ev(KP, 0.0), w((size_t)K), d((size_t)P, 1.0), dsum((size_t)P);
+  for (int j = 0; j < P; ++j) {
+    double acc = 0.0;
+    for (int k = 0; k < K; ++k) acc += Nk[(size_t)k] * fm[(size_t)k * P + j];
+    m[(size_t)j] = acc / N;
+  }
+  if (c->st_center)
+    for (int k = 0; k < K; ++k)
+      for (int j = 0; j < P; ++j) ev[(size_t)k * P + j] = fm[(size_t)k * P + j] - m[(size_t)j];
+  for (int k = 0; k < K; ++k) w[(size_t)k] = Nk[(size_t)k];
+  double *vec = c->st_vec, *wd = vec + 6 * (size_t)P + 8;
+  hipError_t e = hipMemcpyAsync(c->st_fmean, ev.data(), sizeof(double) * KP, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(wd, w.data(), sizeof(double) * K, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = ppls_launch_cvs_diag(c->st_fS, K, p, ldx, q, c->ldy, c->st_fmean, wd, vec + P, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(dsum.data(), vec + P, sizeof(double) * P, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if ((rc = hip_failed(e, "the diagonal of the fold matrices"))) return rc;
+  double tr[2] = {0.0, 0.0};
+  for (int j = 0; j < p; ++j) tr[0] += dsum[(size_t)j];
+  for (int j = 0; j < q; ++j) tr[1] += dsum[(size_t)ldx + j];
+  for (int k = 0; k < 2; ++k)
+    if (!std::isfinite(tr[k]))
+      return fail(c, PPLS_E_ARG,
+                  "%c contains NaN or Inf (the trace of its streamed cross-products is %g; values beyond 1.3e154 "
+                  "also overflow it): the reference's svd() in orth() stops on non-finite data (EM_W_multi.R:732-733)",
+                  k ? 'Y' : 'X', tr[k]);
+  for (int j = 0; j < p + q; ++j) {
+    cen[(size_t)j] = c->st_center ? m[(size_t)(j < p ? j : ldx + j - p)] : 0.0;
+    scl[(size_t)j] = 1.0;
+  }
+  if (c->st_scale) {
+    if (N < 2.0)
+      return fail(c, PPLS_E_ARG, "scale = TRUE needs at least 2 rows (over all ranks: %lld): the standard deviation "
+                                 "divides by n - 1", (long long)N);
+    for (int j = 0; j < p + q; ++j) {
+      const int jj = j < p ? j : ldx + j - p;
+      const double dj = std::sqrt(dsum[(size_t)jj] / (N - 1.0));
+      if (!(dj > 0.0) || !std::isfinite(dj))
+        return fail(c, PPLS_E_ARG, "%c column %d has standard deviation %g (over all ranks): scale = TRUE would fill it "
+                                   "with NaN or Inf, as R's scale() does; the stream is dropped",
+                    j < p ? 'X' : 'Y', (j < p ? j : j - p) + 1, dj);
+      d[(size_t)jj] = scl[(size_t)j] = dj;
+    }
+  }
+  if (c->st_center || c->st_scale) {   // one pass over every fold matrix: recentre and standardise
+    e = hipMemcpyAsync(vec, d.data(), sizeof(double) * P, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = ppls_launch_cvs_finish(c->st_fS, K, p, ldx, q, c->ldy, c->st_fmean, wd, vec, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if ((rc = hip_failed(e, "recentring and standardising the fold matrices"))) return rc;
+  }
+  for (int k = 0; k < K; ++k) c->st_fN[(size_t)k] = (int64_t)Nk[(size_t)k];
+  c->st_fmean_h = fm;
+  if ((rc = fold_select(c, -1))) return rc;
+  s2[0] = c->ssq_host[0];
+  s2[1] = c->ssq_host[1];
+  *N_out = N;
+  return PPLS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ppls_stream_begin(ppls_ctx* c, int p, int q, int center, int scale) {
+  return stream_begin(c, p, q, center, scale, 0);
+}
+
+int ppls_stream_begin_folds(ppls_ctx* c, int p, int q, int center, int scale, int nfolds) {
+  if (!c) return PPLS_E_ARG;
+  if (nfolds < 2) return fail(c, PPLS_E_ARG, "Cross-validation with 1 fold does not make sense, use 2 folds or more");
+  if (nfolds > 65535) return fail(c, PPLS_E_ARG, "nfolds=%d: at most 65535 folds", nfolds);
+  return stream_begin(c, p, q, center, scale, nfolds);
+}
+
+int ppls_stream_rows(ppls_ctx* c, const double* X, const double* Y, int64_t nrows, int layout) {
+  return stream_rows(c, X, Y, nrows, layout, nullptr, false);
+}
+
+int ppls_stream_rows_folds(ppls_ctx* c, const double* X, const double* Y, int64_t nrows, int layout, const int32_t* fold) {
+  return stream_rows(c, X, Y, nrows, layout, fold, true);
+}
+
+int ppls_stream_rows_from(ppls_ctx* c, ppls_ctx* src) { return stream_rows_from(c, src, nullptr, false); }
+
+int ppls_stream_rows_from_folds(ppls_ctx* c, ppls_ctx* src, const int32_t* fold) {
+  return stream_rows_from(c, src, fold, true);
 }
 
 int ppls_stream_end(ppls_ctx* c) {
@@ -4367,7 +4706,9 @@ int ppls_stream_end(ppls_ctx* c) {
   std::vector<double> m((size_t)P, 0.0), h((size_t)P + 2, 0.0);
   if (!c->st_failed && hipMemcpy(m.data(), mean, sizeof(double) * P, hipMemcpyDeviceToHost) != hipSuccess) c->st_failed = true;
   double N = (double)c->st_rows;
-  if (st_collective(c)) {
+  const bool folds = c->st_nfolds > 0;   // a fold stream: fold_end below runs its collectives and its finish
+  if (folds) {
+  } else if (st_collective(c)) {
     // {failed, N_r, N_r m_r}: the global N and mean, and the agreement that nobody failed, in one all-reduce
     const double Nr = N;
     h[0] = c->st_failed ? 1.0 : 0.0;
@@ -4457,7 +4798,14 @@ int ppls_stream_end(ppls_ctx* c) {
     }
     return hip_failed(hipMemcpy(c->ssq, s2, sizeof s2, hipMemcpyHostToDevice), "||X||^2, ||Y||^2");
   };
-  int local = finish_S();
+  int local;
+  if (folds) {
+    bool left = false;
+    local = fold_end(c, &N, cen, scl, s2, &left);
+    if (left) return local;
+  } else {
+    local = finish_S();
+  }
   const std::string local_err = c->err;
   // the staging buffers and partials go back before the free memory is read: the smallest free HBM
   // over all ranks, as compute_ssq records it, beside the agreement on the steps above
@@ -4509,6 +4857,117 @@ int ppls_stream_info(ppls_ctx* c, int* state, int64_t* rows_local, int64_t* n_to
   if (rows_local) *rows_local = c->st_state ? c->st_rows : 0;
   if (n_total) *n_total = c->st_state == 2 ? c->n_total : c->st_state == 1 ? c->st_rows : 0;
   if (chunks) *chunks = c->st_state ? c->st_chunks : 0;
+  return PPLS_OK;
+}
+
+int ppls_stream_fold_info(ppls_ctx* c, int* nfolds, int64_t* fold_total, int* selected) {
+  if (!c) return PPLS_E_ARG;
+  const int K = c->st_state ? c->st_nfolds : 0;
+  if (nfolds) *nfolds = K;
+  if (fold_total)
+    for (int k = 0; k < K; ++k) fold_total[k] = c->st_fN[(size_t)k];
+  if (selected) *selected = c->st_state == 2 && K > 0 ? c->st_sel : -1;
+  return PPLS_OK;
+}
+
+int ppls_stream_select(ppls_ctx* c, int fold) {
+  if (!c) return PPLS_E_ARG;
+  int rc;
+  if ((rc = fold_state_check(c))) return rc;
+  if (c->em_active)
+    return fail(c, PPLS_E_STATE, "an ppls_em_begin session is active on the selected cross-products: finish it before selecting");
+  if (fold < -1 || fold >= c->st_nfolds) return fail(c, PPLS_E_ARG, "fold %d outside [-1, %d)", fold, c->st_nfolds);
+  HIPCHK(c, hipSetDevice(c->device));
+  return fold_select(c, fold);
+}
+
+int ppls_heldout_sse_fold(ppls_ctx* c, const double* W, const double* C, const double* B, int k, int fold, double* sse,
+                          double* mag) {
+  if (!c) return PPLS_E_ARG;
+  int rc;
+  if ((rc = fold_state_check(c))) return rc;
+  if (!W || !C || !B || !sse || k < 1 || k > PPLS_RMAX)
+    return fail(c, PPLS_E_ARG, "W, C, B, sse must be given with 1 <= k <= %d", PPLS_RMAX);
+  if (fold < 0 || fold >= c->st_nfolds) return fail(c, PPLS_E_ARG, "fold %d outside [0, %d)", fold, c->st_nfolds);
+  HIPCHK(c, hipSetDevice(c->device));
+  CvScratch tmp;
+  double *Wd = nullptr, *Cd = nullptr, *Bd = nullptr, *work = nullptr, *out = nullptr;
+  if ((rc = cv_upload_coef(c, tmp, W, c->p, k, &Wd))) return rc;
+  if ((rc = cv_upload_coef(c, tmp, C, c->q, k, &Cd))) return rc;
+  if ((rc = cv_upload_coef(c, tmp, B, k, 1, &Bd))) return rc;
+  if ((rc = tmp.get(c, &work, (size_t)4 * c->p * k))) return rc;
+  if ((rc = tmp.get(c, &out, (size_t)2 * k))) return rc;
+  const size_t PP = (size_t)(c->ldx + c->ldy) * (c->ldx + c->ldy);
+  std::vector<double> h((size_t)2 * k);
+  HIPCHK(c, ppls_launch_cvs_heldout(c->st_fS + (size_t)fold * PP, c->p, c->ldx, c->q, c->ldy, Wd, Cd, Bd, k, work, out, out + k,
+                                    c->stream));
+  HIPCHK(c, hipMemcpyAsync(h.data(), out, sizeof(double) * 2 * k, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int j = 0; j < k; ++j) {
+    sse[j] = h[(size_t)j];
+    if (mag) mag[j] = h[(size_t)k + j];
+  }
+  return PPLS_OK;
+}
+
+int ppls_cv_ppls_stream(ppls_ctx* c, int a, int max_steps, double atol, int crit_abs, const ppls_theta* init, double* rmsep,
+                        int* ncomp, double* cond) {
+  if (!c) return PPLS_E_ARG;
+  int rc;
+  if ((rc = fold_state_check(c))) return rc;
+  if (c->em_active)
+    return fail(c, PPLS_E_STATE, "an ppls_em_begin session is active on the selected cross-products: finish it before cross-validating");
+  if (!init || !rmsep || !ncomp) return fail(c, PPLS_E_ARG, "NULL argument");
+  if (a < 1 || a > PPLS_RMAX) return fail(c, PPLS_E_ARG, "nr_comp=%d outside [1,%d]", a, PPLS_RMAX);
+  const int K = c->st_nfolds, p = c->p, q = c->q;
+  for (int k = 0; k < K * a; ++k)
+    if (!init[k].W || !init[k].C || !init[k].B || !init[k].sigT) return fail(c, PPLS_E_ARG, "init[%d] has NULL fields", k);
+  std::vector<double> W((size_t)p * a), C((size_t)q * a), B((size_t)a), sig((size_t)4 * a), sse((size_t)a), mag((size_t)a);
+  auto run = [&]() -> int {
+    int r;
+    for (int f = 0; f < K; ++f) {
+      if ((r = ppls_stream_select(c, f))) return r;
+      if (c->n_total < 1) return fail(c, PPLS_E_ARG, "fold %d leaves no training row", f);
+      ppls_seq_fit fit;
+      memset(&fit, 0, sizeof fit);
+      fit.W = W.data();
+      fit.C = C.data();
+      fit.B = B.data();
+      fit.sig = sig.data();
+      if ((r = ppls_ppls_ex(c, a, max_steps, atol, crit_abs, init + (size_t)f * a, nullptr, &fit))) return r;
+      ncomp[f] = fit.ncomp;
+      for (int j = 0; j < a; ++j) {
+        rmsep[(size_t)f * a + j] = NAN;
+        if (cond) cond[(size_t)f * a + j] = NAN;
+      }
+      if (fit.ncomp < 1) continue;
+      if ((r = ppls_heldout_sse_fold(c, W.data(), C.data(), B.data(), fit.ncomp, f, sse.data(), mag.data()))) return r;
+      for (int j = 0; j < fit.ncomp; ++j) {
+        rmsep[(size_t)f * a + j] = std::sqrt(sse[(size_t)j] / ((double)c->st_fN[(size_t)f] * q));
+        if (cond) cond[(size_t)f * a + j] = mag[(size_t)j] / sse[(size_t)j];
+      }
+    }
+    return PPLS_OK;
+  };
+  rc = run();
+  // selected on all folds again, also after an error (whose message stays)
+  const std::string err = c->err;
+  const int rs = fold_select(c, -1);
+  if (rc) c->err = err;
+  return rc ? rc : rs;
+}
+
+int ppls_stream_fold_get(ppls_ctx* c, int fold, double* S, double* mean, int64_t* n) {
+  if (!c) return PPLS_E_ARG;
+  int rc;
+  if ((rc = fold_state_check(c))) return rc;
+  if (fold < 0 || fold >= c->st_nfolds) return fail(c, PPLS_E_ARG, "fold %d outside [0, %d)", fold, c->st_nfolds);
+  const int P = c->ldx + c->ldy;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (S) HIPCHK(c, hipMemcpy(S, c->st_fS + (size_t)fold * P * P, sizeof(double) * P * P, hipMemcpyDeviceToHost));
+  if (mean) memcpy(mean, c->st_fmean_h.data() + (size_t)fold * P, sizeof(double) * P);
+  if (n) *n = c->st_fN[(size_t)fold];
   return PPLS_OK;
 }
 
