@@ -40,6 +40,11 @@ int ppls_xprod_tile_timing(ppls_ctx* ctx, int reps, double* ms);
 /* One statistics step from S for theta: stats = [X'mu_T p x r | Y'mu_U q x r | Gram 2r x 2r], all
  * column-major, as ppls_finalize_host takes them (unit parity against the sweep and a host S B). */
 int ppls_xprod_stats(ppls_ctx* ctx, const ppls_theta* th, int r, double* stats);
+/* One statistics step by the sweep for theta, the twin of ppls_xprod_stats: the kernel is the one
+ * ppls_sweep_kernel names under the context's current options; stats in the same layout.  want_mu:
+ * the sweep also writes the moments (its waits then drain the DMA ring instead of counting), and mu
+ * (nullable) receives this rank's n_local x 2r [mu_T | mu_U], column-major.  Needs resident rows. */
+int ppls_sweep_stats(ppls_ctx* ctx, const ppls_theta* th, int r, int want_mu, double* stats, double* mu);
 /* Shape facts for the roofline: bytes of X and Y one sweep reads (algorithmic), kernel variant. */
 int ppls_sweep_info(ppls_ctx* ctx, int r, int64_t* bytes_per_sweep, int* variant, int* grid);
 /* The sweep kernel instantiation the next EM iteration with r components launches, as text

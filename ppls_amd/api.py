@@ -616,6 +616,20 @@ class Context:
         G = out[(self.p + self.q) * r:].reshape(2 * r, 2 * r).T
         return SX, SY, G
 
+    def sweep_stats(self, th: Theta, want_mu=False):
+        """One statistics step by the sweep for theta (the kernel ``sweep_kernel(r)`` names, under the
+        current options): (X'mu_T p x r, Y'mu_U q x r, Gram 2r x 2r, mu), mu = this rank's
+        n_local x 2r [mu_T | mu_U] when want_mu, else None."""
+        r = th.r
+        out = np.zeros(r * (self.p + self.q) + 4 * r * r)
+        mu = np.zeros((self.n_local, 2 * r), order="F") if want_mu else None
+        t = th.struct()
+        self._chk(self._L.ppls_sweep_stats(self.h, ct.byref(t), r, int(bool(want_mu)), dptr(out), dptr(mu)))
+        SX = out[: self.p * r].reshape(r, self.p).T
+        SY = out[self.p * r: (self.p + self.q) * r].reshape(r, self.q).T
+        G = out[(self.p + self.q) * r:].reshape(2 * r, 2 * r).T
+        return SX, SY, G, mu
+
     def xprod_info(self, r=1):
         """{ready, bytes_per_pass (8 P^2), gram_flops (as computed), rows_per_wave} of the cross-product form."""
         rd, b, f, rw = ct.c_int(), ct.c_int64(), ct.c_double(), ct.c_int()

@@ -3396,6 +3396,31 @@ int ppls_xprod_stats(ppls_ctx* c, const ppls_theta* th, int r, double* stats) {
   return PPLS_OK;
 }
 
+int ppls_sweep_stats(ppls_ctx* c, const ppls_theta* th, int r, int want_mu, double* stats, double* mu) {
+  if (!c || !stats) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
+  int rc;
+  if ((rc = check_theta(c, th, r))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = ensure_r(c, r, 1))) return rc;
+  if ((rc = upload_theta(c, th, r, 0))) return rc;
+  if ((rc = sweep(c, r, 0, want_mu != 0))) return rc;
+  std::vector<double> st((size_t)c->part_ld);
+  HIPCHK(c, hipMemcpyAsync(st.data(), c->stats, sizeof(double) * st.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int k = 0; k < r; ++k) {
+    for (int i = 0; i < c->p; ++i) stats[(size_t)k * c->p + i] = st[(size_t)k * c->ldx + i];
+    for (int i = 0; i < c->q; ++i)
+      stats[(size_t)r * c->p + (size_t)k * c->q + i] = st[(size_t)r * c->ldx + (size_t)k * c->ldy + i];
+  }
+  for (int e = 0; e < 4 * r * r; ++e)
+    stats[(size_t)r * (c->p + c->q) + e] = st[(size_t)r * (c->ldx + c->ldy) + e];
+  if (want_mu && mu && c->n_local > 0)
+    HIPCHK(c, hipMemcpy(mu, c->mu, sizeof(double) * (size_t)c->n_local * 2 * r, hipMemcpyDeviceToHost));
+  return PPLS_OK;
+}
+
 int ppls_sweep_timing(ppls_ctx* c, double* total_ms, int64_t* launches, int reset) {
   if (!c) return PPLS_E_ARG;
   HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -399,6 +399,7 @@ def test_streamed_state_refusals():
             em_step_mu=lambda: c.em_step(th, want_fit=True),
             mstep=lambda: c.mstep(e_in),
             scores=lambda: c.scores(th0["W"], th0["C"]),
+            sweep_stats=lambda: c.sweep_stats(th),
             scores_PPLS=lambda: scores_PPLS(fit, None, None, ctx=c),
             get_data=lambda: c.get_data(0, 0),
             get_data_rows=lambda: c.get_data_rows(0, 0),
