@@ -107,6 +107,20 @@ const char* ppls_last_error(const ppls_ctx* ctx);
  *                      every population from one read of X, Y per EM step (the split sweep: one
  *                      segmented launch; fp32 storage / wide p, the panel sweep: one launch per
  *                      population); 0 the per-population loop driven by the host),
+ *       "meta_xprod" (ppls_meta_emstep / ppls_meta_ppls on resident rows: 0, default, sweep the rows
+ *                     every EM step; 1 take every statistic from the populations' cross-products
+ *                     S_j = [X_j Y_j]'[X_j Y_j]: formed once on the fp64 MFMA Gram from each
+ *                     population's local row block (either storage type; "gram_int8" does not apply),
+ *                     all-reduced once when sharded (all K matrices in one all-reduce, after the ranks
+ *                     agreed that each could allocate them: else PPLS_E_NOMEM on every rank alike), then
+ *                     an EM step reads K 8 (p+q)^2 bytes and needs no collective.  The K matrices stay
+ *                     with the pop_local / pop_total they were formed for -- a second fit with other
+ *                     starting values or atol forms nothing -- until the data change (ppls_set_data,
+ *                     ppls_generate_synthetic, ppls_scale_data, ppls_set_data_from, a stream), other
+ *                     populations are passed, meta_xprod goes to 0 or ppls_ctx_destroy.  The
+ *                     populations' sums of squares stay those of the rows.  Takes precedence over
+ *                     "meta_device"; at most 1024 populations.  One formation costs about one full
+ *                     Gram, so it pays only for long or repeated fits: opt-in),
  *       "gram_int8" (the Gram that forms S and ppls_variances' X'X: 0, default, fp64 MFMA; 1 the
  *                    int8-MFMA Chinese-remainder form when the columns' spread allows it -- else the
  *                    fp64 one; ppls_gram_info.  Its residue planes (17 x n x (p + q) bytes at C3's
@@ -115,7 +129,8 @@ const char* ppls_last_error(const ppls_ctx* ctx);
  *                    device allocation of the library that fails frees them and tries again),
  *       "vorth" (the finalize re-orthonormalises the Jacobi warm start it carries between
  *                iterations every vorth-th iteration: 1 .. 255, default 8),
- *       "xprod_rw" (rows of S per wave of the cross-product tile kernel: 0 auto, 1, 2, 4, 8),
+ *       "xprod_rw" (rows of S per wave of the cross-product tile kernel and of the meta statistics pass
+ *                   over the population matrices: 0 auto -- each kernel's own rule --, 1, 2, 4, 8),
  *       "xprod_fuse" (1, default: the finalize after a cross-product step forms the 2r x 2r Gram
  *                     itself when r <= 8 and p + q <= 6144; 0: a separate Gram kernel),
  *       "dots_rows" (panel sweep dots: rows per wave, 0 auto (64 from 32768 rows, else 32), 32, 64),
@@ -270,6 +285,27 @@ typedef struct {
 /* crit_abs: 0 critfunc = identity (default), 1 critfunc = abs.  init: theta with r = 1. */
 int ppls_meta_ppls(ppls_ctx* ctx, int npop, const int64_t* pop_local, const int64_t* pop_total,
                    int max_steps, double atol, int crit_abs, const ppls_theta* init, ppls_meta_fit* out);
+/* The same two on a context streamed with folds (ppls_stream_begin_folds .. ppls_stream_end, below):
+ * the fold labels are the populations in level order 0 .. K-1, N_j the fold's rows over all ranks; no
+ * rows and no row arguments.  meta_PPLSi takes X and Y as given and splits them by Ipopu without
+ * centring per population, which is exactly what the fold matrices S_j hold (centred and scaled as a
+ * whole, if the stream was asked to), and every statistic of a step is a quadratic form in S_j:
+ *   X_j'mu_T = S_j,xx w alpha_j + S_j,xy c beta_j,   Y_j'mu_U = S_j,yx w gamma_j + S_j,yy c delta_j,
+ *   Gram([X_j w, Y_j c]) = blockdiag(w, c)' S_j blockdiag(w, c),   ssq(X_j), ssq(Y_j) = the traces of
+ * S_j's diagonal blocks (summed in column order).  An EM step reads K 8 (p+q)^2 bytes in one pass with
+ * fixed-order sums.  Meaning, outputs and error returns are those of ppls_meta_emstep /
+ * ppls_meta_ppls, the PPLS_E_NUMERIC of a NaN increment and the refusal of all-zero X or Y included
+ * (judged on all streamed rows).  ppls_meta_ppls_stream runs the whole loop on the device.
+ * PPLS_E_STATE: a context not streamed with folds (a plain stream, an open stream, resident data, no
+ * data) and while an ppls_em_begin session is active.  The calls read the fold matrices directly: they
+ * neither need nor change the selection of ppls_stream_select.  No collective: after ppls_stream_end
+ * every rank holds identical fold matrices, so every rank computes identical bits.  One population
+ * cannot be streamed this way (a fold stream has K >= 2); ppls_ppls on a plain stream is that fit. */
+int ppls_meta_emstep_stream(ppls_ctx* ctx, const double* W, const double* C, const double* params_in,
+                            double* W_out, double* C_out, double* params_out,
+                            double* Cxt /* p x K, nullable */, double* Cyu /* q x K, nullable */);
+int ppls_meta_ppls_stream(ppls_ctx* ctx, int max_steps, double atol, int crit_abs, const ppls_theta* init,
+                          ppls_meta_fit* out);
 
 /* loglC_fast (src/loglC.cpp:318-338) with the reference's argument list.  X, Y (column-major
  * n x p / n x q host matrices) are uploaded into ctx like Rcpp's input_parameter copies them;
@@ -379,8 +415,9 @@ int ppls_cv_ppls(ppls_ctx* ctx, int a, int nfolds, const int32_t* fold_of_row /*
  *     ppls_estep, ppls_em_step or ppls_em_run; ppls_mstep (X'mu_T of caller-supplied mu needs the rows);
  *     ppls_scores; ppls_get_data / _rows; ppls_variances; ppls_heldout_sse; ppls_cv_ppls;
  *     ppls_set_data_from / ppls_xprod_downdate with a streamed source; ppls_scale_data;
- *     ppls_meta_emstep / ppls_meta_ppls; ppls_comm_init and ppls_set_reducer (set them before
- *     ppls_stream_begin); option "dtype";
+ *     ppls_meta_emstep / ppls_meta_ppls (a context streamed with folds fits the multi-population
+ *     model with ppls_meta_emstep_stream / ppls_meta_ppls_stream instead); ppls_comm_init and
+ *     ppls_set_reducer (set them before ppls_stream_begin); option "dtype";
  *   - ppls_xprod_release, ppls_set_data, ppls_generate_synthetic and ppls_stream_begin end the state
  *     (after ppls_xprod_release the context has no data).
  * While a stream is open (between begin and end) the context has no data: every fit and data entry
@@ -433,7 +470,8 @@ int ppls_stream_info(ppls_ctx* ctx, int* state, int64_t* rows_local, int64_t* n_
  * the labelled calls and the calls below return PPLS_E_STATE, as do the unlabelled ppls_stream_rows /
  * _rows_from on a fold stream.  A context streamed with folds is "streamed" (everything that needs
  * rows keeps its refusal) and additionally serves ppls_stream_fold_info, ppls_stream_select,
- * ppls_heldout_sse_fold and ppls_cv_ppls_stream; what ends the streamed state frees the fold matrices. */
+ * ppls_heldout_sse_fold, ppls_cv_ppls_stream and ppls_meta_emstep_stream / ppls_meta_ppls_stream (the
+ * folds as populations); what ends the streamed state frees the fold matrices. */
 
 /* ppls_stream_begin with nfolds >= 2 Chan states (N_k, mean_k, S_k) instead of one; the nfolds fold
  * matrices are allocated up front, contiguously (PPLS_E_NOMEM: the stream is not opened). */

@@ -67,10 +67,34 @@ int ppls_oz_modulus(int l);
 /* Which Gram ran last -- forming S, or ppls_variances' X'X / Y'Y (1 int8 CRT form, 0 fp64 MFMA) -- its
  * moduli, bits and phases (ms[4]). */
 int ppls_gram_info(ppls_ctx* ctx, int* int8_used, int* nmod, int* L, double* ms);
-/* The path the last ppls_meta_ppls took: 0 none yet, 1 the host loop, 2 the device loop on the split
- * sweep (one segmented launch per EM step), 3 the device loop on the panel sweep (one launch per
- * population and step). */
+/* The path the last ppls_meta_ppls / ppls_meta_ppls_stream took: 0 none yet, 1 the host loop, 2 the
+ * device loop on the split sweep (one segmented launch per EM step), 3 the device loop on the panel
+ * sweep (one launch per population and step), 4 the device loop on the cross-products of resident
+ * populations (option "meta_xprod"), 5 the device loop on a fold stream's matrices. */
 int ppls_meta_info(ppls_ctx* ctx, int* path);
+/* The population cross-products of option "meta_xprod" on this context: *npop the matrices held now
+ * (0: none), *formations how often they were formed since the context was created (a fit that finds
+ * them cached adds nothing), *form_ms the wall clock of the last formation (the K Grams and their
+ * all-reduce).  All nullable. */
+int ppls_meta_xprod_info(ppls_ctx* ctx, int* npop, int64_t* formations, double* form_ms);
+/* The statistics pass of a meta EM step alone (ppls_xprod_meta.hip), as ppls_xprod_stats is for the
+ * single-matrix kernel: on a context that holds population matrices -- streamed with folds, or resident
+ * after a "meta_xprod" = 1 call; else PPLS_E_STATE -- the K blocks for the shared loadings W (p), C (q)
+ * and params (K x 5 column-major: B_T, sigX, sigY, sigH, sigT).  stats: K x (p + q + 4), population j
+ * at stats + j (p + q + 4): [X_j'mu_T p | Y_j'mu_U q | Gram 2 x 2 column-major], unpadded. */
+int ppls_xprod_meta_stats(ppls_ctx* ctx, const double* W, const double* C, const double* params, double* stats);
+/* Average ms of that statistics pass (both launches) over reps back-to-back passes, HIP events around
+ * the batch, on the population matrices the context holds (else PPLS_E_STATE); the loadings and scalars
+ * are zeroed (the time does not depend on them).  Ends an ppls_em_begin session. */
+int ppls_xprod_meta_timing(ppls_ctx* ctx, int reps, double* ms);
+/* Whether that pass takes its non-temporal instantiation for K matrices of P x P doubles (1) or the
+ * cached one (0): decided on all K 8 P^2 bytes a step reads, against 200 MiB. */
+int ppls_xprod_meta_nt(int K, int P);
+/* Host only: the mu coefficients {alpha, beta, gamma, delta} the rank-1 and meta sweeps and the pass
+ * above use for one population's scalars params5 = {B_T, sigX, sigY, sigH, sigT} (EMstepC_fast's
+ * formulas, src/loglC.cpp:354-361, evaluated in fp64 exactly as the library stages them), so a test
+ * can hand a reference the very inputs the kernel had. */
+int ppls_rank1_mu_coefficients(const double* params5, double* coef4);
 /* The Gram D'D alone (D = X for xory 0, Y for 1, the joint [X Y] for 2; nsplit 0 = auto; this rank's
  * rows), for tests, benchmarks and the 'o2m' starting values of the Python PPLS / PPLSi /
  * meta_PPLSi: G (p x p, q x q or (p + q) x (p + q) without padding columns, column-major,

@@ -156,6 +156,14 @@ SIGNATURES = {
     "ppls_cv_ppls_stream": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.c_double, ct.c_int, ct.POINTER(PplsTheta),
                                        _dp, ct.POINTER(ct.c_int), _dp]),
     "ppls_stream_fold_get": (ct.c_int, [ct.c_void_p, ct.c_int, _dp, _dp, _i64p]),
+    "ppls_meta_emstep_stream": (ct.c_int, [ct.c_void_p, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "ppls_meta_ppls_stream": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_double, ct.c_int, ct.POINTER(PplsTheta),
+                                         ct.POINTER(PplsMetaFit)]),
+    "ppls_meta_xprod_info": (ct.c_int, [ct.c_void_p, ct.POINTER(ct.c_int), _i64p, _dp]),
+    "ppls_xprod_meta_stats": (ct.c_int, [ct.c_void_p, _dp, _dp, _dp, _dp]),
+    "ppls_rank1_mu_coefficients": (ct.c_int, [_dp, _dp]),
+    "ppls_xprod_meta_nt": (ct.c_int, [ct.c_int, ct.c_int]),
+    "ppls_xprod_meta_timing": (ct.c_int, [ct.c_void_p, ct.c_int, _dp]),
 }
 
 

@@ -487,6 +487,74 @@ class Context:
                                          ct.byref(fit)))
         return Wo, Co, po, lg[: fit.steps + 1].copy()
 
+    def meta_emstep_stream(self, W, C, params):
+        """meta_EMstep on a context streamed with folds (ppls_meta_emstep_stream): the fold labels are
+        the populations, every statistic comes from the fold's cross-products.  params: K x 5.
+        Returns what ``meta_emstep`` returns."""
+        held = self.stream_fold_info()["nr_folds"]
+        W = np.ascontiguousarray(np.ravel(W), dtype=np.float64)
+        C = np.ascontiguousarray(np.ravel(C), dtype=np.float64)
+        pin = np.asfortranarray(np.asarray(params, dtype=np.float64).reshape(-1, 5))
+        npop = pin.shape[0]
+        if held and npop != held:      # (no fold stream: the call itself refuses, before it reads params)
+            raise ValueError(f"{npop} parameter sets for {held} populations")
+        Wo, Co = np.zeros(self.p), np.zeros(self.q)
+        po = np.zeros((npop, 5), order="F")
+        cxt, cyu = np.zeros((self.p, npop), order="F"), np.zeros((self.q, npop), order="F")
+        self._chk(self._L.ppls_meta_emstep_stream(self.h, dptr(W), dptr(C), dptr(pin), dptr(Wo), dptr(Co), dptr(po),
+                                                  dptr(cxt), dptr(cyu)))
+        return Wo, Co, po, cxt, cyu
+
+    def meta_ppls_stream(self, max_steps, atol, init, crit_abs=False):
+        """meta_PPLSi's loop on a context streamed with folds (ppls_meta_ppls_stream), the whole loop
+        on the device from the folds' cross-products.  Returns what ``meta_ppls`` returns."""
+        npop = max(self.stream_fold_info()["nr_folds"], 1)
+        th = Theta(np.reshape(init["W"], (self.p, 1)), np.reshape(init["C"], (self.q, 1)),
+                   float(np.ravel(init["B"])[0]), init["sigE"], init["sigF"], init["sigH"],
+                   float(np.ravel(init["sigT"])[0]))
+        t = th.struct()
+        Wo, Co = np.zeros(self.p), np.zeros(self.q)
+        po = np.zeros((npop, 5), order="F")
+        lg = np.full((max_steps + 1, npop), np.nan, order="F")
+        fit = _lib.PplsMetaFit(dptr(Wo), dptr(Co), dptr(po), dptr(lg), 0)
+        self._chk(self._L.ppls_meta_ppls_stream(self.h, int(max_steps), float(atol), int(bool(crit_abs)), ct.byref(t),
+                                                ct.byref(fit)))
+        return Wo, Co, po, lg[: fit.steps + 1].copy()
+
+    def meta_xprod_info(self):
+        """``dict(npop, formations, form_ms)`` (ppls_meta_xprod_info): the population cross-products
+        option "meta_xprod" keeps on this context, how often they were formed so far, and the wall
+        clock of the last formation."""
+        k, n, ms = ct.c_int(), ct.c_int64(), ct.c_double()
+        self._chk(self._L.ppls_meta_xprod_info(self.h, ct.byref(k), ct.byref(n), ct.byref(ms)))
+        return dict(npop=k.value, formations=n.value, form_ms=ms.value)
+
+    def xprod_meta_timing(self, reps=200):
+        """Average ms of the meta statistics pass over the population matrices the context holds
+        (ppls_xprod_meta_timing: HIP events around ``reps`` back-to-back passes)."""
+        ms = ct.c_double()
+        self._chk(self._L.ppls_xprod_meta_timing(self.h, int(reps), ct.byref(ms)))
+        return ms.value
+
+    def xprod_meta_stats(self, W, C, params):
+        """The statistics pass of one meta EM step alone (ppls_xprod_meta_stats) on a context that
+        holds population matrices (streamed with folds, or resident after a "meta_xprod" = 1 call):
+        ``(SX K x p, SY K x q, G K x 2 x 2)`` for the shared loadings and params (K x 5)."""
+        params = np.asarray(params, dtype=np.float64)
+        K = params.shape[0]
+        W = np.ascontiguousarray(np.ravel(W), dtype=np.float64)
+        C = np.ascontiguousarray(np.ravel(C), dtype=np.float64)
+        if W.shape[0] != self.p or C.shape[0] != self.q or params.shape != (K, 5):
+            raise ValueError("W (p), C (q) and params (K x 5) are needed")
+        held = self.stream_fold_info()["nr_folds"] or self.meta_xprod_info()["npop"]
+        if held and K != held:
+            raise ValueError(f"{K} parameter sets for {held} populations")
+        pin = np.asfortranarray(params)
+        st = np.zeros((K, self.p + self.q + 4))
+        self._chk(self._L.ppls_xprod_meta_stats(self.h, dptr(W), dptr(C), dptr(pin), dptr(st)))
+        return (st[:, :self.p].copy(), st[:, self.p:self.p + self.q].copy(),
+                st[:, self.p + self.q:].reshape(K, 2, 2).copy())
+
     def variances(self, mu, Cdiag, sigE, xory, full=True):
         """variances.PPLS_simult (EM_W_multi.R:830-860) on the resident X (xory 0) or Y (xory 1):
         mu = this rank's rows of Expectations$mu_T / mu_U (n_local x a), Cdiag = diag(Ctt / Cuu).
@@ -823,10 +891,11 @@ class Context:
         return dict(bytes_per_sweep=b.value, variant={4: "split512", 5: "panel"}[v.value], grid=g.value)
 
     def meta_info(self):
-        """The path the last meta_ppls took: "none", "host", "device_split" or "device_panel"."""
+        """The path the last meta_ppls / meta_ppls_stream took: "none", "host", "device_split",
+        "device_panel", "device_xprod" (option meta_xprod) or "device_stream" (a fold stream)."""
         v = ct.c_int()
         self._chk(self._L.ppls_meta_info(self.h, ct.byref(v)))
-        return ("none", "host", "device_split", "device_panel")[v.value]
+        return ("none", "host", "device_split", "device_panel", "device_xprod", "device_stream")[v.value]
 
     def sweep_kernel(self, r):
         """The sweep kernel instantiation an EM iteration with r components launches (text)."""
@@ -1273,6 +1342,41 @@ def _populations(Ipopu, n):
     return levels, counts.astype(np.int64)
 
 
+def population_labels(Ipopu):
+    """``(labels int32, levels)``: every row's population as 0 .. K-1 in R's level order
+    (as.factor(Ipopu), the order of ``_populations``) -- the third element of each chunk triple when
+    the rows of a multi-population fit are streamed with ``stream_data(..., nr_folds=K)``.  Compute it
+    from all labels at once (or pass the chunks' labels through the same ``levels``), so that every
+    chunk uses the same numbering."""
+    Ipopu = np.asarray(Ipopu)
+    if Ipopu.ndim != 1:
+        raise ValueError("Ipopu must be a vector")
+    levels, inv = np.unique(Ipopu, return_inverse=True)
+    return np.ascontiguousarray(inv, dtype=np.int32), levels
+
+
+def rank1_mu_coefficients(params):
+    """``K x 4`` (alpha, beta, gamma, delta) for ``params`` (K x 5: B_T, sigX, sigY, sigH, sigT), as
+    the library stages them for a rank-1 or meta statistics pass (ppls_rank1_mu_coefficients; host
+    only, no GPU)."""
+    P = np.ascontiguousarray(np.asarray(params, dtype=np.float64).reshape(-1, 5))
+    out = np.zeros((P.shape[0], 4))
+    L = _lib.lib()
+    for j in range(P.shape[0]):
+        if L.ppls_rank1_mu_coefficients(dptr(P[j]), dptr(out[j])) != 0:
+            raise ValueError("ppls_rank1_mu_coefficients failed")
+    return out
+
+
+def _meta_streamed(ctx, X, Ipopu):
+    """Whether a meta_* call runs on a fold stream's populations (and may: no Ipopu there)."""
+    if X is not None or ctx is None or not ctx.streamed or not ctx._stream_folds:
+        return False
+    if Ipopu is not None:
+        raise ValueError("Ipopu cannot be given: the populations are the labels the rows were streamed with")
+    return True
+
+
 def _params_list(levels, P):
     return [dict(B_T=float(P[j, 0]), sigX=float(P[j, 1]), sigY=float(P[j, 2]), sigH=float(P[j, 3]),
                  sigT=float(P[j, 4])) for j in range(len(levels))]
@@ -1287,12 +1391,22 @@ def meta_EMstep(X, Y, W, C, Ipopu, params, ctx=None):
     """meta_EMstep (EM_W_multi.R:446-485) on the GPU: one EM step of the multi-population rank-1
     model.  ``params``: one dict per population (B_T, sigX, sigY, sigH, sigT), in level order.
     Returns the reference's list: per population dict(B, sighat, siglathat, Cxt, Cyu), plus
-    ``W.`` and ``C.`` (shared loadings, orth of the sign-aligned sums, :481-482)."""
-    ctx = _ctx_with(X, Y, ctx)
-    levels, counts = _populations(Ipopu, ctx.n_total)
-    if len(params) != len(levels):
-        raise ValueError(f"{len(params)} parameter sets for {len(levels)} populations")
-    Wo, Co, P, cxt, cyu = ctx.meta_emstep(W, C, counts, _params_matrix(params))
+    ``W.`` and ``C.`` (shared loadings, orth of the sign-aligned sums, :481-482).
+
+    ``meta_EMstep(None, None, W, C, None, params, ctx=ctx)`` on a context streamed with
+    ``stream_data(..., nr_folds=K)`` runs on the stream's labels as populations, from their
+    cross-products (ppls_meta_emstep_stream); passing an ``Ipopu`` there raises ``ValueError``."""
+    if _meta_streamed(ctx, X, Ipopu):
+        levels = np.arange(ctx._stream_folds)
+        if len(params) != len(levels):
+            raise ValueError(f"{len(params)} parameter sets for {len(levels)} populations")
+        Wo, Co, P, cxt, cyu = ctx.meta_emstep_stream(W, C, _params_matrix(params))
+    else:
+        ctx = _ctx_with(X, Y, ctx)
+        levels, counts = _populations(Ipopu, ctx.n_total)
+        if len(params) != len(levels):
+            raise ValueError(f"{len(params)} parameter sets for {len(levels)} populations")
+        Wo, Co, P, cxt, cyu = ctx.meta_emstep(W, C, counts, _params_matrix(params))
     out = [dict(B=P[j, 0], sighat=P[j, 1:3].copy(), siglathat=P[j, 3:5].copy(), Cxt=cxt[:, j].copy(),
                 Cyu=cyu[:, j].copy()) for j in range(len(levels))]
     return dict(pops=out, **{"W.": Wo.reshape(-1, 1), "C.": Co.reshape(-1, 1)})
@@ -1305,9 +1419,21 @@ def meta_PPLSi(X, Y, Ipopu, EMsteps=100, atol=1e-4, initialGuess=("equal", "o2m"
     ``log`` is logvalue[1:i+1, ] (rows 2..i+1 of the trace: the per-population log-likelihoods after
     each step; kept 2-D) and, additionally, ``logvalue`` (the full trace incl. the initial row).
     critfunc: None/identity or abs.  constraints: dict with numeric "W" / "C" (the only constraints
-    the reference applies, :543-544)."""
-    ctx = _ctx_with(X, Y, ctx)
-    levels, counts = _populations(Ipopu, ctx.n_total)
+    the reference applies, :543-544).
+
+    ``meta_PPLSi(None, None, None, ..., ctx=ctx)`` on a context streamed with
+    ``stream_data(chunks, nr_folds=K)`` -- chunks of ``(X, Y, labels)`` with the labels of
+    ``population_labels`` -- fits the stream's K populations from their cross-products
+    (ppls_meta_ppls_stream): data larger than device memory, no rows resident; ``params`` are in label
+    order 0 .. K-1.  Passing an ``Ipopu`` there raises ``ValueError``, and ``initialGuess="o2m"`` stays
+    refused on streamed contexts.  One population cannot be streamed this way (a fold stream needs
+    K >= 2): ``PPLSi`` on a plain stream is that fit."""
+    streamed = _meta_streamed(ctx, X, Ipopu)
+    if streamed:
+        levels, counts = np.arange(ctx._stream_folds), None
+    else:
+        ctx = _ctx_with(X, Y, ctx)
+        levels, counts = _populations(Ipopu, ctx.n_total)
     kind = initialGuess if isinstance(initialGuess, str) else initialGuess[0]
     if customGuess is not None:
         kind = "custom"
@@ -1330,7 +1456,10 @@ def meta_PPLSi(X, Y, Ipopu, EMsteps=100, atol=1e-4, initialGuess=("equal", "o2m"
         crit_abs = True
     else:
         raise NotImplementedError("critfunc must be the identity (default) or abs")
-    W, C, P, lg = ctx.meta_ppls(counts, int(EMsteps), float(atol), init, crit_abs)
+    if streamed:
+        W, C, P, lg = ctx.meta_ppls_stream(int(EMsteps), float(atol), init, crit_abs)
+    else:
+        W, C, P, lg = ctx.meta_ppls(counts, int(EMsteps), float(atol), init, crit_abs)
     return dict(W=W, C=C, params=_params_list(levels, P), log=lg[1:], logvalue=lg)
 
 

@@ -29,6 +29,7 @@
 #include "ppls_cvstream.h"
 #include "ppls_stream.h"
 #include "ppls_xprod.h"
+#include "ppls_xprod_meta.h"
 
 struct ppls_ctx {
   int device = 0;
@@ -142,7 +143,15 @@ struct ppls_ctx {
   bool xp_pending_gram = false;   // the last statistics step left the Gram B'M to the next finalize
   int xprod_fuse = 1;       // option "xprod_fuse": the finalize forms the Gram (r <= 8, P <= 6144)
   bool xp_explicit = false; // S was formed by ppls_xprod_prepare: kept until ppls_xprod_release / new data
-  int meta_path = 0;        // the last ppls_meta_ppls: 1 host loop, 2 device split, 3 device panel
+  int meta_path = 0;        // the last ppls_meta_ppls: 1 host loop, 2 device split, 3 device panel,
+                            // 4 resident cross-products (meta_xprod), 5 streamed (ppls_meta_ppls_stream)
+  int meta_xprod = 0;       // option "meta_xprod": resident meta_* take their statistics from the
+                            // populations' cross-products S_j
+  double* mx_S = nullptr;   // the cached S_j: mx_K matrices of P x P, contiguous, all-reduced
+  int mx_K = 0;
+  std::vector<int64_t> mx_local, mx_total;   // the pop_local / pop_total they were formed for
+  int64_t mx_formations = 0;                 // formations of the K matrices on this context
+  double mx_form_ms = 0.0;                   // the last one: wall clock incl. its all-reduce
   int meta_device = 1;      // option "meta_device": meta_PPLSi's loop on the device (1) or per population
                             // from the host (0; also where the split sweep does not apply)
   int vorth = 8;            // option "vorth": the finalize re-orthonormalises its carried Jacobi V every
@@ -1165,7 +1174,16 @@ void fold_free(ppls_ctx* c) {
   c->st_fmean_h.clear();
 }
 
+// The population cross-products of option meta_xprod go with the data they were formed from.
+void meta_xp_free(ppls_ctx* c) {
+  dfree(c->mx_S);
+  c->mx_K = 0;
+  c->mx_local.clear();
+  c->mx_total.clear();
+}
+
 void xprod_free(ppls_ctx* c) {
+  meta_xp_free(c);
   if (c->st_state) {   // S is all a streamed (or streaming) context has: without it there is no data
     stream_release(c);
     c->have_data = false;
@@ -1425,6 +1443,7 @@ void ppls_ctx_destroy(ppls_ctx* c) {
   if (c->st_stream) (void)hipStreamDestroy(c->st_stream);
   dfree(c->xp_S);
   dfree(c->xp_M);
+  dfree(c->mx_S);
   oz_free(c);
   dfree(c->bal_bounds);
   dfree(c->team_bar);
@@ -1526,6 +1545,13 @@ int ppls_set_option(ppls_ctx* c, const char* key, int64_t value) {
     }
   } else if (!strcmp(key, "meta_device")) {
     c->meta_device = value ? 1 : 0;
+  } else if (!strcmp(key, "meta_xprod")) {
+    if (value != 0 && value != 1) return fail(c, PPLS_E_ARG, "meta_xprod must be 0 (sweep the rows) or 1 (population cross-products)");
+    c->meta_xprod = (int)value;
+    if (!c->meta_xprod && c->mx_S) {   // back to the sweeps: the K matrices' bytes go back
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      meta_xp_free(c);
+    }
   } else if (!strcmp(key, "vorth")) {
     if (value < 1 || value > 255) return fail(c, PPLS_E_ARG, "vorth must be in [1, 255]");
     c->vorth = (int)value;
@@ -2565,6 +2591,114 @@ bool meta_device_ok(const ppls_ctx* c, int npop) {
   return c->meta_device && npop >= 1 && npop <= PPLS_META_KMAX;
 }
 
+// What every device loop of meta_PPLSi keeps on the device, whatever its statistics come from: the K
+// statistics blocks, the populations' rows and sums of squares, their scalars, the log-likelihoods.
+struct MetaDev {
+  double* stats = nullptr;
+  double* N = nullptr;
+  double* ssq = nullptr;
+  double* log = nullptr;
+  PplsRank1* st = nullptr;
+  PplsScalars* sc = nullptr;
+  ppls_ctx* c = nullptr;
+  std::vector<hipEvent_t> evs;
+  ~MetaDev() {
+    dfree(stats); dfree(N); dfree(ssq); dfree(log); dfree(st); dfree(sc);
+    if (c) c->sweep_stop = nullptr;
+    for (auto e : evs) (void)hipEventDestroy(e);
+  }
+};
+
+// Allocate and stage a fit that starts every population from t0: N (K), ssq (2K: ssq(X_j), ssq(Y_j)),
+// the shared loadings into W[0], C[0].  The stop flag must be reset before.
+int meta_dev_begin(ppls_ctx* c, MetaDev& d, int K, const double* N, const double* ssq, const Rank1& t0, int max_steps) {
+  int rc;
+  d.c = c;
+  const int64_t pld = c->part_ld, lld = (int64_t)max_steps + 1;
+  if ((rc = dalloc(c, &d.stats, (size_t)K * pld)) || (rc = dalloc(c, &d.N, (size_t)K)) ||
+      (rc = dalloc(c, &d.ssq, (size_t)2 * K)) || (rc = dalloc(c, &d.log, (size_t)K * lld)) ||
+      (rc = dalloc(c, &d.st, (size_t)K)) || (rc = dalloc(c, &d.sc, (size_t)K)))
+    return rc;
+  std::vector<double> hl((size_t)K * lld, NAN);
+  std::vector<PplsRank1> hst((size_t)K, r1_of(t0));
+  std::vector<PplsScalars> hsc((size_t)K);
+  for (int j = 0; j < K; ++j) ppls_rank1_sweep_scalars(&hst[(size_t)j], &hsc[(size_t)j]);
+  std::vector<double> wv((size_t)c->ldx, 0.0), cv((size_t)c->ldy, 0.0);
+  std::copy(t0.w.begin(), t0.w.end(), wv.begin());
+  std::copy(t0.c.begin(), t0.c.end(), cv.begin());
+  HIPCHK(c, hipMemcpyAsync(d.N, N, sizeof(double) * K, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d.ssq, ssq, sizeof(double) * 2 * K, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d.log, hl.data(), sizeof(double) * hl.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d.st, hst.data(), sizeof(PplsRank1) * K, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d.sc, hsc.data(), sizeof(PplsScalars) * K, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->W[0], wv.data(), sizeof(double) * wv.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->C[0], cv.data(), sizeof(double) * cv.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // the host vectors go out of scope
+  return PPLS_OK;
+}
+
+// The loop itself (EM_W_multi.R:551-578): per EM step stats_pass() leaves the K statistics blocks of
+// the current parameters in d.stats (all-reduced where that is needed), then ppls_meta_step_kernel.
+// No host round trip per step: the host enqueues at most LOOKAHEAD steps ahead and stops launching
+// once the step kernel reports the end of the fit (all ranks at the same step).  ssqX, ssqY, Ntot:
+// the whole data's, for logvalue[1, ].
+template <class Pass>
+int meta_dev_loop(ppls_ctx* c, MetaDev& d, int K, int max_steps, double atol, int crit_abs, double ssqX, double ssqY,
+                  double Ntot, Pass&& stats_pass, ppls_meta_fit* out) {
+  const int p = c->p, q = c->q;
+  const int64_t pld = c->part_ld, lld = (int64_t)max_steps + 1;
+  int rc;
+  c->sweep_stop = c->stop_d;
+  PplsMetaStepArgs m;
+  memset(&m, 0, sizeof m);
+  m.stats = d.stats; m.part_ld = pld; m.K = K; m.p = p; m.q = q; m.ldx = c->ldx; m.ldy = c->ldy;
+  m.N = d.N; m.ssq = d.ssq; m.st = d.st; m.sc = d.sc; m.W = c->W[0]; m.C = c->C[0];
+  m.log = d.log; m.log_ld = lld; m.max_steps = max_steps; m.crit_abs = crit_abs; m.atol = atol;
+  m.stop = c->stop_d; m.stop_mirror = c->stop_mirror_dev;
+  m.ssqX = ssqX; m.ssqY = ssqY; m.Ntot = Ntot;
+  constexpr int LOOKAHEAD = 8;
+  for (int step = 0; step <= max_steps; ++step) {
+    if (step >= LOOKAHEAD) {
+      HIPCHK(c, hipEventSynchronize(d.evs[(size_t)(step - LOOKAHEAD) % LOOKAHEAD]));
+      const int ended = __atomic_load_n(c->stop_mirror, __ATOMIC_ACQUIRE);
+      if (ended != 0 && ended <= step - LOOKAHEAD) break;   // the same break step on every rank
+    }
+    if ((rc = stats_pass())) return rc;
+    m.step = step;
+    HIPCHK(c, ppls_launch_meta_step(&m, c->stream));
+    const size_t k = (size_t)step % LOOKAHEAD;
+    if (d.evs.size() <= k) {
+      hipEvent_t e;
+      HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      d.evs.push_back(e);
+    }
+    HIPCHK(c, hipEventRecord(d.evs[k], c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int stop[2] = {0, 0};
+  HIPCHK(c, hipMemcpy(stop, c->stop_d, sizeof stop, hipMemcpyDeviceToHost));
+  if (stop[1] == 2)
+    return fail(c, PPLS_E_NUMERIC, "meta_PPLSi: the log-likelihood increment of EM step %d is NaN", stop[0]);
+  out->steps = stop[0] > 0 ? stop[0] : max_steps;
+  std::vector<double> hl((size_t)K * lld), hw((size_t)c->ldx), hc((size_t)c->ldy);
+  std::vector<PplsRank1> hst((size_t)K);
+  HIPCHK(c, hipMemcpy(hl.data(), d.log, sizeof(double) * hl.size(), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(hw.data(), c->W[0], sizeof(double) * hw.size(), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(hc.data(), c->C[0], sizeof(double) * hc.size(), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(hst.data(), d.st, sizeof(PplsRank1) * K, hipMemcpyDeviceToHost));
+  if (out->log) std::copy(hl.begin(), hl.end(), out->log);
+  std::copy(hw.begin(), hw.begin() + p, out->W);
+  std::copy(hc.begin(), hc.begin() + q, out->C);
+  for (int j = 0; j < K; ++j) {
+    out->params[j] = hst[(size_t)j].B;
+    out->params[K + j] = hst[(size_t)j].sigE;
+    out->params[2 * K + j] = hst[(size_t)j].sigF;
+    out->params[3 * K + j] = hst[(size_t)j].sigH;
+    out->params[4 * K + j] = hst[(size_t)j].sigT;
+  }
+  return PPLS_OK;
+}
+
 // The whole meta_PPLSi loop (EM_W_multi.R:544-578) on the device.  Per EM step the statistics of
 // every population from ONE segmented sweep over X and Y -- the split sweep: workgroups partitioned
 // over the populations in proportion to their rows (each workgroup's rows in one population, using
@@ -2579,7 +2713,6 @@ bool meta_device_ok(const ppls_ctx* c, int npop) {
 int meta_ppls_device(ppls_ctx* c, const std::vector<MetaPop>& pops, const Rank1& t0, int max_steps, double atol,
                      int crit_abs, ppls_meta_fit* out) {
   const int K = (int)pops.size();
-  const int p = c->p, q = c->q;
   int rc;
   PplsSweepArgs a;
   const int plan = sweep_plan(c, 1, &a);
@@ -2632,58 +2765,30 @@ int meta_ppls_device(ppls_ctx* c, const std::vector<MetaPop>& pops, const Rank1&
     c->z_cols = 4;
   }
   if ((rc = ensure_stop(c)) || (rc = reset_stop(c))) return rc;
-  struct Dev {
+  struct Seg {   // the segmented sweep's own device state
     int64_t* bnd = nullptr;
     int64_t* segend = nullptr;
     int* seg = nullptr;
-    double* stats = nullptr;
-    double* N = nullptr;
-    double* ssq = nullptr;
-    double* log = nullptr;
-    PplsRank1* st = nullptr;
-    PplsScalars* sc = nullptr;
-    ppls_ctx* c = nullptr;
-    std::vector<hipEvent_t> evs;
-    ~Dev() {
-      dfree(bnd); dfree(segend); dfree(seg); dfree(stats); dfree(N); dfree(ssq); dfree(log); dfree(st); dfree(sc);
-      if (c) c->sweep_stop = nullptr;
-      for (auto e : evs) (void)hipEventDestroy(e);
-    }
-  } d;
-  d.c = c;
-  const int64_t pld = c->part_ld, lld = (int64_t)max_steps + 1;
-  if ((rc = dalloc(c, &d.bnd, (size_t)G + 1)) || (rc = dalloc(c, &d.seg, (size_t)std::max(G, 1))) ||
-      (rc = dalloc(c, &d.segend, (size_t)K)) ||
-      (rc = dalloc(c, &d.stats, (size_t)K * pld)) || (rc = dalloc(c, &d.N, (size_t)K)) ||
-      (rc = dalloc(c, &d.ssq, (size_t)2 * K)) || (rc = dalloc(c, &d.log, (size_t)K * lld)) ||
-      (rc = dalloc(c, &d.st, (size_t)K)) || (rc = dalloc(c, &d.sc, (size_t)K)))
+    ~Seg() { dfree(bnd); dfree(segend); dfree(seg); }
+  } sg;
+  MetaDev d;   // (destroyed before sg: nothing of sg is read once the loop has synchronised)
+  const int64_t pld = c->part_ld;
+  if ((rc = dalloc(c, &sg.bnd, (size_t)G + 1)) || (rc = dalloc(c, &sg.seg, (size_t)std::max(G, 1))) ||
+      (rc = dalloc(c, &sg.segend, (size_t)K)))
     return rc;
   {
-    std::vector<double> hN((size_t)K), hs((size_t)2 * K), hl((size_t)K * lld, NAN);
-    std::vector<PplsRank1> hst((size_t)K, r1_of(t0));
-    std::vector<PplsScalars> hsc((size_t)K);
+    std::vector<int64_t> se((size_t)K);
+    for (int j = 0; j < K; ++j) se[(size_t)j] = pops[j].row0 + pops[j].nloc;
+    HIPCHK(c, hipMemcpyAsync(sg.bnd, bnd.data(), sizeof(int64_t) * bnd.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sg.seg, seg.data(), sizeof(int) * seg.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sg.segend, se.data(), sizeof(int64_t) * K, hipMemcpyHostToDevice, c->stream));
+    std::vector<double> hN((size_t)K), hs((size_t)2 * K);
     for (int j = 0; j < K; ++j) {
       hN[(size_t)j] = pops[j].N;
       hs[(size_t)2 * j] = pops[j].ssq[0];
       hs[(size_t)2 * j + 1] = pops[j].ssq[1];
-      ppls_rank1_sweep_scalars(&hst[(size_t)j], &hsc[(size_t)j]);
     }
-    std::vector<double> wv((size_t)c->ldx, 0.0), cv((size_t)c->ldy, 0.0);
-    std::copy(t0.w.begin(), t0.w.end(), wv.begin());
-    std::copy(t0.c.begin(), t0.c.end(), cv.begin());
-    HIPCHK(c, hipMemcpyAsync(d.bnd, bnd.data(), sizeof(int64_t) * bnd.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d.seg, seg.data(), sizeof(int) * seg.size(), hipMemcpyHostToDevice, c->stream));
-    std::vector<int64_t> se((size_t)K);
-    for (int j = 0; j < K; ++j) se[(size_t)j] = pops[j].row0 + pops[j].nloc;
-    HIPCHK(c, hipMemcpyAsync(d.segend, se.data(), sizeof(int64_t) * K, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d.N, hN.data(), sizeof(double) * K, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d.ssq, hs.data(), sizeof(double) * 2 * K, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d.log, hl.data(), sizeof(double) * hl.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d.st, hst.data(), sizeof(PplsRank1) * K, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d.sc, hsc.data(), sizeof(PplsScalars) * K, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->W[0], wv.data(), sizeof(double) * wv.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->C[0], cv.data(), sizeof(double) * cv.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // the host vectors go out of scope
+    if ((rc = meta_dev_begin(c, d, K, hN.data(), hs.data(), t0, max_steps))) return rc;   // (synchronises)
   }
   a.X = c->X;
   a.Y = c->Y;
@@ -2696,27 +2801,20 @@ int meta_ppls_device(ppls_ctx* c, const std::vector<MetaPop>& pops, const Rank1&
   a.mu = nullptr;
   a.write_mu = 0;
   a.grid = G;
-  a.row_bounds = d.bnd;
-  a.wg_seg = d.seg;
+  a.row_bounds = sg.bnd;
+  a.wg_seg = sg.seg;
   a.nt = (c->nt_loads > 0 || (c->nt_loads < 0 && 8.0 * c->n_local * (double)(c->ldx + c->ldy) > 256.0 * (1 << 20))) ? 1 : 0;
   a.stop = c->stop_d;
   a.trace = nullptr;
   c->sweep_stop = c->stop_d;
-  PplsMetaStepArgs m;
-  memset(&m, 0, sizeof m);
-  m.stats = d.stats; m.part_ld = pld; m.K = K; m.p = p; m.q = q; m.ldx = c->ldx; m.ldy = c->ldy;
-  m.N = d.N; m.ssq = d.ssq; m.st = d.st; m.sc = d.sc; m.W = c->W[0]; m.C = c->C[0];
-  m.log = d.log; m.log_ld = lld; m.max_steps = max_steps; m.crit_abs = crit_abs; m.atol = atol;
-  m.stop = c->stop_d; m.stop_mirror = c->stop_mirror_dev;
-  m.ssqX = c->ssq_host[0]; m.ssqY = c->ssq_host[1]; m.Ntot = (double)c->n_total;
   double* tmp = c->part + (size_t)c->part_groups * pld;
   // one segmented sweep of the current parameters -> d.stats (K blocks, all-reduced)
   if (panel) {   // the dots use each row's population scalars; the accumulation's chunks are bnd
     a.row_bounds = nullptr;
     a.wg_seg = nullptr;
-    a.seg_ends = d.segend;
+    a.seg_ends = sg.segend;
     a.nseg = K;
-    a.chunk_bounds = d.bnd;
+    a.chunk_bounds = sg.bnd;
   }
   auto seg_sweep = [&]() -> int {
     if (G > 0) {
@@ -2733,46 +2831,150 @@ int meta_ppls_device(ppls_ctx* c, const std::vector<MetaPop>& pops, const Rank1&
     }
     return allreduce(c, d.stats, (size_t)K * pld);
   };
-  constexpr int LOOKAHEAD = 8;
-  for (int step = 0; step <= max_steps; ++step) {
-    if (step >= LOOKAHEAD) {
-      HIPCHK(c, hipEventSynchronize(d.evs[(size_t)(step - LOOKAHEAD) % LOOKAHEAD]));
-      const int ended = __atomic_load_n(c->stop_mirror, __ATOMIC_ACQUIRE);
-      if (ended != 0 && ended <= step - LOOKAHEAD) break;   // the same break step on every rank
-    }
-    if ((rc = seg_sweep())) return rc;
-    m.step = step;
-    HIPCHK(c, ppls_launch_meta_step(&m, c->stream));
-    const size_t k = (size_t)step % LOOKAHEAD;
-    if (d.evs.size() <= k) {
-      hipEvent_t e;
-      HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      d.evs.push_back(e);
-    }
-    HIPCHK(c, hipEventRecord(d.evs[k], c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  int stop[2] = {0, 0};
-  HIPCHK(c, hipMemcpy(stop, c->stop_d, sizeof stop, hipMemcpyDeviceToHost));
-  if (stop[1] == 2)
-    return fail(c, PPLS_E_NUMERIC, "meta_PPLSi: the log-likelihood increment of EM step %d is NaN", stop[0]);
-  out->steps = stop[0] > 0 ? stop[0] : max_steps;
-  std::vector<double> hl((size_t)K * lld), hw((size_t)c->ldx), hc((size_t)c->ldy);
-  std::vector<PplsRank1> hst((size_t)K);
-  HIPCHK(c, hipMemcpy(hl.data(), d.log, sizeof(double) * hl.size(), hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(hw.data(), c->W[0], sizeof(double) * hw.size(), hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(hc.data(), c->C[0], sizeof(double) * hc.size(), hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(hst.data(), d.st, sizeof(PplsRank1) * K, hipMemcpyDeviceToHost));
-  if (out->log) std::copy(hl.begin(), hl.end(), out->log);
-  std::copy(hw.begin(), hw.begin() + p, out->W);
-  std::copy(hc.begin(), hc.begin() + q, out->C);
+  return meta_dev_loop(c, d, K, max_steps, atol, crit_abs, c->ssq_host[0], c->ssq_host[1], (double)c->n_total, seg_sweep,
+                       out);
+}
+
+// ---- meta_* from per-population cross-products (ppls_xprod_meta.hip) -----------------
+
+// The K statistics blocks of the loadings in W[0], C[0] and the scalars sc from the K matrices S:
+// two launches, no collective (every rank holds the same S_j).  M: K x 2 P doubles of scratch.
+int meta_xprod_pass(ppls_ctx* c, const double* S, int K, const PplsScalars* sc, double* stats, double* M,
+                    const int* stop) {
+  const int P = c->ldx + c->ldy;
+  const int rw = ppls_xprod_meta_rows(K, P, c->xprod_rw, c->num_cus);
+  HIPCHK(c, ppls_launch_xprod_meta(S, K, c->ldx, c->ldy, rw, c->W[0], c->C[0], sc, stats, c->part_ld, M, stop, c->stream));
+  return PPLS_OK;
+}
+
+struct MetaXpScratch {
+  double* M = nullptr;
+  double* stats = nullptr;
+  PplsScalars* sc = nullptr;
+  ~MetaXpScratch() { dfree(M); dfree(stats); dfree(sc); }
+};
+
+// meta_ppls_device's loop with the segmented sweep replaced by the pass over the K matrices.
+// N (K), ssq (2K) and ssqX, ssqY, Ntot as for meta_dev_loop; path: what ppls_meta_info reports.
+int meta_ppls_xprod(ppls_ctx* c, const double* S, int K, const double* N, const double* ssq, double ssqX, double ssqY,
+                    double Ntot, const Rank1& t0, int max_steps, double atol, int crit_abs, int path, ppls_meta_fit* out) {
+  if (K < 1 || K > PPLS_META_KMAX)
+    return fail(c, PPLS_E_ARG, "meta_PPLSi from cross-products: %d populations, at most %d", K, PPLS_META_KMAX);
+  int rc;
+  c->meta_path = path;
+  if ((rc = ensure_stop(c)) || (rc = reset_stop(c))) return rc;
+  MetaXpScratch x;   // (freed after d, whose loop has synchronised by then)
+  MetaDev d;
+  if ((rc = dalloc(c, &x.M, (size_t)K * 2 * (c->ldx + c->ldy)))) return rc;
+  if ((rc = meta_dev_begin(c, d, K, N, ssq, t0, max_steps))) return rc;
+  auto pass = [&]() -> int { return meta_xprod_pass(c, S, K, d.sc, d.stats, x.M, c->stop_d); };
+  return meta_dev_loop(c, d, K, max_steps, atol, crit_abs, ssqX, ssqY, Ntot, pass, out);
+}
+
+// meta_sweep_all from the K matrices: every population's SX, SY, G for its scalars pops[j].t and the
+// shared loadings w, cv.
+int meta_xprod_all(ppls_ctx* c, const double* S, std::vector<MetaPop>& pops, const std::vector<double>& w,
+                   const std::vector<double>& cv) {
+  const int K = (int)pops.size(), P = c->ldx + c->ldy;
+  const int64_t pld = c->part_ld;
+  int rc;
+  MetaXpScratch x;
+  if ((rc = dalloc(c, &x.M, (size_t)K * 2 * P)) || (rc = dalloc(c, &x.stats, (size_t)K * pld)) ||
+      (rc = dalloc(c, &x.sc, (size_t)K)))
+    return rc;
+  std::vector<PplsScalars> hsc((size_t)K);
   for (int j = 0; j < K; ++j) {
-    out->params[j] = hst[(size_t)j].B;
-    out->params[K + j] = hst[(size_t)j].sigE;
-    out->params[2 * K + j] = hst[(size_t)j].sigF;
-    out->params[3 * K + j] = hst[(size_t)j].sigH;
-    out->params[4 * K + j] = hst[(size_t)j].sigT;
+    pops[j].t.w = w;
+    pops[j].t.c = cv;
+    const PplsRank1 r1 = r1_of(pops[j].t);
+    ppls_rank1_sweep_scalars(&r1, &hsc[(size_t)j]);
   }
+  std::vector<double> wv((size_t)c->ldx, 0.0), cvv((size_t)c->ldy, 0.0);
+  std::copy(w.begin(), w.end(), wv.begin());
+  std::copy(cv.begin(), cv.end(), cvv.begin());
+  HIPCHK(c, hipMemcpyAsync(c->W[0], wv.data(), sizeof(double) * wv.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->C[0], cvv.data(), sizeof(double) * cvv.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(x.sc, hsc.data(), sizeof(PplsScalars) * K, hipMemcpyHostToDevice, c->stream));
+  if ((rc = meta_xprod_pass(c, S, K, x.sc, x.stats, x.M, nullptr))) return rc;
+  std::vector<double> st((size_t)K * pld);
+  HIPCHK(c, hipMemcpyAsync(st.data(), x.stats, sizeof(double) * st.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int j = 0; j < K; ++j) {
+    const double* b = st.data() + (size_t)j * pld;
+    pops[j].SX.assign(b, b + c->p);
+    pops[j].SY.assign(b + c->ldx, b + c->ldx + c->q);
+    for (int e = 0; e < 4; ++e) pops[j].G[e] = b[(size_t)c->ldx + c->ldy + e];
+  }
+  return PPLS_OK;
+}
+
+// Option meta_xprod on resident rows: S_j = [X_j Y_j]'[X_j Y_j] of every population's contiguous
+// local row block on the fp64 MFMA Gram (either storage type; gram_int8 does not apply), then one
+// all-reduce of all K matrices (a rank without rows of a population contributes zeros).  Kept with the
+// pop_local / pop_total they were formed for until the data change (xprod_free), other populations
+// are passed or the option goes to 0: a second fit forms nothing.
+int meta_xp_ensure(ppls_ctx* c, const std::vector<MetaPop>& pops, const int64_t* pop_local, const int64_t* pop_total) {
+  const int K = (int)pops.size(), P = c->ldx + c->ldy;
+  const size_t PP = (size_t)P * P;
+  if (c->mx_S && c->mx_K == K && std::equal(pop_local, pop_local + K, c->mx_local.begin()) &&
+      std::equal(pop_total, pop_total + K, c->mx_total.begin()))
+    return PPLS_OK;
+  int rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  meta_xp_free(c);
+  const auto t0 = std::chrono::steady_clock::now();
+  const size_t es = c->dtype ? 4 : 8;
+  auto shape = [&](int j) {
+    GramShape g = gram_shape(c, true, 0);
+    g.X = (const char*)c->X + (size_t)pops[j].row0 * c->ldx * es;
+    g.Y = (const char*)c->Y + (size_t)pops[j].row0 * c->ldy * es;
+    return g;
+  };
+  // the K matrices and the largest population's Gram partials; when sharded the ranks agree that all
+  // of them were allocated before anyone enters the all-reduce of the matrices
+  size_t part_len = 0;
+  for (int j = 0; j < K; ++j)
+    if (pops[j].nloc > 0)
+      part_len = std::max(part_len, (size_t)ppls_gram_part_doubles(P, gram_nsplit(c, shape(j), pops[j].nloc, 0)));
+  double* part = nullptr;
+  int rc_alloc = dalloc(c, &c->mx_S, (size_t)K * PP);
+  if (!rc_alloc && part_len) rc_alloc = dalloc(c, &part, part_len);
+  if (c->nranks > 1 || c->reducer) {
+    const double f = rc_alloc ? 1.0 : 0.0;
+    double tot = 0.0;
+    hipError_t e = hipMemcpyAsync(c->flag, &f, sizeof f, hipMemcpyHostToDevice, c->stream);
+    rc = e == hipSuccess ? allreduce(c, c->flag, 1) : fail(c, PPLS_E_HIP, "meta_xprod: %s", hipGetErrorString(e));
+    if (!rc) {
+      e = hipMemcpyAsync(&tot, c->flag, sizeof tot, hipMemcpyDeviceToHost, c->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+      if (e != hipSuccess) rc = fail(c, PPLS_E_HIP, "meta_xprod: %s", hipGetErrorString(e));
+    }
+    if (!rc && tot > 0.0)
+      rc = fail(c, PPLS_E_NOMEM, "meta_xprod: %d rank(s) could not allocate the %d population cross-products (%.3g GB)",
+                (int)tot, K, 8.0 * K * (double)PP / 1e9);
+    if (rc) { dfree(c->mx_S); dfree(part); return rc; }
+  } else if (rc_alloc) {
+    dfree(c->mx_S);
+    dfree(part);
+    return rc_alloc;
+  }
+  rc = PPLS_OK;
+  for (int j = 0; j < K && !rc; ++j) {
+    if (pops[j].nloc > 0) {
+      rc = gram_run(c, shape(j), pops[j].nloc, 0, c->mx_S + (size_t)j * PP, nullptr, part);
+    } else if (hipMemsetAsync(c->mx_S + (size_t)j * PP, 0, sizeof(double) * PP, c->stream) != hipSuccess) {
+      rc = fail(c, PPLS_E_HIP, "meta_xprod: clearing an empty population's cross-products failed");
+    }
+  }
+  dfree(part);
+  if (!rc) rc = allreduce(c, c->mx_S, (size_t)K * PP);
+  if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, PPLS_E_HIP, "meta_xprod: the formation failed");
+  if (rc) { dfree(c->mx_S); return rc; }
+  c->mx_K = K;
+  c->mx_local.assign(pop_local, pop_local + K);
+  c->mx_total.assign(pop_total, pop_total + K);
+  c->mx_form_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  ++c->mx_formations;
   return PPLS_OK;
 }
 
@@ -2801,7 +3003,11 @@ int ppls_meta_emstep(ppls_ctx* c, int npop, const int64_t* pop_local, const int6
     t.sigH = params_in[3 * npop + j];
     t.sigT = params_in[4 * npop + j];
   }
-  if ((rc = meta_sweep_all(c, pops, w, cv))) return rc;
+  if (c->meta_xprod) {   // the statistics from the populations' cross-products (formed once, kept)
+    if ((rc = meta_xp_ensure(c, pops, pop_local, pop_total)) || (rc = meta_xprod_all(c, c->mx_S, pops, w, cv))) return rc;
+  } else if ((rc = meta_sweep_all(c, pops, w, cv))) {
+    return rc;
+  }
   std::vector<double> cx, cy;
   meta_mstep(pops, c->p, c->q, w, cv, Cxt ? &cx : nullptr, Cyu ? &cy : nullptr);
   std::copy(w.begin(), w.end(), W_out);
@@ -2841,6 +3047,17 @@ int ppls_meta_ppls(ppls_ctx* c, int npop, const int64_t* pop_local, const int64_
   const size_t ld = (size_t)max_steps + 1;
   if (out->log)
     for (size_t e = 0; e < ld * npop; ++e) out->log[e] = NAN;
+  if (c->meta_xprod) {   // every step reads the K cross-product matrices (8 K P^2 bytes), not the rows
+    if ((rc = meta_xp_ensure(c, pops, pop_local, pop_total))) return rc;
+    std::vector<double> hN((size_t)npop), hs((size_t)2 * npop);
+    for (int j = 0; j < npop; ++j) {
+      hN[(size_t)j] = pops[j].N;
+      hs[(size_t)2 * j] = pops[j].ssq[0];   // meta_setup's, from the rows
+      hs[(size_t)2 * j + 1] = pops[j].ssq[1];
+    }
+    return meta_ppls_xprod(c, c->mx_S, npop, hN.data(), hs.data(), c->ssq_host[0], c->ssq_host[1], (double)c->n_total, t0,
+                           max_steps, atol, crit_abs, 4, out);
+  }
   if (meta_device_ok(c, npop)) return meta_ppls_device(c, pops, t0, max_steps, atol, crit_abs, out);
   c->meta_path = 1;
   // logvalue[1, ] = rep(logl_W(X, Y, Wnw, Cnw, Bnw, ...), K) (:544): one full-data sweep
@@ -4993,6 +5210,209 @@ int ppls_stream_fold_get(ppls_ctx* c, int fold, double* S, double* mean, int64_t
   if (S) HIPCHK(c, hipMemcpy(S, c->st_fS + (size_t)fold * P * P, sizeof(double) * P * P, hipMemcpyDeviceToHost));
   if (mean) memcpy(mean, c->st_fmean_h.data() + (size_t)fold * P, sizeof(double) * P);
   if (n) *n = c->st_fN[(size_t)fold];
+  return PPLS_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The populations of a context streamed with folds: N_j the fold's rows, ssq(X_j), ssq(Y_j) the traces
+// of S_j's diagonal blocks in column order; s2 = the whole data's ||X||^2, ||Y||^2 as fold_select(-1)
+// forms them (the diagonals added in fold order, then the columns), whatever is selected now.
+int stream_pops(ppls_ctx* c, std::vector<MetaPop>& pops, double s2[2]) {
+  const int K = c->st_nfolds, p = c->p, q = c->q, ldx = c->ldx, P = c->ldx + c->ldy;
+  pops.assign((size_t)K, MetaPop());
+  std::vector<double> diag((size_t)P), dsum((size_t)P, 0.0);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int k = 0; k < K; ++k) {
+    HIPCHK(c, hipMemcpy2D(diag.data(), sizeof(double), c->st_fS + (size_t)k * P * P, sizeof(double) * ((size_t)P + 1),
+                          sizeof(double), (size_t)P, hipMemcpyDeviceToHost));
+    MetaPop& pp = pops[(size_t)k];
+    pp.N = (double)c->st_fN[(size_t)k];
+    for (int j = 0; j < p; ++j) pp.ssq[0] += diag[(size_t)j];
+    for (int j = 0; j < q; ++j) pp.ssq[1] += diag[(size_t)ldx + j];
+    for (int j = 0; j < P; ++j) dsum[(size_t)j] += diag[(size_t)j];
+  }
+  s2[0] = s2[1] = 0.0;
+  for (int j = 0; j < p; ++j) s2[0] += dsum[(size_t)j];
+  for (int j = 0; j < q; ++j) s2[1] += dsum[(size_t)ldx + j];
+  return PPLS_OK;
+}
+
+int meta_stream_check(ppls_ctx* c) {
+  int rc;
+  if ((rc = fold_state_check(c))) return rc;
+  if (c->em_active)
+    return fail(c, PPLS_E_STATE, "an ppls_em_begin session is active on the selected cross-products: finish it before a meta fit");
+  return PPLS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ppls_meta_emstep_stream(ppls_ctx* c, const double* W, const double* C, const double* params_in, double* W_out,
+                            double* C_out, double* params_out, double* Cxt, double* Cyu) {
+  if (!c) return PPLS_E_ARG;
+  int rc;
+  if ((rc = meta_stream_check(c))) return rc;
+  if (!W || !C || !params_in || !W_out || !C_out || !params_out) return fail(c, PPLS_E_ARG, "NULL argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = ensure_r(c, 1, 1))) return rc;
+  std::vector<MetaPop> pops;
+  double s2[2];
+  if ((rc = stream_pops(c, pops, s2))) return rc;
+  const int npop = (int)pops.size();
+  std::vector<double> w(W, W + c->p), cv(C, C + c->q);
+  for (int j = 0; j < npop; ++j) {
+    Rank1& t = pops[j].t;
+    t.B = params_in[j];
+    t.sigE = params_in[npop + j];
+    t.sigF = params_in[2 * npop + j];
+    t.sigH = params_in[3 * npop + j];
+    t.sigT = params_in[4 * npop + j];
+  }
+  if ((rc = meta_xprod_all(c, c->st_fS, pops, w, cv))) return rc;
+  std::vector<double> cx, cy;
+  meta_mstep(pops, c->p, c->q, w, cv, Cxt ? &cx : nullptr, Cyu ? &cy : nullptr);
+  std::copy(w.begin(), w.end(), W_out);
+  std::copy(cv.begin(), cv.end(), C_out);
+  meta_params_out(pops, params_out);
+  if (Cxt) std::copy(cx.begin(), cx.end(), Cxt);
+  if (Cyu) std::copy(cy.begin(), cy.end(), Cyu);
+  return PPLS_OK;
+}
+
+int ppls_meta_ppls_stream(ppls_ctx* c, int max_steps, double atol, int crit_abs, const ppls_theta* init,
+                          ppls_meta_fit* out) {
+  if (!c) return PPLS_E_ARG;
+  int rc;
+  if ((rc = meta_stream_check(c))) return rc;
+  if (!init || !init->W || !init->C || !init->B || !init->sigT || !out || !out->W || !out->C || !out->params)
+    return fail(c, PPLS_E_ARG, "NULL argument");
+  if (max_steps < 1) return fail(c, PPLS_E_ARG, "EMsteps must be >= 1");
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<MetaPop> pops;
+  double s2[2];
+  if ((rc = stream_pops(c, pops, s2))) return rc;
+  for (int m = 0; m < 2; ++m)   // check_fit_data's refusal, on all the streamed rows whatever is selected
+    if (!(s2[m] > 0.0))
+      return fail(c, PPLS_E_ARG,
+                  "%c is all zero (sum of squares over all ranks = 0): the PPLS model is degenerate and the "
+                  "reference's fit stops on the NA log-likelihood increment it produces (EM_W_multi.R:173,792)",
+                  m ? 'Y' : 'X');
+  if ((rc = ensure_r(c, 1, max_steps))) return rc;
+  const int K = (int)pops.size();
+  Rank1 t0;
+  t0.w.assign(init->W, init->W + c->p);
+  t0.c.assign(init->C, init->C + c->q);
+  t0.B = init->B[0];
+  t0.sigE = init->sigE;
+  t0.sigF = init->sigF;
+  t0.sigH = init->sigH;
+  t0.sigT = init->sigT[0];
+  const size_t ld = (size_t)max_steps + 1;
+  if (out->log)
+    for (size_t e = 0; e < ld * K; ++e) out->log[e] = NAN;
+  std::vector<double> hN((size_t)K), hs((size_t)2 * K);
+  double Ntot = 0.0;
+  for (int j = 0; j < K; ++j) {
+    hN[(size_t)j] = pops[j].N;
+    hs[(size_t)2 * j] = pops[j].ssq[0];
+    hs[(size_t)2 * j + 1] = pops[j].ssq[1];
+    Ntot += pops[j].N;
+  }
+  return meta_ppls_xprod(c, c->st_fS, K, hN.data(), hs.data(), s2[0], s2[1], Ntot, t0, max_steps, atol, crit_abs, 5, out);
+}
+
+int ppls_meta_xprod_info(ppls_ctx* c, int* npop, int64_t* formations, double* form_ms) {
+  if (!c) return PPLS_E_ARG;
+  if (npop) *npop = c->mx_S ? c->mx_K : 0;
+  if (formations) *formations = c->mx_formations;
+  if (form_ms) *form_ms = c->mx_form_ms;
+  return PPLS_OK;
+}
+
+int ppls_xprod_meta_timing(ppls_ctx* c, int reps, double* ms) {
+  if (!c || reps < 1 || !ms) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  const bool folds = c->st_state == 2 && c->st_nfolds > 0;
+  if (!folds && !(c->st_state == 0 && c->mx_S))
+    return fail(c, PPLS_E_STATE, "the context holds no population cross-products");
+  const double* S = folds ? c->st_fS : c->mx_S;
+  const int K = folds ? c->st_nfolds : c->mx_K, P = c->ldx + c->ldy;
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = ensure_r(c, 1, 1))) return rc;
+  MetaXpScratch x;
+  if ((rc = dalloc(c, &x.M, (size_t)K * 2 * P)) || (rc = dalloc(c, &x.stats, (size_t)K * c->part_ld)) ||
+      (rc = dalloc(c, &x.sc, (size_t)K)))
+    return rc;
+  HIPCHK(c, hipMemsetAsync(x.sc, 0, sizeof(PplsScalars) * K, c->stream));   // (the time does not depend on the values)
+  HIPCHK(c, hipMemsetAsync(c->W[0], 0, sizeof(double) * c->ldx, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->C[0], 0, sizeof(double) * c->ldy, c->stream));
+  if ((rc = meta_xprod_pass(c, S, K, x.sc, x.stats, x.M, nullptr))) return rc;   // warm-up
+  hipEvent_t e0, e1;
+  HIPCHK(c, hipEventCreate(&e0));
+  HIPCHK(c, hipEventCreate(&e1));
+  hipError_t e = hipEventRecord(e0, c->stream);
+  for (int i = 0; e == hipSuccess && i < reps; ++i)
+    if (meta_xprod_pass(c, S, K, x.sc, x.stats, x.M, nullptr)) e = hipErrorUnknown;
+  if (e == hipSuccess) e = hipEventRecord(e1, c->stream);
+  if (e == hipSuccess) e = hipEventSynchronize(e1);
+  float t = 0.f;
+  if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  HIPCHK(c, e);
+  *ms = (double)t / reps;
+  return PPLS_OK;
+}
+
+int ppls_rank1_mu_coefficients(const double* params5, double* coef4) {
+  if (!params5 || !coef4) return PPLS_E_ARG;
+  const PplsRank1 t{params5[0], params5[1], params5[2], params5[3], params5[4]};
+  PplsScalars s;
+  ppls_rank1_sweep_scalars(&t, &s);
+  coef4[0] = s.alpha[0];
+  coef4[1] = s.beta[0];
+  coef4[2] = s.gamma[0];
+  coef4[3] = s.delta[0];
+  return PPLS_OK;
+}
+
+int ppls_xprod_meta_stats(ppls_ctx* c, const double* W, const double* C, const double* params, double* stats) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  if (!W || !C || !params || !stats) return fail(c, PPLS_E_ARG, "NULL argument");
+  const bool folds = c->st_state == 2 && c->st_nfolds > 0;
+  if (!folds && !(c->st_state == 0 && c->mx_S))
+    return fail(c, PPLS_E_STATE, "the context holds no population cross-products: stream the rows with "
+                                 "ppls_stream_begin_folds, or make a meta_xprod = 1 call");
+  const double* S = folds ? c->st_fS : c->mx_S;
+  const int K = folds ? c->st_nfolds : c->mx_K;
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = ensure_r(c, 1, 1))) return rc;
+  std::vector<MetaPop> pops((size_t)K);
+  for (int j = 0; j < K; ++j) {
+    Rank1& t = pops[(size_t)j].t;
+    t.B = params[j];
+    t.sigE = params[K + j];
+    t.sigF = params[2 * K + j];
+    t.sigH = params[3 * K + j];
+    t.sigT = params[4 * K + j];
+  }
+  const std::vector<double> w(W, W + c->p), cv(C, C + c->q);
+  if ((rc = meta_xprod_all(c, S, pops, w, cv))) return rc;
+  const size_t ld = (size_t)c->p + c->q + 4;
+  for (int j = 0; j < K; ++j) {
+    double* o = stats + (size_t)j * ld;
+    std::copy(pops[(size_t)j].SX.begin(), pops[(size_t)j].SX.end(), o);
+    std::copy(pops[(size_t)j].SY.begin(), pops[(size_t)j].SY.end(), o + c->p);
+    for (int e = 0; e < 4; ++e) o[(size_t)c->p + c->q + e] = pops[(size_t)j].G[e];
+  }
   return PPLS_OK;
 }
 
