@@ -208,7 +208,7 @@ struct ppls_ctx {
   int st_next = 0;           // the buffer the next chunk goes to
   double* st_cm = nullptr;   // column-major upload scratch (rows x max(p, q))
   int64_t st_cm_len = 0;
-  double* st_vec = nullptr;  // joint-layout vectors of P: chunk sums, chunk mean, delta, mean, ones; then P + 2 for reductions
+  double* st_vec = nullptr;  // joint-layout vectors of P: chunk sums, chunk mean, delta, mean, ones; then a fold stream's st_nfolds weights
   double* st_part = nullptr; // the chunk Gram's split partials
   int64_t st_part_len = 0;
   double* st_colpart = nullptr;   // the column sums' row-block partials
@@ -465,6 +465,22 @@ int allreduce(ppls_ctx* c, double* buf, size_t count) {
   }
   if (!c->comm) return PPLS_OK;   // a 1-rank communicator still takes the RCCL path
   RCCLCHK(c, ncclAllReduce(buf, buf, count, ncclDouble, ncclSum, c->comm, c->stream));
+  return PPLS_OK;
+}
+
+// Whether other ranks take part in this context's calls.
+bool collective(const ppls_ctx* c) { return c->nranks > 1 || c->reducer; }
+
+// The agreement before a large collective: vals[0..n) (n <= 8, the length of c->flag) summed over
+// the ranks, in place and waited for.  A rank puts 1 where a step of its own failed, and nobody
+// enters the collective that follows alone.  Nothing happens without other ranks.
+int agree(ppls_ctx* c, double* vals, int n) {
+  if (!collective(c)) return PPLS_OK;
+  HIPCHK(c, hipMemcpyAsync(c->flag, vals, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  const int rc = allreduce(c, c->flag, (size_t)n);
+  if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(vals, c->flag, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return PPLS_OK;
 }
 
@@ -1019,23 +1035,18 @@ int xprod_setup(ppls_ctx* c) {
     rc_alloc = dalloc(c, &part, (size_t)ppls_gram_part_doubles(P, gram_nsplit(c, g, c->n_local, 0)));
     if (!rc_alloc) rc_alloc = gram_queue(c, g, c->n_local, 0, &q);
   }
-  if (c->nranks > 1 || c->reducer) {
-    const double f = rc_alloc ? 1.0 : 0.0;
-    double tot = 0.0;
-    HIPCHK(c, hipMemcpyAsync(c->flag, &f, sizeof f, hipMemcpyHostToDevice, c->stream));
-    if ((rc = allreduce(c, c->flag, 1))) { dfree(c->xp_S); dfree(part); return rc; }
-    HIPCHK(c, hipMemcpyAsync(&tot, c->flag, sizeof tot, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (tot > 0.0) {
-      dfree(c->xp_S);
-      dfree(part);
-      return fail(c, PPLS_E_NOMEM, "cross-products S: %d rank(s) could not allocate %.3g GB of S and Gram partials",
-                  (int)tot, xprod_bytes(c) / 1e9);
-    }
-  } else if (rc_alloc) {
+  double tot = rc_alloc ? 1.0 : 0.0;
+  if (collective(c)) {
+    if (!(rc = agree(c, &tot, 1)) && tot > 0.0)
+      rc = fail(c, PPLS_E_NOMEM, "cross-products S: %d rank(s) could not allocate %.3g GB of S and Gram partials",
+                (int)tot, xprod_bytes(c) / 1e9);
+  } else {
+    rc = rc_alloc;
+  }
+  if (rc) {
     dfree(c->xp_S);
     dfree(part);
-    return rc_alloc;
+    return rc;
   }
   c->xp_setup_ms = 0.0;
   if (c->n_local > 0) {
@@ -1051,7 +1062,7 @@ int xprod_setup(ppls_ctx* c) {
   const auto ta = std::chrono::steady_clock::now();
   if ((rc = allreduce(c, c->xp_S, PP))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->xp_setup_ar_ms = c->nranks > 1 || c->reducer ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count() : 0.0;
+  c->xp_setup_ar_ms = collective(c) ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count() : 0.0;
   c->xp_setup_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   c->xp_ready = true;
   return PPLS_OK;
@@ -2093,6 +2104,40 @@ struct Rank1 {
 
 PplsRank1 r1_of(const Rank1& t) { return PplsRank1{t.B, t.sigE, t.sigF, t.sigH, t.sigT}; }
 
+// The meta calls' params (5 x K: B, sigE, sigF, sigH, sigT, population j at [. K + j]) to the scalars
+// of population j (no loadings), and back from a Rank1 or a PplsRank1.
+Rank1 rank1_from_params(const double* params, int K, int j) {
+  Rank1 t;
+  t.B = params[j];
+  t.sigE = params[K + j];
+  t.sigF = params[2 * K + j];
+  t.sigH = params[3 * K + j];
+  t.sigT = params[4 * K + j];
+  return t;
+}
+
+template <class R>
+void rank1_to_params(const R& t, double* params, int K, int j) {
+  params[j] = t.B;
+  params[K + j] = t.sigE;
+  params[2 * K + j] = t.sigF;
+  params[3 * K + j] = t.sigH;
+  params[4 * K + j] = t.sigT;
+}
+
+// A one-component start (the first component of init) with its loadings.
+Rank1 rank1_from_init(const ppls_theta* init, int p, int q) {
+  Rank1 t;
+  t.w.assign(init->W, init->W + p);
+  t.c.assign(init->C, init->C + q);
+  t.B = init->B[0];
+  t.sigE = init->sigE;
+  t.sigF = init->sigF;
+  t.sigH = init->sigH;
+  t.sigT = init->sigT[0];
+  return t;
+}
+
 // EMstep_W's coefficients (:60-70) and EMstepC_fast's mu coefficients (:354, :358) (ppls_math.h).
 void rank1_coefs(const Rank1& t, double* c1, double* c2, double* c3, double* al, double* be, double* ga,
                  double* de) {
@@ -2564,13 +2609,25 @@ void meta_mstep(std::vector<MetaPop>& pops, int p, int q, std::vector<double>& w
 
 void meta_params_out(const std::vector<MetaPop>& pops, double* params) {
   const int npop = (int)pops.size();
-  for (int j = 0; j < npop; ++j) {
-    params[j] = pops[j].t.B;
-    params[npop + j] = pops[j].t.sigE;
-    params[2 * npop + j] = pops[j].t.sigF;
-    params[3 * npop + j] = pops[j].t.sigH;
-    params[4 * npop + j] = pops[j].t.sigT;
+  for (int j = 0; j < npop; ++j) rank1_to_params(pops[j].t, params, npop, j);
+}
+
+// The populations' rows (K) and sums of squares (2K: ssq(X_j), ssq(Y_j)) as meta_dev_begin takes them.
+void meta_pack_counts(const std::vector<MetaPop>& pops, std::vector<double>& hN, std::vector<double>& hs) {
+  const size_t K = pops.size();
+  hN.resize(K);
+  hs.resize(2 * K);
+  for (size_t j = 0; j < K; ++j) {
+    hN[j] = pops[j].N;
+    hs[2 * j] = pops[j].ssq[0];
+    hs[2 * j + 1] = pops[j].ssq[1];
   }
+}
+
+// What a fit's start shares: every log-likelihood slot NaN until its step is reached.
+void meta_log_clear(ppls_meta_fit* out, int max_steps, int npop) {
+  if (!out->log) return;
+  for (size_t e = 0; e < ((size_t)max_steps + 1) * npop; ++e) out->log[e] = NAN;
 }
 
 int meta_sweep_all(ppls_ctx* c, std::vector<MetaPop>& pops, const std::vector<double>& w,
@@ -2689,13 +2746,7 @@ int meta_dev_loop(ppls_ctx* c, MetaDev& d, int K, int max_steps, double atol, in
   if (out->log) std::copy(hl.begin(), hl.end(), out->log);
   std::copy(hw.begin(), hw.begin() + p, out->W);
   std::copy(hc.begin(), hc.begin() + q, out->C);
-  for (int j = 0; j < K; ++j) {
-    out->params[j] = hst[(size_t)j].B;
-    out->params[K + j] = hst[(size_t)j].sigE;
-    out->params[2 * K + j] = hst[(size_t)j].sigF;
-    out->params[3 * K + j] = hst[(size_t)j].sigH;
-    out->params[4 * K + j] = hst[(size_t)j].sigT;
-  }
+  for (int j = 0; j < K; ++j) rank1_to_params(hst[(size_t)j], out->params, K, j);
   return PPLS_OK;
 }
 
@@ -2782,12 +2833,8 @@ int meta_ppls_device(ppls_ctx* c, const std::vector<MetaPop>& pops, const Rank1&
     HIPCHK(c, hipMemcpyAsync(sg.bnd, bnd.data(), sizeof(int64_t) * bnd.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(sg.seg, seg.data(), sizeof(int) * seg.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(sg.segend, se.data(), sizeof(int64_t) * K, hipMemcpyHostToDevice, c->stream));
-    std::vector<double> hN((size_t)K), hs((size_t)2 * K);
-    for (int j = 0; j < K; ++j) {
-      hN[(size_t)j] = pops[j].N;
-      hs[(size_t)2 * j] = pops[j].ssq[0];
-      hs[(size_t)2 * j + 1] = pops[j].ssq[1];
-    }
+    std::vector<double> hN, hs;
+    meta_pack_counts(pops, hN, hs);
     if ((rc = meta_dev_begin(c, d, K, hN.data(), hs.data(), t0, max_steps))) return rc;   // (synchronises)
   }
   a.X = c->X;
@@ -2939,26 +2986,19 @@ int meta_xp_ensure(ppls_ctx* c, const std::vector<MetaPop>& pops, const int64_t*
   double* part = nullptr;
   int rc_alloc = dalloc(c, &c->mx_S, (size_t)K * PP);
   if (!rc_alloc && part_len) rc_alloc = dalloc(c, &part, part_len);
-  if (c->nranks > 1 || c->reducer) {
-    const double f = rc_alloc ? 1.0 : 0.0;
-    double tot = 0.0;
-    hipError_t e = hipMemcpyAsync(c->flag, &f, sizeof f, hipMemcpyHostToDevice, c->stream);
-    rc = e == hipSuccess ? allreduce(c, c->flag, 1) : fail(c, PPLS_E_HIP, "meta_xprod: %s", hipGetErrorString(e));
-    if (!rc) {
-      e = hipMemcpyAsync(&tot, c->flag, sizeof tot, hipMemcpyDeviceToHost, c->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      if (e != hipSuccess) rc = fail(c, PPLS_E_HIP, "meta_xprod: %s", hipGetErrorString(e));
-    }
-    if (!rc && tot > 0.0)
+  double tot = rc_alloc ? 1.0 : 0.0;
+  if (collective(c)) {
+    if (!(rc = agree(c, &tot, 1)) && tot > 0.0)
       rc = fail(c, PPLS_E_NOMEM, "meta_xprod: %d rank(s) could not allocate the %d population cross-products (%.3g GB)",
                 (int)tot, K, 8.0 * K * (double)PP / 1e9);
-    if (rc) { dfree(c->mx_S); dfree(part); return rc; }
-  } else if (rc_alloc) {
+  } else {
+    rc = rc_alloc;
+  }
+  if (rc) {
     dfree(c->mx_S);
     dfree(part);
-    return rc_alloc;
+    return rc;
   }
-  rc = PPLS_OK;
   for (int j = 0; j < K && !rc; ++j) {
     if (pops[j].nloc > 0) {
       rc = gram_run(c, shape(j), pops[j].nloc, 0, c->mx_S + (size_t)j * PP, nullptr, part);
@@ -2978,6 +3018,19 @@ int meta_xp_ensure(ppls_ctx* c, const std::vector<MetaPop>& pops, const int64_t*
   return PPLS_OK;
 }
 
+// meta_EMstep after the populations' statistics, from rows or from cross-products: the M-step and
+// the outputs.
+void meta_emstep_finish(std::vector<MetaPop>& pops, int p, int q, std::vector<double>& w, std::vector<double>& cv,
+                        double* W_out, double* C_out, double* params_out, double* Cxt, double* Cyu) {
+  std::vector<double> cx, cy;
+  meta_mstep(pops, p, q, w, cv, Cxt ? &cx : nullptr, Cyu ? &cy : nullptr);
+  std::copy(w.begin(), w.end(), W_out);
+  std::copy(cv.begin(), cv.end(), C_out);
+  meta_params_out(pops, params_out);
+  if (Cxt) std::copy(cx.begin(), cx.end(), Cxt);
+  if (Cyu) std::copy(cy.begin(), cy.end(), Cyu);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2995,26 +3048,13 @@ int ppls_meta_emstep(ppls_ctx* c, int npop, const int64_t* pop_local, const int6
   std::vector<MetaPop> pops;
   if ((rc = meta_setup(c, npop, pop_local, pop_total, pops))) return rc;
   std::vector<double> w(W, W + c->p), cv(C, C + c->q);
-  for (int j = 0; j < npop; ++j) {
-    Rank1& t = pops[j].t;
-    t.B = params_in[j];
-    t.sigE = params_in[npop + j];
-    t.sigF = params_in[2 * npop + j];
-    t.sigH = params_in[3 * npop + j];
-    t.sigT = params_in[4 * npop + j];
-  }
+  for (int j = 0; j < npop; ++j) pops[j].t = rank1_from_params(params_in, npop, j);
   if (c->meta_xprod) {   // the statistics from the populations' cross-products (formed once, kept)
     if ((rc = meta_xp_ensure(c, pops, pop_local, pop_total)) || (rc = meta_xprod_all(c, c->mx_S, pops, w, cv))) return rc;
   } else if ((rc = meta_sweep_all(c, pops, w, cv))) {
     return rc;
   }
-  std::vector<double> cx, cy;
-  meta_mstep(pops, c->p, c->q, w, cv, Cxt ? &cx : nullptr, Cyu ? &cy : nullptr);
-  std::copy(w.begin(), w.end(), W_out);
-  std::copy(cv.begin(), cv.end(), C_out);
-  meta_params_out(pops, params_out);
-  if (Cxt) std::copy(cx.begin(), cx.end(), Cxt);
-  if (Cyu) std::copy(cy.begin(), cy.end(), Cyu);
+  meta_emstep_finish(pops, c->p, c->q, w, cv, W_out, C_out, params_out, Cxt, Cyu);
   return PPLS_OK;
 }
 
@@ -3033,28 +3073,16 @@ int ppls_meta_ppls(ppls_ctx* c, int npop, const int64_t* pop_local, const int64_
   std::vector<MetaPop> pops;
   if ((rc = meta_setup(c, npop, pop_local, pop_total, pops))) return rc;
   const int p = c->p, q = c->q;
-  std::vector<double> w(init->W, init->W + p), cv(init->C, init->C + q);
-  Rank1 t0;
-  t0.w = w;
-  t0.c = cv;
-  t0.B = init->B[0];
-  t0.sigE = init->sigE;
-  t0.sigF = init->sigF;
-  t0.sigH = init->sigH;
-  t0.sigT = init->sigT[0];
+  const Rank1 t0 = rank1_from_init(init, p, q);
+  std::vector<double> w = t0.w, cv = t0.c;
   for (auto& pp : pops) pp.t = t0;   // params = lapply(.., list(B_T = Bnw, sigX = signw[1], ...)) (:545)
   auto crit = [&](double x) { return crit_abs ? std::fabs(x) : x; };
   const size_t ld = (size_t)max_steps + 1;
-  if (out->log)
-    for (size_t e = 0; e < ld * npop; ++e) out->log[e] = NAN;
+  meta_log_clear(out, max_steps, npop);
   if (c->meta_xprod) {   // every step reads the K cross-product matrices (8 K P^2 bytes), not the rows
     if ((rc = meta_xp_ensure(c, pops, pop_local, pop_total))) return rc;
-    std::vector<double> hN((size_t)npop), hs((size_t)2 * npop);
-    for (int j = 0; j < npop; ++j) {
-      hN[(size_t)j] = pops[j].N;
-      hs[(size_t)2 * j] = pops[j].ssq[0];   // meta_setup's, from the rows
-      hs[(size_t)2 * j + 1] = pops[j].ssq[1];
-    }
+    std::vector<double> hN, hs;   // (the sums of squares are meta_setup's, from the rows)
+    meta_pack_counts(pops, hN, hs);
     return meta_ppls_xprod(c, c->mx_S, npop, hN.data(), hs.data(), c->ssq_host[0], c->ssq_host[1], (double)c->n_total, t0,
                            max_steps, atol, crit_abs, 4, out);
   }
@@ -3941,8 +3969,6 @@ int cv_upload_coef(ppls_ctx* c, CvScratch& tmp, const double* M, int rowsM, int 
   return PPLS_OK;
 }
 
-bool cv_collective(const ppls_ctx* c) { return c->nranks > 1 || c->reducer; }
-
 }  // namespace
 
 extern "C" {
@@ -3997,7 +4023,7 @@ int ppls_xprod_downdate(ppls_ctx* dst, ppls_ctx* src, const int64_t* out_rows, i
     return rc;
   }
   const auto t0 = std::chrono::steady_clock::now();
-  const bool coll = cv_collective(src);
+  const bool coll = collective(src);
   const int P = src->ldx + src->ldy;
   const size_t PP = (size_t)P * P;
   // this rank's verdict on its arguments joins the agreement below, so that ranks return together
@@ -4029,10 +4055,7 @@ int ppls_xprod_downdate(ppls_ctx* dst, ppls_ctx* src, const int64_t* out_rows, i
   double n_out_total = (double)no;
   if (coll) {
     double f[3] = {rc_alloc ? 1.0 : 0.0, bad ? 1.0 : 0.0, (double)no};
-    HIPCHK(dst, hipMemcpyAsync(src->flag, f, sizeof f, hipMemcpyHostToDevice, src->stream));
-    if ((rc = allreduce(src, src->flag, 3))) { dfree(dst->xp_S); dst->err = src->err; return rc; }
-    HIPCHK(dst, hipMemcpyAsync(f, src->flag, sizeof f, hipMemcpyDeviceToHost, src->stream));
-    HIPCHK(dst, hipStreamSynchronize(src->stream));
+    if ((rc = agree(src, f, 3))) { dfree(dst->xp_S); dst->err = src->err; return rc; }
     if (f[0] > 0.0) {
       dfree(dst->xp_S);
       return fail(dst, PPLS_E_NOMEM, "downdate of S: %d rank(s) could not allocate S, the held-out rows or their Gram", (int)f[0]);
@@ -4596,7 +4619,74 @@ int stream_refuse(ppls_ctx* c, int rc) {
   return rc;
 }
 
-bool st_collective(const ppls_ctx* c) { return c->nranks > 1 || c->reducer; }
+// ---- ppls_stream_end: what the plain and the fold stream share -------------------------------------
+// Sharded, every rank must reach every collective of the call.  A HIP error in this rank's own work
+// between the collectives therefore goes into a flag the ranks agree on (agree), so every rank
+// returns and none waits alone; only a failed copy of a collective's own buffer returns at once
+// (that rank cannot take part in a collective over device buffers at all): REFUSECHK, which drops
+// the stream.
+#define REFUSECHK(c, call)                                                                                          \
+  do {                                                                                                              \
+    hipError_t e_ = (call);                                                                                         \
+    if (e_ != hipSuccess)                                                                                           \
+      return stream_refuse((c), fail((c), PPLS_E_HIP, "%s: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__)); \
+  } while (0)
+
+// A HIP error of this rank's own steps after the collectives: its verdict, which the last collective shares.
+int end_hip(ppls_ctx* c, hipError_t e, const char* what) {
+  return e == hipSuccess ? PPLS_OK : fail(c, PPLS_E_HIP, "ppls_stream_end, %s: %s", what, hipGetErrorString(e));
+}
+
+// The diagonal of a P x P device matrix.
+hipError_t diag_to_host(const double* S, int P, std::vector<double>& diag) {
+  diag.resize((size_t)P);
+  return hipMemcpy2D(diag.data(), sizeof(double), S, sizeof(double) * ((size_t)P + 1), sizeof(double), (size_t)P,
+                     hipMemcpyDeviceToHost);
+}
+
+// ||X||^2, ||Y||^2 = the traces of the diagonal blocks of a matrix in the joint layout, in column order.
+void diag_traces(const ppls_ctx* c, const std::vector<double>& diag, double s2[2]) {
+  s2[0] = s2[1] = 0.0;
+  for (int j = 0; j < c->p; ++j) s2[0] += diag[(size_t)j];
+  for (int j = 0; j < c->q; ++j) s2[1] += diag[(size_t)c->ldx + j];
+}
+
+int traces_finite(ppls_ctx* c, const double s2[2]) {
+  for (int k = 0; k < 2; ++k)
+    if (!std::isfinite(s2[k]))
+      return fail(c, PPLS_E_ARG,
+                  "%c contains NaN or Inf (the trace of its streamed cross-products is %g; values beyond 1.3e154 "
+                  "also overflow it): the reference's svd() in orth() stops on non-finite data (EM_W_multi.R:732-733)",
+                  k ? 'Y' : 'X', s2[k]);
+  return PPLS_OK;
+}
+
+// The transform of a stream of N rows with mean m (joint layout) and centred sums of squares dsum:
+// cen, scl over the p + q real columns as ppls_scale_get reports them, and d (joint layout, 1 where
+// nothing is divided) for the kernels.  Refuses what R's scale() would fill with NaN or Inf.
+int stream_transform(ppls_ctx* c, double N, const std::vector<double>& m, const std::vector<double>& dsum,
+                     std::vector<double>& cen, std::vector<double>& scl, std::vector<double>& d) {
+  const int p = c->p, q = c->q, ldx = c->ldx;
+  d.assign((size_t)ldx + c->ldy, 1.0);
+  for (int j = 0; j < p + q; ++j) {
+    cen[(size_t)j] = c->st_center ? m[(size_t)(j < p ? j : ldx + j - p)] : 0.0;
+    scl[(size_t)j] = 1.0;
+  }
+  if (!c->st_scale) return PPLS_OK;
+  if (N < 2.0)
+    return fail(c, PPLS_E_ARG, "scale = TRUE needs at least 2 rows (over all ranks: %lld): the standard deviation "
+                               "divides by n - 1", (long long)N);
+  for (int j = 0; j < p + q; ++j) {
+    const int jj = j < p ? j : ldx + j - p;
+    const double dj = std::sqrt(dsum[(size_t)jj] / (N - 1.0));
+    if (!(dj > 0.0) || !std::isfinite(dj))
+      return fail(c, PPLS_E_ARG, "%c column %d has standard deviation %g (over all ranks): scale = TRUE would fill it "
+                                 "with NaN or Inf, as R's scale() does; the stream is dropped",
+                  j < p ? 'X' : 'Y', (j < p ? j : j - p) + 1, dj);
+    d[(size_t)jj] = scl[(size_t)j] = dj;
+  }
+  return PPLS_OK;
+}
 
 // ppls_stream_begin (nfolds = 0) and ppls_stream_begin_folds.
 int stream_begin(ppls_ctx* c, int p, int q, int center, int scale, int nfolds) {
@@ -4611,7 +4701,7 @@ int stream_begin(ppls_ctx* c, int p, int q, int center, int scale, int nfolds) {
   for (int b = 0; b < 2; ++b)
     if (!c->st_done[b]) HIPCHK(c, hipEventCreateWithFlags(&c->st_done[b], hipEventDisableTiming));
   const int P = c->ldx + c->ldy;
-  const size_t nvec = (size_t)6 * P + 8 + (size_t)nfolds;   // (a fold stream: + the folds' weights at the end)
+  const size_t nvec = (size_t)5 * P + (size_t)nfolds;   // (a fold stream: + the folds' weights at the end)
   auto drop = [&]() {
     dfree(c->xp_S);
     dfree(c->st_vec);
@@ -4721,15 +4811,13 @@ int stream_rows_from(ppls_ctx* c, ppls_ctx* src, const int32_t* fold, bool label
 // xp_S = the sum of the fold matrices but `fold` (-1: all), with n_total and ||X||^2, ||Y||^2 (the
 // traces of S's diagonal blocks, in column order) to match.  No state checks.
 int fold_select(ppls_ctx* c, int fold) {
-  const int p = c->p, q = c->q, ldx = c->ldx, P = c->ldx + c->ldy;
+  const int P = c->ldx + c->ldy;
   HIPCHK(c, ppls_launch_cvs_select(c->st_fS, c->st_nfolds, fold, (int64_t)P * P, c->xp_S, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::vector<double> diag((size_t)P);
-  HIPCHK(c, hipMemcpy2D(diag.data(), sizeof(double), c->xp_S, sizeof(double) * ((size_t)P + 1), sizeof(double), (size_t)P,
-                        hipMemcpyDeviceToHost));
-  double s2[2] = {0.0, 0.0};
-  for (int j = 0; j < p; ++j) s2[0] += diag[(size_t)j];
-  for (int j = 0; j < q; ++j) s2[1] += diag[(size_t)ldx + j];
+  std::vector<double> diag;
+  HIPCHK(c, diag_to_host(c->xp_S, P, diag));
+  double s2[2];
+  diag_traces(c, diag, s2);
   HIPCHK(c, hipMemcpy(c->ssq, s2, sizeof s2, hipMemcpyHostToDevice));
   c->ssq_host[0] = s2[0];
   c->ssq_host[1] = s2[1];
@@ -4749,87 +4837,105 @@ int fold_state_check(ppls_ctx* c) {
   return PPLS_OK;
 }
 
-// ppls_stream_end of a fold stream, up to and including the finish.  Returns with
-// *left = true where the caller must return at once (the stream is dropped already: a collective
-// failed, or a failure every rank agreed on), else this rank's verdict on the finish, which the
-// caller's last collective shares.  On PPLS_OK: *N_out rows over all ranks, the transform in cen / scl,
-// ||X||^2, ||Y||^2 in s2, and the context selected on all folds.
-int fold_end(ppls_ctx* c, double* N_out, std::vector<double>& cen, std::vector<double>& scl, double s2[2], bool* left) {
-  *left = true;
-#define FENDCHK(call)                                                                                             \
-  do {                                                                                                            \
-    hipError_t e_ = (call);                                                                                       \
-    if (e_ != hipSuccess)                                                                                         \
-      return stream_refuse(c, fail(c, PPLS_E_HIP, "%s: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__)); \
-  } while (0)
+// The collectives of ppls_stream_end, over K Chan states (N_k, mean_k, S_k): a fold stream's K folds,
+// or the plain stream's one state.  S: the K matrices, P x P each; mean_d: their K x P
+// means on the device (overwritten); Nk: this rank's rows per state; what: the matrices' name in a
+// message.  On PPLS_OK every rank holds the same matrices, Nk the rows over all ranks and mh (K x P)
+// the means over all ranks.  Any other return has dropped the stream: the caller returns at once.
+int stream_end_merge(ppls_ctx* c, double* S, int K, double* mean_d, std::vector<double>& Nk, std::vector<double>& mh,
+                     const char* what) {
+  int rc;
+  const int P = c->ldx + c->ldy;
+  const size_t PP = (size_t)P * P, KP = (size_t)K * P;
+  mh.assign(KP, 0.0);
+  if (!c->st_failed && hipMemcpy(mh.data(), mean_d, sizeof(double) * KP, hipMemcpyDeviceToHost) != hipSuccess)
+    c->st_failed = true;
+  if (!collective(c))
+    return c->st_failed ? stream_refuse(c, fail(c, PPLS_E_STATE, "the stream failed before ppls_stream_end")) : PPLS_OK;
+  // {failed, N_rk, N_rk m_rk for all k}: the global counts and means, and the agreement that nobody
+  // failed, in one all-reduce
+  const size_t nred = 1 + (size_t)K + KP;
+  CvScratch tmp;
+  double* red = nullptr;
+  if ((rc = tmp.get(c, &red, nred))) return stream_refuse(c, rc);
+  std::vector<double> h(nred, 0.0);
+  h[0] = c->st_failed ? 1.0 : 0.0;
+  for (int k = 0; k < K; ++k) {
+    h[(size_t)1 + k] = Nk[(size_t)k];
+    for (int j = 0; j < P; ++j)
+      h[1 + (size_t)K + (size_t)k * P + j] = c->st_failed ? 0.0 : Nk[(size_t)k] * mh[(size_t)k * P + j];
+  }
+  REFUSECHK(c, hipMemcpyAsync(red, h.data(), sizeof(double) * nred, hipMemcpyHostToDevice, c->stream));
+  if ((rc = allreduce(c, red, nred))) return stream_refuse(c, rc);
+  REFUSECHK(c, hipMemcpyAsync(h.data(), red, sizeof(double) * nred, hipMemcpyDeviceToHost, c->stream));
+  REFUSECHK(c, hipStreamSynchronize(c->stream));
+  if (h[0] > 0.0)
+    return stream_refuse(c, fail(c, PPLS_E_STATE, "the stream failed on %d rank(s) before ppls_stream_end", (int)h[0]));
+  // each rank's S_k is centred about its own mean: + N_rk (m_rk - m_k)(m_rk - m_k)', the merge with
+  // no partials, state by state
+  std::vector<double> d(KP, 0.0);
+  for (int k = 0; k < K; ++k)
+    for (int j = 0; j < P; ++j) {
+      const size_t at = (size_t)k * P + j;
+      const double mg = h[(size_t)1 + k] > 0.0 ? h[1 + (size_t)K + at] / h[(size_t)1 + k] : 0.0;
+      d[at] = mh[at] - mg;
+      mh[at] = mg;
+    }
+  hipError_t e = hipSuccess;
+  if (c->st_center) {
+    e = hipMemcpyAsync(mean_d, d.data(), sizeof(double) * KP, hipMemcpyHostToDevice, c->stream);
+    for (int k = 0; k < K && e == hipSuccess; ++k)
+      if (Nk[(size_t)k] > 0.0)
+        e = ppls_launch_stream_merge(S + (size_t)k * PP, c->p, c->ldx, c->q, c->ldy, nullptr, 0, mean_d + (size_t)k * P,
+                                     Nk[(size_t)k], c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  }
+  for (int k = 0; k < K; ++k) Nk[(size_t)k] = h[(size_t)1 + k];
+  // nobody enters the all-reduce of the matrices alone (the pattern of xprod_setup)
+  double bad = e == hipSuccess ? 0.0 : 1.0;
+  if ((rc = agree(c, &bad, 1))) return stream_refuse(c, rc);
+  if (bad > 0.0)
+    return stream_refuse(c, fail(c, PPLS_E_HIP, "the cross-rank merge of %s failed on %d rank(s)", what, (int)bad));
+  if ((rc = allreduce(c, S, (size_t)K * PP))) return stream_refuse(c, rc);
+  REFUSECHK(c, hipStreamSynchronize(c->stream));
+  return PPLS_OK;
+}
+
+// The finish of a plain stream of N rows with mean m (over all ranks, as every rank holds them after
+// stream_end_merge), on this rank alone and with the same bits on every rank: the transform in
+// cen / scl, S standardised where scale is set, ||X||^2, ||Y||^2 in s2 and on the device.  Returns
+// PPLS_OK, a refusal decided from the shared values (PPLS_E_ARG: the same on every rank) or a HIP error
+// of this rank, which the caller's last collective makes everybody's.
+int plain_finish(ppls_ctx* c, double N, const std::vector<double>& m, std::vector<double>& cen, std::vector<double>& scl,
+                 double s2[2]) {
+  int rc;
+  const int P = c->ldx + c->ldy;
+  if (!(N >= 1.0)) return fail(c, PPLS_E_ARG, "no rows were streamed (over all ranks)");
+  std::vector<double> diag, d;
+  auto traces = [&]() -> int {
+    const int r = end_hip(c, diag_to_host(c->xp_S, P, diag), "the diagonal of S");
+    if (r) return r;
+    diag_traces(c, diag, s2);
+    return traces_finite(c, s2);
+  };
+  if ((rc = traces()) || (rc = stream_transform(c, N, m, diag, cen, scl, d))) return rc;
+  if (c->st_scale) {
+    hipError_t e = hipMemcpyAsync(c->st_vec, d.data(), sizeof(double) * P, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = ppls_launch_stream_standardise(c->xp_S, c->p, c->ldx, c->q, c->ldy, c->st_vec, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if ((rc = end_hip(c, e, "standardising S")) || (rc = traces())) return rc;
+  }
+  return end_hip(c, hipMemcpy(c->ssq, s2, sizeof(double) * 2, hipMemcpyHostToDevice), "||X||^2, ||Y||^2");
+}
+
+// The finish of a fold stream from the fold counts Nk and fold means fm of
+// stream_end_merge, with plain_finish's returns.  On PPLS_OK: *N_out rows over all ranks, the
+// transform in cen / scl, ||X||^2, ||Y||^2 in s2, and the context selected on all folds.
+int fold_finish(ppls_ctx* c, const std::vector<double>& Nk, const std::vector<double>& fm, double* N_out,
+                std::vector<double>& cen, std::vector<double>& scl, double s2[2]) {
   int rc;
   const int K = c->st_nfolds, p = c->p, q = c->q, ldx = c->ldx, P = c->ldx + c->ldy;
-  const size_t PP = (size_t)P * P, KP = (size_t)K * P;
-  std::vector<double> fm(KP, 0.0), Nk((size_t)K);
-  for (int k = 0; k < K; ++k) Nk[(size_t)k] = (double)c->st_fN[(size_t)k];
-  if (!c->st_failed && hipMemcpy(fm.data(), c->st_fmean, sizeof(double) * KP, hipMemcpyDeviceToHost) != hipSuccess)
-    c->st_failed = true;
-  if (st_collective(c)) {
-    // {failed, N_rk, N_rk m_rk for all k}: the global fold counts and fold means, and the agreement
-    // that nobody failed, in one all-reduce
-    const size_t nred = 1 + (size_t)K + KP;
-    CvScratch tmp;
-    double* red = nullptr;
-    if ((rc = tmp.get(c, &red, nred))) return stream_refuse(c, rc);
-    std::vector<double> h(nred, 0.0);
-    h[0] = c->st_failed ? 1.0 : 0.0;
-    for (int k = 0; k < K; ++k) {
-      h[(size_t)1 + k] = Nk[(size_t)k];
-      for (int j = 0; j < P; ++j)
-        h[1 + (size_t)K + (size_t)k * P + j] = c->st_failed ? 0.0 : Nk[(size_t)k] * fm[(size_t)k * P + j];
-    }
-    FENDCHK(hipMemcpyAsync(red, h.data(), sizeof(double) * nred, hipMemcpyHostToDevice, c->stream));
-    if ((rc = allreduce(c, red, nred))) return stream_refuse(c, rc);
-    FENDCHK(hipMemcpyAsync(h.data(), red, sizeof(double) * nred, hipMemcpyDeviceToHost, c->stream));
-    FENDCHK(hipStreamSynchronize(c->stream));
-    if (h[0] > 0.0)
-      return stream_refuse(c, fail(c, PPLS_E_STATE, "the stream failed on %d rank(s) before ppls_stream_end", (int)h[0]));
-    // each rank's S_k is centred about its own fold mean: + N_rk (m_rk - m_k)(m_rk - m_k)', the merge
-    // with no partials, fold by fold
-    std::vector<double> d(KP, 0.0);
-    for (int k = 0; k < K; ++k)
-      for (int j = 0; j < P; ++j) {
-        const size_t at = (size_t)k * P + j;
-        const double mg = h[(size_t)1 + k] > 0.0 ? h[1 + (size_t)K + at] / h[(size_t)1 + k] : 0.0;
-        d[at] = fm[at] - mg;
-        fm[at] = mg;
-      }
-    hipError_t e = hipSuccess;
-    if (c->st_center) {
-      e = hipMemcpyAsync(c->st_fmean, d.data(), sizeof(double) * KP, hipMemcpyHostToDevice, c->stream);
-      for (int k = 0; k < K && e == hipSuccess; ++k)
-        if (Nk[(size_t)k] > 0.0)
-          e = ppls_launch_stream_merge(c->st_fS + (size_t)k * PP, p, ldx, q, c->ldy, nullptr, 0, c->st_fmean + (size_t)k * P,
-                                       Nk[(size_t)k], c->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    for (int k = 0; k < K; ++k) Nk[(size_t)k] = h[(size_t)1 + k];
-    // nobody enters the all-reduce of the fold matrices alone
-    const double f = e == hipSuccess ? 0.0 : 1.0;
-    double tot = 0.0;
-    FENDCHK(hipMemcpyAsync(c->flag, &f, sizeof f, hipMemcpyHostToDevice, c->stream));
-    if ((rc = allreduce(c, c->flag, 1))) return stream_refuse(c, rc);
-    FENDCHK(hipMemcpyAsync(&tot, c->flag, sizeof tot, hipMemcpyDeviceToHost, c->stream));
-    FENDCHK(hipStreamSynchronize(c->stream));
-    if (tot > 0.0)
-      return stream_refuse(c, fail(c, PPLS_E_HIP, "the cross-rank merge of the fold matrices failed on %d rank(s)", (int)tot));
-    if ((rc = allreduce(c, c->st_fS, (size_t)K * PP))) return stream_refuse(c, rc);
-    FENDCHK(hipStreamSynchronize(c->stream));
-  } else if (c->st_failed) {
-    return stream_refuse(c, fail(c, PPLS_E_STATE, "the stream failed before ppls_stream_end"));
-  }
-#undef FENDCHK
-  // From here every rank holds the same fold matrices, counts and fold means; the steps below run on
-  // this rank alone and give the same bits on every rank.
-  *left = false;
-  auto hip_failed = [&](hipError_t e, const char* what) -> int {
-    return e == hipSuccess ? PPLS_OK : fail(c, PPLS_E_HIP, "ppls_stream_end, %s: %s", what, hipGetErrorString(e));
-  };
+  const size_t KP = (size_t)K * P;
   double N = 0.0;
   for (int k = 0; k < K; ++k) {
     if (!(Nk[(size_t)k] >= 1.0))
@@ -4837,7 +4943,7 @@ int fold_end(ppls_ctx* c, double* N_out, std::vector<double>& cen, std::vector<d
     N += Nk[(size_t)k];
   }
   // the global mean, summed in fold order, and the folds' offsets from it
-  std::vector<double> m((size_t)P, 0.0), ev(KP, 0.0), w((size_t)K), d((size_t)P, 1.0), dsum((size_t)P);
+  std::vector<double> m((size_t)P, 0.0), ev(KP, 0.0), d, dsum((size_t)P);
   for (int j = 0; j < P; ++j) {
     double acc = 0.0;
     for (int k = 0; k < K; ++k) acc += Nk[(size_t)k] * fm[(size_t)k * P + j];
@@ -4846,46 +4952,21 @@ int fold_end(ppls_ctx* c, double* N_out, std::vector<double>& cen, std::vector<d
   if (c->st_center)
     for (int k = 0; k < K; ++k)
       for (int j = 0; j < P; ++j) ev[(size_t)k * P + j] = fm[(size_t)k * P + j] - m[(size_t)j];
-  for (int k = 0; k < K; ++k) w[(size_t)k] = Nk[(size_t)k];
-  double *vec = c->st_vec, *wd = vec + 6 * (size_t)P + 8;
+  double *vec = c->st_vec, *wd = vec + 5 * (size_t)P;   // the folds' weights N_k
   hipError_t e = hipMemcpyAsync(c->st_fmean, ev.data(), sizeof(double) * KP, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(wd, w.data(), sizeof(double) * K, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(wd, Nk.data(), sizeof(double) * K, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = ppls_launch_cvs_diag(c->st_fS, K, p, ldx, q, c->ldy, c->st_fmean, wd, vec + P, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(dsum.data(), vec + P, sizeof(double) * P, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if ((rc = hip_failed(e, "the diagonal of the fold matrices"))) return rc;
-  double tr[2] = {0.0, 0.0};
-  for (int j = 0; j < p; ++j) tr[0] += dsum[(size_t)j];
-  for (int j = 0; j < q; ++j) tr[1] += dsum[(size_t)ldx + j];
-  for (int k = 0; k < 2; ++k)
-    if (!std::isfinite(tr[k]))
-      return fail(c, PPLS_E_ARG,
-                  "%c contains NaN or Inf (the trace of its streamed cross-products is %g; values beyond 1.3e154 "
-                  "also overflow it): the reference's svd() in orth() stops on non-finite data (EM_W_multi.R:732-733)",
-                  k ? 'Y' : 'X', tr[k]);
-  for (int j = 0; j < p + q; ++j) {
-    cen[(size_t)j] = c->st_center ? m[(size_t)(j < p ? j : ldx + j - p)] : 0.0;
-    scl[(size_t)j] = 1.0;
-  }
-  if (c->st_scale) {
-    if (N < 2.0)
-      return fail(c, PPLS_E_ARG, "scale = TRUE needs at least 2 rows (over all ranks: %lld): the standard deviation "
-                                 "divides by n - 1", (long long)N);
-    for (int j = 0; j < p + q; ++j) {
-      const int jj = j < p ? j : ldx + j - p;
-      const double dj = std::sqrt(dsum[(size_t)jj] / (N - 1.0));
-      if (!(dj > 0.0) || !std::isfinite(dj))
-        return fail(c, PPLS_E_ARG, "%c column %d has standard deviation %g (over all ranks): scale = TRUE would fill it "
-                                   "with NaN or Inf, as R's scale() does; the stream is dropped",
-                    j < p ? 'X' : 'Y', (j < p ? j : j - p) + 1, dj);
-      d[(size_t)jj] = scl[(size_t)j] = dj;
-    }
-  }
+  if ((rc = end_hip(c, e, "the diagonal of the fold matrices"))) return rc;
+  double tr[2];
+  diag_traces(c, dsum, tr);
+  if ((rc = traces_finite(c, tr)) || (rc = stream_transform(c, N, m, dsum, cen, scl, d))) return rc;
   if (c->st_center || c->st_scale) {   // one pass over every fold matrix: recentre and standardise
     e = hipMemcpyAsync(vec, d.data(), sizeof(double) * P, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = ppls_launch_cvs_finish(c->st_fS, K, p, ldx, q, c->ldy, c->st_fmean, wd, vec, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if ((rc = hip_failed(e, "recentring and standardising the fold matrices"))) return rc;
+    if ((rc = end_hip(c, e, "recentring and standardising the fold matrices"))) return rc;
   }
   for (int k = 0; k < K; ++k) c->st_fN[(size_t)k] = (int64_t)Nk[(size_t)k];
   c->st_fmean_h = fm;
@@ -4929,144 +5010,44 @@ int ppls_stream_end(ppls_ctx* c) {
   if (!c) return PPLS_E_ARG;
   if (c->st_state != 1) return fail(c, PPLS_E_STATE, "no stream is open: call ppls_stream_begin first");
   HIPCHK(c, hipSetDevice(c->device));
-  // Every return from here drops the stream (stream_refuse) or leaves the context streamed.  A HIP
-  // error in this rank's own work between the collectives goes into a flag the ranks all-reduce, so
-  // every rank returns and none waits alone; only a failed copy of a collective's own buffer returns
-  // at once (that rank cannot take part in a collective over device buffers at all).
-#define ENDCHK(call)                                                                                              \
-  do {                                                                                                            \
-    hipError_t e_ = (call);                                                                                       \
-    if (e_ != hipSuccess)                                                                                         \
-      return stream_refuse(c, fail(c, PPLS_E_HIP, "%s: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__)); \
-  } while (0)
+  // Every return from here drops the stream (stream_refuse) or leaves the context streamed.
   int rc;
-  const int p = c->p, q = c->q, ldx = c->ldx, P = c->ldx + c->ldy;
+  const int p = c->p, q = c->q, P = c->ldx + c->ldy;
   // wait for the pending chunk work; a failure (now or earlier) is agreed on below when sharded
   if (hipStreamSynchronize(c->st_stream) != hipSuccess) c->st_failed = true;
-  double* vec = c->st_vec;
-  double *delta = vec + 2 * P, *mean = vec + 3 * P, *red = vec + 5 * P;
-  std::vector<double> m((size_t)P, 0.0), h((size_t)P + 2, 0.0);
-  if (!c->st_failed && hipMemcpy(m.data(), mean, sizeof(double) * P, hipMemcpyDeviceToHost) != hipSuccess) c->st_failed = true;
-  double N = (double)c->st_rows;
-  const bool folds = c->st_nfolds > 0;   // a fold stream: fold_end below runs its collectives and its finish
-  if (folds) {
-  } else if (st_collective(c)) {
-    // {failed, N_r, N_r m_r}: the global N and mean, and the agreement that nobody failed, in one all-reduce
-    const double Nr = N;
-    h[0] = c->st_failed ? 1.0 : 0.0;
-    h[1] = Nr;
-    for (int j = 0; j < P; ++j) h[(size_t)2 + j] = c->st_failed ? 0.0 : Nr * m[(size_t)j];
-    ENDCHK(hipMemcpyAsync(red, h.data(), sizeof(double) * (P + 2), hipMemcpyHostToDevice, c->stream));
-    if ((rc = allreduce(c, red, (size_t)P + 2))) return stream_refuse(c, rc);
-    ENDCHK(hipMemcpyAsync(h.data(), red, sizeof(double) * (P + 2), hipMemcpyDeviceToHost, c->stream));
-    ENDCHK(hipStreamSynchronize(c->stream));
-    if (h[0] > 0.0)
-      return stream_refuse(c, fail(c, PPLS_E_STATE, "the stream failed on %d rank(s) before ppls_stream_end", (int)h[0]));
-    N = h[1];
-    std::vector<double> d((size_t)P, 0.0);
-    for (int j = 0; j < P; ++j) {
-      const double mg = N > 0.0 ? h[(size_t)2 + j] / N : 0.0;
-      d[(size_t)j] = m[(size_t)j] - mg;   // m_r - m
-      m[(size_t)j] = mg;
-    }
-    // each rank's S is centred about its own mean: + N_r (m_r - m)(m_r - m)', the merge with no partials
-    hipError_t e = hipSuccess;
-    if (c->st_center && Nr > 0.0) {
-      e = hipMemcpyAsync(delta, d.data(), sizeof(double) * P, hipMemcpyHostToDevice, c->stream);
-      if (e == hipSuccess) e = ppls_launch_stream_merge(c->xp_S, p, ldx, q, c->ldy, nullptr, 0, delta, Nr, c->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    // nobody enters the all-reduce of S alone (the pattern of xprod_setup)
-    const double f = e == hipSuccess ? 0.0 : 1.0;
-    double tot = 0.0;
-    ENDCHK(hipMemcpyAsync(c->flag, &f, sizeof f, hipMemcpyHostToDevice, c->stream));
-    if ((rc = allreduce(c, c->flag, 1))) return stream_refuse(c, rc);
-    ENDCHK(hipMemcpyAsync(&tot, c->flag, sizeof tot, hipMemcpyDeviceToHost, c->stream));
-    ENDCHK(hipStreamSynchronize(c->stream));
-    if (tot > 0.0)
-      return stream_refuse(c, fail(c, PPLS_E_HIP, "the cross-rank merge of S failed on %d rank(s)", (int)tot));
-    if ((rc = allreduce(c, c->xp_S, (size_t)P * P))) return stream_refuse(c, rc);
-    ENDCHK(hipStreamSynchronize(c->stream));
-  } else if (c->st_failed) {
-    return stream_refuse(c, fail(c, PPLS_E_STATE, "the stream failed before ppls_stream_end"));
-  }
-  // From here every rank holds the same S, N and mean.  The steps on them run on this rank alone;
-  // their outcome is PPLS_OK, a refusal decided from those shared values (PPLS_E_ARG: the same on
+  // the plain stream is one Chan state (st_rows, mean, xp_S), a fold stream one per fold
+  const bool folds = c->st_nfolds > 0;
+  const int K = folds ? c->st_nfolds : 1;
+  std::vector<double> Nk((size_t)K, (double)c->st_rows), m;
+  for (int k = 0; folds && k < K; ++k) Nk[(size_t)k] = (double)c->st_fN[(size_t)k];
+  if ((rc = stream_end_merge(c, folds ? c->st_fS : c->xp_S, K, folds ? c->st_fmean : c->st_vec + 3 * P, Nk, m,
+                             folds ? "the fold matrices" : "S")))
+    return rc;
+  // From here every rank holds the same matrices, counts and means.  The finish runs on this rank
+  // alone; its outcome is PPLS_OK, a refusal decided from those shared values (PPLS_E_ARG: the same on
   // every rank) or a HIP error of this rank, which the last collective below makes everybody's.
-  std::vector<double> diag((size_t)P), cen((size_t)p + q, 0.0), scl((size_t)p + q, 1.0);
-  double s2[2] = {0.0, 0.0};
-  auto hip_failed = [&](hipError_t e, const char* what) -> int {
-    return e == hipSuccess ? PPLS_OK : fail(c, PPLS_E_HIP, "ppls_stream_end, %s: %s", what, hipGetErrorString(e));
-  };
-  auto get_diag = [&]() -> int {
-    return hip_failed(hipMemcpy2D(diag.data(), sizeof(double), c->xp_S, sizeof(double) * ((size_t)P + 1), sizeof(double),
-                                  (size_t)P, hipMemcpyDeviceToHost), "the diagonal of S");
-  };
-  auto ssq_of = [&]() -> int {   // ||X||^2, ||Y||^2 = the traces of S's diagonal blocks, in column order
-    s2[0] = s2[1] = 0.0;
-    for (int j = 0; j < p; ++j) s2[0] += diag[(size_t)j];
-    for (int j = 0; j < q; ++j) s2[1] += diag[(size_t)ldx + j];
-    for (int k = 0; k < 2; ++k)
-      if (!std::isfinite(s2[k]))
-        return fail(c, PPLS_E_ARG,
-                    "%c contains NaN or Inf (the trace of its streamed cross-products is %g; values beyond 1.3e154 "
-                    "also overflow it): the reference's svd() in orth() stops on non-finite data (EM_W_multi.R:732-733)",
-                    k ? 'Y' : 'X', s2[k]);
-    return PPLS_OK;
-  };
-  auto finish_S = [&]() -> int {
-    int r;
-    if (!(N >= 1.0)) return fail(c, PPLS_E_ARG, "no rows were streamed (over all ranks)");
-    if ((r = get_diag()) || (r = ssq_of())) return r;
-    for (int j = 0; j < p + q; ++j) cen[(size_t)j] = c->st_center ? m[(size_t)(j < p ? j : ldx + j - p)] : 0.0;
-    if (c->st_scale) {
-      if (N < 2.0)
-        return fail(c, PPLS_E_ARG, "scale = TRUE needs at least 2 rows (over all ranks: %lld): the standard deviation "
-                                   "divides by n - 1", (long long)N);
-      std::vector<double> d((size_t)P, 1.0);
-      for (int j = 0; j < p + q; ++j) {
-        const int jj = j < p ? j : ldx + j - p;
-        const double dj = std::sqrt(diag[(size_t)jj] / (N - 1.0));
-        if (!(dj > 0.0) || !std::isfinite(dj))
-          return fail(c, PPLS_E_ARG, "%c column %d has standard deviation %g (over all ranks): scale = TRUE would fill it "
-                                     "with NaN or Inf, as R's scale() does; the stream is dropped",
-                      j < p ? 'X' : 'Y', (j < p ? j : j - p) + 1, dj);
-        d[(size_t)jj] = scl[(size_t)j] = dj;
-      }
-      hipError_t e = hipMemcpyAsync(vec, d.data(), sizeof(double) * P, hipMemcpyHostToDevice, c->stream);
-      if (e == hipSuccess) e = ppls_launch_stream_standardise(c->xp_S, p, ldx, q, c->ldy, vec, c->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      if ((r = hip_failed(e, "standardising S")) || (r = get_diag()) || (r = ssq_of())) return r;
-    }
-    return hip_failed(hipMemcpy(c->ssq, s2, sizeof s2, hipMemcpyHostToDevice), "||X||^2, ||Y||^2");
-  };
-  int local;
-  if (folds) {
-    bool left = false;
-    local = fold_end(c, &N, cen, scl, s2, &left);
-    if (left) return local;
-  } else {
-    local = finish_S();
-  }
+  std::vector<double> cen((size_t)p + q, 0.0), scl((size_t)p + q, 1.0);
+  double s2[2] = {0.0, 0.0}, N = Nk[0];
+  int local = folds ? fold_finish(c, Nk, m, &N, cen, scl, s2) : plain_finish(c, N, m, cen, scl, s2);
   const std::string local_err = c->err;
   // the staging buffers and partials go back before the free memory is read: the smallest free HBM
   // over all ranks, as compute_ssq records it, beside the agreement on the steps above
   const int64_t rows = c->st_rows, chunks = c->st_chunks;
   stream_release(c);   // (st_state = 0: stream_refuse below still clears S and have_data)
   size_t mfree = 0, mtot = 0;
-  if (!local) local = hip_failed(hipMemGetInfo(&mfree, &mtot), "hipMemGetInfo");
+  if (!local) local = end_hip(c, hipMemGetInfo(&mfree, &mtot), "hipMemGetInfo");
   c->mem_free_min = (double)mfree;
-  if (st_collective(c)) {
+  if (collective(c)) {
     CvScratch tmp;
     double* slots_d = nullptr;
     if ((rc = tmp.get(c, &slots_d, (size_t)c->nranks + 1))) return stream_refuse(c, rc);
     std::vector<double> slots((size_t)c->nranks + 1, 0.0);   // {HIP failures, free HBM of rank 0, 1, ...}
     slots[0] = local == PPLS_OK || local == PPLS_E_ARG ? 0.0 : 1.0;
     slots[(size_t)c->rank + 1] = (double)mfree;
-    ENDCHK(hipMemcpy(slots_d, slots.data(), sizeof(double) * slots.size(), hipMemcpyHostToDevice));
+    REFUSECHK(c, hipMemcpy(slots_d, slots.data(), sizeof(double) * slots.size(), hipMemcpyHostToDevice));
     if ((rc = allreduce(c, slots_d, slots.size()))) return stream_refuse(c, rc);
-    ENDCHK(hipStreamSynchronize(c->stream));
-    ENDCHK(hipMemcpy(slots.data(), slots_d, sizeof(double) * slots.size(), hipMemcpyDeviceToHost));
+    REFUSECHK(c, hipStreamSynchronize(c->stream));
+    REFUSECHK(c, hipMemcpy(slots.data(), slots_d, sizeof(double) * slots.size(), hipMemcpyDeviceToHost));
     if (slots[0] > 0.0 && (local == PPLS_OK || local == PPLS_E_ARG))
       local = fail(c, PPLS_E_HIP, "ppls_stream_end failed on %d other rank(s)", (int)slots[0]);
     else if (local)
@@ -5074,7 +5055,6 @@ int ppls_stream_end(ppls_ctx* c) {
     for (size_t k = 1; k < slots.size(); ++k) c->mem_free_min = std::min(c->mem_free_min, slots[k]);
   }
   if (local) return stream_refuse(c, local);
-#undef ENDCHK
   c->ssq_host[0] = s2[0];
   c->ssq_host[1] = s2[1];
   c->sc_center = cen;
@@ -5221,22 +5201,18 @@ namespace {
 // of S_j's diagonal blocks in column order; s2 = the whole data's ||X||^2, ||Y||^2 as fold_select(-1)
 // forms them (the diagonals added in fold order, then the columns), whatever is selected now.
 int stream_pops(ppls_ctx* c, std::vector<MetaPop>& pops, double s2[2]) {
-  const int K = c->st_nfolds, p = c->p, q = c->q, ldx = c->ldx, P = c->ldx + c->ldy;
+  const int K = c->st_nfolds, P = c->ldx + c->ldy;
   pops.assign((size_t)K, MetaPop());
-  std::vector<double> diag((size_t)P), dsum((size_t)P, 0.0);
+  std::vector<double> diag, dsum((size_t)P, 0.0);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int k = 0; k < K; ++k) {
-    HIPCHK(c, hipMemcpy2D(diag.data(), sizeof(double), c->st_fS + (size_t)k * P * P, sizeof(double) * ((size_t)P + 1),
-                          sizeof(double), (size_t)P, hipMemcpyDeviceToHost));
+    HIPCHK(c, diag_to_host(c->st_fS + (size_t)k * P * P, P, diag));
     MetaPop& pp = pops[(size_t)k];
     pp.N = (double)c->st_fN[(size_t)k];
-    for (int j = 0; j < p; ++j) pp.ssq[0] += diag[(size_t)j];
-    for (int j = 0; j < q; ++j) pp.ssq[1] += diag[(size_t)ldx + j];
+    diag_traces(c, diag, pp.ssq);
     for (int j = 0; j < P; ++j) dsum[(size_t)j] += diag[(size_t)j];
   }
-  s2[0] = s2[1] = 0.0;
-  for (int j = 0; j < p; ++j) s2[0] += dsum[(size_t)j];
-  for (int j = 0; j < q; ++j) s2[1] += dsum[(size_t)ldx + j];
+  diag_traces(c, dsum, s2);
   return PPLS_OK;
 }
 
@@ -5265,22 +5241,9 @@ int ppls_meta_emstep_stream(ppls_ctx* c, const double* W, const double* C, const
   if ((rc = stream_pops(c, pops, s2))) return rc;
   const int npop = (int)pops.size();
   std::vector<double> w(W, W + c->p), cv(C, C + c->q);
-  for (int j = 0; j < npop; ++j) {
-    Rank1& t = pops[j].t;
-    t.B = params_in[j];
-    t.sigE = params_in[npop + j];
-    t.sigF = params_in[2 * npop + j];
-    t.sigH = params_in[3 * npop + j];
-    t.sigT = params_in[4 * npop + j];
-  }
+  for (int j = 0; j < npop; ++j) pops[j].t = rank1_from_params(params_in, npop, j);
   if ((rc = meta_xprod_all(c, c->st_fS, pops, w, cv))) return rc;
-  std::vector<double> cx, cy;
-  meta_mstep(pops, c->p, c->q, w, cv, Cxt ? &cx : nullptr, Cyu ? &cy : nullptr);
-  std::copy(w.begin(), w.end(), W_out);
-  std::copy(cv.begin(), cv.end(), C_out);
-  meta_params_out(pops, params_out);
-  if (Cxt) std::copy(cx.begin(), cx.end(), Cxt);
-  if (Cyu) std::copy(cy.begin(), cy.end(), Cyu);
+  meta_emstep_finish(pops, c->p, c->q, w, cv, W_out, C_out, params_out, Cxt, Cyu);
   return PPLS_OK;
 }
 
@@ -5304,25 +5267,12 @@ int ppls_meta_ppls_stream(ppls_ctx* c, int max_steps, double atol, int crit_abs,
                   m ? 'Y' : 'X');
   if ((rc = ensure_r(c, 1, max_steps))) return rc;
   const int K = (int)pops.size();
-  Rank1 t0;
-  t0.w.assign(init->W, init->W + c->p);
-  t0.c.assign(init->C, init->C + c->q);
-  t0.B = init->B[0];
-  t0.sigE = init->sigE;
-  t0.sigF = init->sigF;
-  t0.sigH = init->sigH;
-  t0.sigT = init->sigT[0];
-  const size_t ld = (size_t)max_steps + 1;
-  if (out->log)
-    for (size_t e = 0; e < ld * K; ++e) out->log[e] = NAN;
-  std::vector<double> hN((size_t)K), hs((size_t)2 * K);
+  const Rank1 t0 = rank1_from_init(init, c->p, c->q);
+  meta_log_clear(out, max_steps, K);
+  std::vector<double> hN, hs;
+  meta_pack_counts(pops, hN, hs);
   double Ntot = 0.0;
-  for (int j = 0; j < K; ++j) {
-    hN[(size_t)j] = pops[j].N;
-    hs[(size_t)2 * j] = pops[j].ssq[0];
-    hs[(size_t)2 * j + 1] = pops[j].ssq[1];
-    Ntot += pops[j].N;
-  }
+  for (int j = 0; j < K; ++j) Ntot += hN[(size_t)j];
   return meta_ppls_xprod(c, c->st_fS, K, hN.data(), hs.data(), s2[0], s2[1], Ntot, t0, max_steps, atol, crit_abs, 5, out);
 }
 
@@ -5396,14 +5346,7 @@ int ppls_xprod_meta_stats(ppls_ctx* c, const double* W, const double* C, const d
   int rc;
   if ((rc = ensure_r(c, 1, 1))) return rc;
   std::vector<MetaPop> pops((size_t)K);
-  for (int j = 0; j < K; ++j) {
-    Rank1& t = pops[(size_t)j].t;
-    t.B = params[j];
-    t.sigE = params[K + j];
-    t.sigF = params[2 * K + j];
-    t.sigH = params[3 * K + j];
-    t.sigT = params[4 * K + j];
-  }
+  for (int j = 0; j < K; ++j) pops[(size_t)j].t = rank1_from_params(params, K, j);
   const std::vector<double> w(W, W + c->p), cv(C, C + c->q);
   if ((rc = meta_xprod_all(c, S, pops, w, cv))) return rc;
   const size_t ld = (size_t)c->p + c->q + 4;

@@ -5,10 +5,8 @@
 //                             what the scale d_j = sqrt(. / (N - 1)) is formed from.
 //   ppls_cvs_finish_kernel    one 64 x 64 block of the lower triangle of one fold matrix per workgroup:
 //                             S_k,ij <- (S_k,ij + (N_k e_ki) e_kj) / (d_i d_j), recentring and
-//                             standardising in one pass.  The layout of ppls_stream_tile_kernel: a
-//                             thread owns one 16-byte column pair of 8 rows of the block, the mirror
-//                             block is written from an LDS copy, a diagonal block takes every entry
-//                             from its lower triangle, padding is written 0.
+//                             standardising in one pass: ppls_symtile_pass (ppls_symtile.h, the walk
+//                             ppls_stream_tile_kernel uses) around that update.
 //   ppls_cvs_select_kernel    working S = the fold matrices but one (or all), added in fold order.
 //   ppls_cvs_rows_kernel      held-out error, pass over the X rows of S_k: a wave per row i forms
 //                             (S_xx W)_i. and (S_xy C)_i. and the same sums of absolute values.
@@ -18,17 +16,13 @@
 #include <hip/hip_runtime.h>
 
 #include "ppls_cvstream.h"
+#include "ppls_symtile.h"
 
 namespace {
 
-constexpr int SB = 64;
-constexpr int CT = 256;
-
-struct CvsCols {
-  int P, p, ldx, yend;   // live columns: [0, p) and [ldx, yend)
-};
-
-__device__ inline bool col_live(const CvsCols& g, int c) { return c < g.p || (c >= g.ldx && c < g.yend); }
+constexpr int SB = PPLS_SYM_SB;
+constexpr int CT = PPLS_SYM_THREADS;
+using CvsCols = PplsSymCols;
 
 // the recentring term, formed in one place: S + (w e_i) e_j with a single rounding of the sum
 __device__ inline double recentred(double s, double we_i, double e_j) { return fma(we_i, e_j, s); }
@@ -39,7 +33,7 @@ __global__ __launch_bounds__(CT) void ppls_cvs_diag_kernel(const double* __restr
   const int j = blockIdx.x * CT + threadIdx.x;
   if (j >= g.P) return;
   double acc = 0.0;
-  if (col_live(g, j)) {
+  if (ppls_sym_col_live(g, j)) {
     const int64_t PP = (int64_t)g.P * g.P;
     for (int k = 0; k < K; ++k) {
       const double ej = e[(int64_t)k * g.P + j];
@@ -49,66 +43,25 @@ __global__ __launch_bounds__(CT) void ppls_cvs_diag_kernel(const double* __restr
   dsum[j] = acc;
 }
 
+// (S_ij + (N_k e_i) e_j) / (d_i d_j); staged vector 0 is the fold's e, 1 is d
+struct CvsFinish {
+  double w;
+  __device__ double2 operator()(double2 v, int r, int c2, const double (&a)[2][SB], const double (&b)[2][SB]) const {
+    const double wa = w * a[0][r];
+    v.x = recentred(v.x, wa, b[0][c2]) / (a[1][r] * b[1][c2]);
+    v.y = recentred(v.y, wa, b[0][c2 + 1]) / (a[1][r] * b[1][c2 + 1]);
+    return v;
+  }
+};
+
 __global__ __launch_bounds__(CT) void ppls_cvs_finish_kernel(double* __restrict__ Sall, CvsCols g,
                                                             const double* __restrict__ eall,
                                                             const double* __restrict__ wall,
                                                             const double* __restrict__ d) {
-  // block t of the lower triangle in row order: (qi, qj), qj <= qi, t = qi (qi + 1) / 2 + qj
-  const int t_blk = blockIdx.x, fold = blockIdx.y;
-  int qi = (int)((sqrt(8.0 * t_blk + 1.0) - 1.0) * 0.5);
-  while ((qi + 1) * (qi + 2) / 2 <= t_blk) ++qi;
-  while (qi * (qi + 1) / 2 > t_blk) --qi;
-  const int qj = t_blk - qi * (qi + 1) / 2;
-  __shared__ double T[SB][SB + 1];
-  __shared__ double ea[SB], eb[SB], da[SB], db[SB];   // e and d over the block's rows / columns
-  const int t = threadIdx.x;
-  const int P = g.P;
-  double* S = Sall + (int64_t)fold * P * P;
-  const double* e = eall + (int64_t)fold * P;
-  const double w = wall[fold];
-  if (t < 2 * SB) {
-    const int c = (t < SB ? qi * SB + t : qj * SB + (t - SB));
-    const double ev = c < P ? e[c] : 0.0, dv = c < P ? d[c] : 1.0;
-    if (t < SB) { ea[t] = ev; da[t] = dv; } else { eb[t - SB] = ev; db[t - SB] = dv; }
-  }
-  __syncthreads();
-  const int c2 = (t & 31) * 2, rb = t >> 5;
-  const int lo = qj * SB + c2;
-  const bool diag = qi == qj;
-#pragma unroll
-  for (int k = 0; k < SB / 8; ++k) {
-    const int r = rb + 8 * k, hi = qi * SB + r;
-    double2 v = make_double2(0.0, 0.0);
-    if (hi < P && lo < P) {   // P is even: lo + 1 < P as well
-      double* sp = S + (int64_t)hi * P + lo;
-      v = *(const double2*)sp;
-      const double wa = w * ea[r];
-      v.x = recentred(v.x, wa, eb[c2]) / (da[r] * db[c2]);
-      v.y = recentred(v.y, wa, eb[c2 + 1]) / (da[r] * db[c2 + 1]);
-      const bool lh = col_live(g, hi);
-      if (!lh || !col_live(g, lo)) v.x = 0.0;
-      if (!lh || !col_live(g, lo + 1)) v.y = 0.0;
-      if (!diag) *(double2*)sp = v;
-    }
-    T[r][c2] = v.x;
-    T[r][c2 + 1] = v.y;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < SB / 8; ++k) {
-    const int r = rb + 8 * k;
-    if (diag) {   // entry (r, c) from the lower triangle: (max, min)
-      const int hi = qi * SB + r;
-      if (hi < P && lo < P) {
-        const double x = c2 <= r ? T[r][c2] : T[c2][r];
-        const double y = c2 + 1 <= r ? T[r][c2 + 1] : T[c2 + 1][r];
-        *(double2*)(S + (int64_t)hi * P + lo) = make_double2(x, y);
-      }
-    } else {      // the mirror block (qj, qi): row qj SB + r, columns qi SB + c2, c2 + 1
-      const int mr = qj * SB + r, mc = qi * SB + c2;
-      if (mr < P && mc < P) *(double2*)(S + (int64_t)mr * P + mc) = make_double2(T[c2][r], T[c2 + 1][r]);
-    }
-  }
+  const int fold = blockIdx.y;
+  const double* const v[2] = {eall + (int64_t)fold * g.P, d};
+  ppls_symtile_pass<2>(Sall + (int64_t)fold * g.P * g.P, g, ppls_sym_block(blockIdx.x), v, {0.0, 1.0},
+                       CvsFinish{wall[fold]});
 }
 
 __global__ __launch_bounds__(CT) void ppls_cvs_select_kernel(const double2* __restrict__ S, int K, int skip, int64_t len2,
@@ -229,10 +182,7 @@ __global__ __launch_bounds__(CT) void ppls_cvs_sse_kernel(const double* __restri
   }
 }
 
-bool shape_ok(int K, int p, int ldx, int q, int ldy) {
-  return K >= 1 && K <= 65535 && p >= 1 && q >= 1 && p <= ldx && q <= ldy && ldx % 2 == 0 && ldy % 2 == 0 &&
-         (int64_t)ldx + ldy < (1 << 30);
-}
+bool shape_ok(int K, int p, int ldx, int q, int ldy) { return K >= 1 && K <= 65535 && ppls_sym_shape_ok(p, ldx, q, ldy); }
 
 }  // namespace
 
@@ -250,9 +200,9 @@ hipError_t ppls_launch_cvs_diag(const double* S, int K, int p, int ldx, int q, i
 hipError_t ppls_launch_cvs_finish(double* S, int K, int p, int ldx, int q, int ldy, const double* e,
                                   const double* w, const double* d, hipStream_t st) {
   if (!S || !e || !w || !d || !shape_ok(K, p, ldx, q, ldy)) return hipErrorInvalidValue;
-  const int P = ldx + ldy, nq = (P + SB - 1) / SB;
+  const int P = ldx + ldy;
   const CvsCols g{P, p, ldx, ldx + q};
-  hipLaunchKernelGGL(ppls_cvs_finish_kernel, dim3(nq * (nq + 1) / 2, K), dim3(CT), 0, st, S, g, e, w, d);
+  hipLaunchKernelGGL(ppls_cvs_finish_kernel, dim3(ppls_sym_blocks(P), K), dim3(CT), 0, st, S, g, e, w, d);
   return hipGetLastError();
 }
 
