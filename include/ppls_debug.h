@@ -45,6 +45,36 @@ int ppls_xprod_stats(ppls_ctx* ctx, const ppls_theta* th, int r, double* stats);
  * the sweep also writes the moments (its waits then drain the DMA ring instead of counting), and mu
  * (nullable) receives this rank's n_local x 2r [mu_T | mu_U], column-major.  Needs resident rows. */
 int ppls_sweep_stats(ppls_ctx* ctx, const ppls_theta* th, int r, int want_mu, double* stats, double* mu);
+/* One production finalize on given statistics, the twin of ppls_sweep_stats and ppls_xprod_stats for
+ * the other half of an EM iteration: on a context with data loaded (p, q, the padded widths, the sums
+ * of squares and N are its own) theta, the host stats ([SX p x r | SY q x r | G 2r x 2r], column-major,
+ * as ppls_finalize_host takes them) and the nullable gram_cur ([W'W | C'C], 2 r^2; NULL: the scalar
+ * block forms them from theta's loadings), vstate_in ([V_W | V_C], 2 r^2; NULL: identity) and xpM (the
+ * M = S B buffer of a cross-product step, (ldx + ldy) x 2r column-major; then the scalar block forms
+ * the Gram B'M itself and stats' G is ignored; r <= 8) are uploaded into the context's own buffers
+ * and the launch goes through the function the EM loop uses, under the current options (polar1,
+ * polar1_kappa, team_rows, exact_gram, vorth): teams, LDS staging and mode bits are production's.
+ * iter is the kernel's logl_index (< 0: no log-likelihood; it also decides whether option "vorth"
+ * re-orthonormalises the carried V on this call).  ldx, ldy: the padded widths the caller sized xpM,
+ * W_next and C_next for (PPLS_E_ARG unless they are the context's).  Out, all nullable: W_next
+ * (ldx x r) and C_next (ldy x r) with their padding rows (rows the launch did not write read NaN);
+ * scalars = [B r | sigT r |
+ * sigE sigF sigH | alpha r | beta r | gamma r | delta r] of the next theta; the moments; loglik[iter];
+ * gram_nxt (2 r^2; 0 where the kernel has none, r > 10); vstate_out (2 r^2); gram_stats (4 r^2: stats'
+ * Gram slot after the launch) and status3 = {the status word, the form that produced W_next, C_next:
+ * 1 Cholesky-QR1, 2 Cholesky-QR2, 3 Householder (after a refused fast form, or r > 10), 4 QR type}.
+ * A status that signals rank deficiency is data here: the call still returns PPLS_OK. */
+int ppls_finalize_stats(ppls_ctx* ctx, const ppls_theta* th, int r, int type, int iter, const double* stats,
+                        const double* gram_cur, const double* vstate_in, const double* xpM, int ldx, int ldy,
+                        double* W_next, double* C_next, double* scalars, ppls_expect* mom, double* loglik,
+                        double* gram_nxt, double* vstate_out, double* gram_stats, int* status3);
+/* The launch geometry of the next finalize with r components and orth type under the current options,
+ * from the function the launcher itself calls: *templated (1: ppls_finalize_kernel<r>, r <= 10; 0: the
+ * runtime-r kernel), *KX, *KY workgroups per polar factor, *staged (members keep their rows of S in
+ * LDS) and *stage_budget, the bytes of LDS the instantiation leaves for that (staged iff r x the
+ * largest member's rows x 8 fits).  All nullable. */
+int ppls_finalize_plan(ppls_ctx* ctx, int r, int type, int* templated, int* KX, int* KY, int* staged,
+                       int64_t* stage_budget);
 /* Shape facts for the roofline: bytes of X and Y one sweep reads (algorithmic), kernel variant. */
 int ppls_sweep_info(ppls_ctx* ctx, int r, int64_t* bytes_per_sweep, int* variant, int* grid);
 /* The sweep kernel instantiation the next EM iteration with r components launches, as text

@@ -108,6 +108,11 @@ SIGNATURES = {
     "ppls_xprod_tile_timing": (ct.c_int, [ct.c_void_p, ct.c_int, _dp]),
     "ppls_xprod_stats": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsTheta), ct.c_int, _dp]),
     "ppls_sweep_stats": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsTheta), ct.c_int, ct.c_int, _dp, _dp]),
+    "ppls_finalize_stats": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsTheta), ct.c_int, ct.c_int, ct.c_int, _dp, _dp, _dp,
+                                       _dp, ct.c_int, ct.c_int, _dp, _dp, _dp, ct.POINTER(PplsExpect), _dp, _dp,
+                                       _dp, _dp, ct.POINTER(ct.c_int)]),
+    "ppls_finalize_plan": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(ct.c_int), ct.POINTER(ct.c_int),
+                                      ct.POINTER(ct.c_int), ct.POINTER(ct.c_int), ct.POINTER(ct.c_int64)]),
     "ppls_xprod_info": (ct.c_int, [ct.c_void_p, ct.c_int, ct.POINTER(ct.c_int), ct.POINTER(ct.c_int64), _dp,
                                    ct.POINTER(ct.c_int)]),
     "ppls_sweep_timing": (ct.c_int, [ct.c_void_p, _dp, ct.POINTER(ct.c_int64), ct.c_int]),

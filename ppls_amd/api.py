@@ -698,6 +698,63 @@ class Context:
         G = out[(self.p + self.q) * r:].reshape(2 * r, 2 * r).T
         return SX, SY, G, mu
 
+    def finalize_plan(self, r, type=0):
+        """The launch geometry of the next finalize with r components under the current options, from
+        the function the launcher itself calls: {templated, KX, KY, staged, stage_budget (bytes of LDS
+        left for staging S; 0 for the runtime-r kernel)}."""
+        t, kx, ky, sg, bud = ct.c_int(), ct.c_int(), ct.c_int(), ct.c_int(), ct.c_int64()
+        self._chk(self._L.ppls_finalize_plan(self.h, int(r), int(type), ct.byref(t), ct.byref(kx), ct.byref(ky),
+                                             ct.byref(sg), ct.byref(bud)))
+        return dict(templated=t.value, KX=kx.value, KY=ky.value, staged=sg.value, stage_budget=bud.value)
+
+    def finalize_stats(self, th: Theta, SX, SY, G, type=0, iter=-1, gram_cur=None, vstate=None, xpM=None):
+        """One production finalize on given statistics (``ppls_finalize_stats``): theta, X'mu_T (p x r),
+        Y'mu_U (q x r), the Gram (2r x 2r), and optionally gram_cur = (W'W, C'C) (None: the scalar block
+        forms them), vstate = (V_W, V_C) (None: identity) and xpM ((ldx + ldy) x 2r: the scalar block
+        forms the Gram B'M itself, r <= 8).  Returns a dict: W, C (with their padding rows), B, sigT,
+        sigE, sigF, sigH, alpha, beta, gamma, delta, moments (Expect), loglik (None when iter < 0),
+        gram_nxt = (W'W, C'C), vstate = (V_W, V_C), gram_stats (the Gram slot after the launch), status,
+        path = (code of W, code of C): 1 Cholesky-QR1, 2 Cholesky-QR2, 3 Householder, 4 QR type."""
+        r = th.r
+        f = lambda a: np.asfortranarray(a, dtype=np.float64).ravel(order="F")   # noqa: E731
+        st = np.ascontiguousarray(np.concatenate([f(SX), f(SY), f(G)]))
+        assert st.size == r * (self.p + self.q) + 4 * r * r
+        pair = lambda ab: None if ab is None else np.ascontiguousarray(np.concatenate([f(ab[0]), f(ab[1])]))  # noqa: E731
+        gc, vs = pair(gram_cur), pair(vstate)
+        assert gc is None or gc.size == 2 * r * r
+        assert vs is None or vs.size == 2 * r * r
+        M = None if xpM is None else np.ascontiguousarray(f(xpM))
+        t = th.struct()
+        ldx, ldy = self._ld(self.p), self._ld(self.q)   # (the library refuses other widths than its own)
+        Wn = np.zeros(ldx * r)
+        Cn = np.zeros(ldy * r)
+        assert M is None or M.size == (Wn.size + Cn.size) * 2
+        sc = np.zeros(6 * r + 3)
+        ex = Expect(r)
+        es = ex.struct()
+        ll = np.zeros(1)
+        gn, vo, gs = np.zeros(2 * r * r), np.zeros(2 * r * r), np.zeros(4 * r * r)
+        st3 = (ct.c_int * 3)()
+        self._chk(self._L.ppls_finalize_stats(self.h, ct.byref(t), r, int(type), int(iter), dptr(st), dptr(gc),
+                                              dptr(vs), dptr(M), ldx, ldy, dptr(Wn), dptr(Cn), dptr(sc), ct.byref(es), dptr(ll),
+                                              dptr(gn), dptr(vo), dptr(gs), st3))
+        ex.pull(es)
+        sq = lambda v: v.reshape(r, r).T   # noqa: E731
+        return dict(W=Wn.reshape(r, -1).T, C=Cn.reshape(r, -1).T, B=sc[:r], sigT=sc[r:2 * r], sigE=sc[2 * r],
+                    sigF=sc[2 * r + 1], sigH=sc[2 * r + 2], alpha=sc[2 * r + 3:3 * r + 3],
+                    beta=sc[3 * r + 3:4 * r + 3], gamma=sc[4 * r + 3:5 * r + 3], delta=sc[5 * r + 3:],
+                    moments=ex, loglik=float(ll[0]) if iter >= 0 else None,
+                    gram_nxt=(sq(gn[:r * r]), sq(gn[r * r:])), vstate=(sq(vo[:r * r]), sq(vo[r * r:])),
+                    gram_stats=gs.reshape(2 * r, 2 * r).T, status=int(st3[0]), path=(int(st3[1]), int(st3[2])))
+
+    @staticmethod
+    def _ld(p):
+        """The padded width of a p-column fp64 matrix under the default options (ld_of in ppls_capi.cpp)."""
+        if p <= 2048:
+            return (p + 1) & ~1
+        al = 4096 if p * 8 >= 16384 else 128
+        return (p * 8 + al - 1) // al * al // 8
+
     def xprod_info(self, r=1):
         """{ready, bytes_per_pass (8 P^2), gram_flops (as computed), rows_per_wave} of the cross-product form."""
         rd, b, f, rw = ct.c_int(), ct.c_int64(), ct.c_double(), ct.c_int()

@@ -347,7 +347,7 @@ int ensure_r(ppls_ctx* c, int r, int max_steps) {
     c->part_ld = (int64_t)r * c->ldx + (int64_t)r * c->ldy + 4 * (int64_t)r * r;
     if ((rc = dalloc(c, &c->stats, (size_t)c->part_ld))) return rc;
     if ((rc = dalloc(c, &c->work, (size_t)2 * (c->p + c->q) * r + 16))) return rc;
-    if ((rc = dalloc(c, &c->status, 1))) return rc;
+    if ((rc = dalloc(c, &c->status, PPLS_STATUS_INTS))) return rc;
     if ((rc = dalloc(c, &c->coefs, (size_t)5 * r))) return rc;
     dfree(c->part);
     dfree(c->Z);
@@ -725,8 +725,10 @@ int sweep(ppls_ctx* c, int r, int slot, bool write_mu, bool mu_only = false) {
   return allreduce(c, c->stats, (size_t)c->part_ld);
 }
 
-int finalize(ppls_ctx* c, int r, int cur, int nxt, int logl_index, int type, int stop_step = 0) {
-  PplsFinalizeArgs f;
+// The arguments of one finalize launch under the context's current options (everything but the
+// pending cross-product Gram, which finalize() below consumes).
+int finalize_args(ppls_ctx* c, int r, int cur, int nxt, int logl_index, int type, int stop_step, PplsFinalizeArgs* out) {
+  PplsFinalizeArgs& f = *out;
   f.stats = c->stats;
   f.ssq = c->ssq;
   f.N = (double)c->n_total;
@@ -767,6 +769,18 @@ int finalize(ppls_ctx* c, int r, int cur, int nxt, int logl_index, int type, int
   f.stop_check = stop_step > 0 ? 1 : 0;
   f.stop_step = stop_step;
   f.atol = c->stop_atol;
+  f.xpM = nullptr;
+  return PPLS_OK;
+}
+
+// own_gram: the scalar block forms W'W, C'C of the current loadings itself (ppls_finalize_stats only;
+// every EM path hands it the Gram the previous finalize or the upload left in gram[cur]).
+int finalize(ppls_ctx* c, int r, int cur, int nxt, int logl_index, int type, int stop_step = 0,
+             bool own_gram = false) {
+  PplsFinalizeArgs f;
+  int rc;
+  if ((rc = finalize_args(c, r, cur, nxt, logl_index, type, stop_step, &f))) return rc;
+  if (own_gram) f.gram_cur = nullptr;
   f.xpM = c->xp_pending_gram ? c->xp_M : nullptr;   // the Gram of a cross-product step, formed here
   c->xp_pending_gram = false;
   HIPCHK(c, ppls_launch_finalize(&f, c->stream));
@@ -1354,8 +1368,9 @@ int host_orth(const double* S, int p, int r, int type, double* out) {
     for (int i = k; i < p; ++i) s2 += A[(size_t)k * p + i] * A[(size_t)k * p + i];
     const double sig = std::sqrt(s2), akk = A[(size_t)k * p + k];
     if (!(sig > 0.0)) return PPLS_E_NUMERIC;
-    const double alpha = akk >= 0.0 ? -sig : sig;
-    vtv[k] = 2.0 * sig * (sig + std::fabs(akk));
+    const bool last = k == p - 1;   // nothing to reflect: R_kk = a_kk (dqrdc2, dlarfg), H_k = I
+    const double alpha = last ? akk : akk >= 0.0 ? -sig : sig;
+    vtv[k] = last ? 0.0 : 2.0 * sig * (sig + std::fabs(akk));
     A[(size_t)k * p + k] = akk - alpha;
     R[k * r + k] = alpha;
     for (int j = k + 1; j < r; ++j) {
@@ -1371,7 +1386,7 @@ int host_orth(const double* S, int p, int r, int type, double* out) {
     for (int j = 0; j < r; ++j) {
       double d = 0.0;
       for (int i = k; i < p; ++i) d += A[(size_t)k * p + i] * E[(size_t)j * p + i];
-      const double f = 2.0 * d / vtv[k];
+      const double f = vtv[k] > 0.0 ? 2.0 * d / vtv[k] : 0.0;
       for (int i = k; i < p; ++i) E[(size_t)j * p + i] -= f * A[(size_t)k * p + i];
     }
   if (type == PPLS_ORTH_QR) {   // sign_e * qr.Q(qr(S)), sign_e = sign(<e_1, S_1>) = sign(R_11) (functions.R:257-259)
@@ -1847,7 +1862,7 @@ int ppls_estep(ppls_ctx* c, const ppls_theta* th, int r, ppls_expect* out) {
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = ensure_r(c, r, 1))) return rc;
   if ((rc = upload_theta(c, th, r, 0))) return rc;
-  HIPCHK(c, hipMemsetAsync(c->status, 0, sizeof(int), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->status, 0, PPLS_STATUS_INTS * sizeof(int), c->stream));
   const bool wm = out && (out->mu_T || out->mu_U);
   if ((rc = sweep(c, r, 0, wm))) return rc;
   if ((rc = finalize(c, r, 0, 1, -1, PPLS_ORTH_SVD))) return rc;
@@ -1866,7 +1881,7 @@ int ppls_em_step(ppls_ctx* c, const ppls_theta* in, int r, int type, ppls_theta*
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = ensure_r(c, r, 1))) return rc;
   if ((rc = upload_theta(c, in, r, 0))) return rc;
-  HIPCHK(c, hipMemsetAsync(c->status, 0, sizeof(int), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->status, 0, PPLS_STATUS_INTS * sizeof(int), c->stream));
   const bool wm = fit && (fit->mu_T || fit->mu_U);
   if ((rc = sweep(c, r, 0, wm))) return rc;
   if ((rc = finalize(c, r, 0, 1, -1, type))) return rc;
@@ -1921,7 +1936,7 @@ int ppls_mstep(ppls_ctx* c, const ppls_expect* fit, int r, int type, ppls_theta*
     HIPCHK(c, hipMemsetAsync(c->stats, 0, sizeof(double) * c->part_ld, c->stream));
   }
   if ((rc = allreduce(c, c->stats, (size_t)c->part_ld))) return rc;
-  HIPCHK(c, hipMemsetAsync(c->status, 0, sizeof(int), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->status, 0, PPLS_STATUS_INTS * sizeof(int), c->stream));
   PplsFinalizeArgs f;
   memset(&f, 0, sizeof f);
   f.stats = c->stats; f.ssq = c->ssq; f.N = (double)c->n_total; f.p = c->p; f.q = c->q; f.r = r;
@@ -1980,7 +1995,7 @@ int ppls_em_run(ppls_ctx* c, ppls_theta* th, int r, int max_steps, double atol, 
     canonicalize(&t0, c->p, c->q, r);
     if ((rc = upload_theta(c, &t0, r, 0))) return rc;
   }
-  HIPCHK(c, hipMemsetAsync(c->status, 0, sizeof(int), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->status, 0, PPLS_STATUS_INTS * sizeof(int), c->stream));
   const bool want_mu = eout && (eout->mu_T || eout->mu_U);
   const bool do_check = !(atol == -INFINITY);   // atol = -Inf: the stop rule never fires
   // statistics from the cross-products S (option xprod; formed here if needed, outside the loop)
@@ -3455,7 +3470,7 @@ int ppls_em_begin(ppls_ctx* c, const ppls_theta* th, int r) {
   ppls_theta t0 = {W.data(), C.data(), B.data(), T.data(), th->sigE, th->sigF, th->sigH};
   canonicalize(&t0, c->p, c->q, r);
   if ((rc = upload_theta(c, &t0, r, 0))) return rc;
-  HIPCHK(c, hipMemsetAsync(c->status, 0, sizeof(int), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->status, 0, PPLS_STATUS_INTS * sizeof(int), c->stream));
   c->em_r = r;
   c->em_cur = 0;
   c->em_iter = 0;
@@ -3663,6 +3678,96 @@ int ppls_sweep_stats(ppls_ctx* c, const ppls_theta* th, int r, int want_mu, doub
     stats[(size_t)r * (c->p + c->q) + e] = st[(size_t)r * (c->ldx + c->ldy) + e];
   if (want_mu && mu && c->n_local > 0)
     HIPCHK(c, hipMemcpy(mu, c->mu, sizeof(double) * (size_t)c->n_local * 2 * r, hipMemcpyDeviceToHost));
+  return PPLS_OK;
+}
+
+int ppls_finalize_plan(ppls_ctx* c, int r, int type, int* templated, int* KX, int* KY, int* staged,
+                       int64_t* stage_budget) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  if (r < 1 || r > PPLS_RMAX) return fail(c, PPLS_E_ARG, "bad r");
+  HIPCHK(c, hipSetDevice(c->device));
+  PplsFinalizeArgs f;
+  int rc;
+  if ((rc = finalize_args(c, r, 0, 1, -1, type, 0, &f))) return rc;
+  PplsFinalizeGeometry g;
+  HIPCHK(c, ppls_finalize_geometry(&f, &g));
+  if (templated) *templated = g.templated;
+  if (KX) *KX = g.KX;
+  if (KY) *KY = g.KY;
+  if (staged) *staged = g.staged;
+  if (stage_budget) *stage_budget = (int64_t)g.stage_budget;
+  return PPLS_OK;
+}
+
+int ppls_finalize_stats(ppls_ctx* c, const ppls_theta* th, int r, int type, int iter, const double* stats,
+                        const double* gram_cur, const double* vstate_in, const double* xpM, int ldx, int ldy,
+                        double* W_next, double* C_next, double* scalars, ppls_expect* mom, double* loglik,
+                        double* gram_nxt, double* vstate_out, double* gram_stats, int* status3) {
+  if (!c || !stats) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  int rc;
+  if ((rc = check_theta(c, th, r))) return rc;
+  if (type != PPLS_ORTH_SVD && type != PPLS_ORTH_QR) return fail(c, PPLS_E_ARG, "type must be SVD (0) or QR (1)");
+  if (xpM && r > PPLS_FUSED_RMAX) return fail(c, PPLS_E_ARG, "the finalize forms the Gram from M for r <= 8 only");
+  if (iter > (1 << 20)) return fail(c, PPLS_E_ARG, "iter too large");
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = ensure_r(c, r, std::max(iter, 0) + 1))) return rc;
+  if ((rc = upload_theta(c, th, r, 0))) return rc;   // W, C, scalars, their Gram; V = I
+  if (ldx != c->ldx || ldy != c->ldy)
+    return fail(c, PPLS_E_ARG, "the padded widths are %d and %d, not %d and %d", c->ldx, c->ldy, ldx, ldy);
+  const int p = c->p, q = c->q, rr = r * r;
+  {
+    std::vector<double> st((size_t)c->part_ld, 0.0);   // padding rows 0, as the statistics steps leave them
+    for (int k = 0; k < r; ++k) {
+      for (int i = 0; i < p; ++i) st[(size_t)k * ldx + i] = stats[(size_t)k * p + i];
+      for (int i = 0; i < q; ++i) st[(size_t)r * ldx + (size_t)k * ldy + i] = stats[(size_t)r * p + (size_t)k * q + i];
+    }
+    for (int e = 0; e < 4 * rr; ++e) st[(size_t)r * (ldx + ldy) + e] = stats[(size_t)r * (p + q) + e];
+    HIPCHK(c, hipMemcpy(c->stats, st.data(), sizeof(double) * st.size(), hipMemcpyHostToDevice));
+  }
+  if (gram_cur) HIPCHK(c, hipMemcpy(c->gram[0], gram_cur, sizeof(double) * 2 * rr, hipMemcpyHostToDevice));
+  if (vstate_in) HIPCHK(c, hipMemcpy(c->vstate, vstate_in, sizeof(double) * 2 * rr, hipMemcpyHostToDevice));
+  if (xpM) {
+    const size_t P = (size_t)ldx + ldy;
+    if (!c->xp_M && (rc = dalloc(c, &c->xp_M, P * 2 * PPLS_RMAX))) return rc;
+    HIPCHK(c, hipMemcpy(c->xp_M, xpM, sizeof(double) * P * 2 * r, hipMemcpyHostToDevice));
+  }
+  // what the launch does not write shows: the next loadings start as NaN, the rest as 0
+  HIPCHK(c, hipMemsetAsync(c->W[1], 0xff, sizeof(double) * (size_t)ldx * r, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->C[1], 0xff, sizeof(double) * (size_t)ldy * r, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->gram[1], 0, sizeof(double) * 2 * rr, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->status, 0, PPLS_STATUS_INTS * sizeof(int), c->stream));
+  c->xp_pending_gram = xpM != nullptr;
+  if ((rc = finalize(c, r, 0, 1, iter, type, 0, gram_cur == nullptr))) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int st3[PPLS_STATUS_INTS];
+  HIPCHK(c, hipMemcpy(st3, c->status, sizeof st3, hipMemcpyDeviceToHost));
+  if (st3[0] == -7 && c->team_bar) HIPCHK(c, hipMemset(c->team_bar, 0, 8 * sizeof(unsigned)));
+  if (status3) memcpy(status3, st3, sizeof st3);
+  if (W_next) HIPCHK(c, hipMemcpy(W_next, c->W[1], sizeof(double) * (size_t)ldx * r, hipMemcpyDeviceToHost));
+  if (C_next) HIPCHK(c, hipMemcpy(C_next, c->C[1], sizeof(double) * (size_t)ldy * r, hipMemcpyDeviceToHost));
+  if (scalars) {   // [B r | sigT r | sigE sigF sigH | alpha r | beta r | gamma r | delta r]
+    PplsScalars s;
+    HIPCHK(c, hipMemcpy(&s, c->sc[1], sizeof s, hipMemcpyDeviceToHost));
+    for (int k = 0; k < r; ++k) {
+      scalars[k] = s.b[k];
+      scalars[r + k] = s.t[k];
+      scalars[2 * r + 3 + k] = s.alpha[k];
+      scalars[3 * r + 3 + k] = s.beta[k];
+      scalars[4 * r + 3 + k] = s.gamma[k];
+      scalars[5 * r + 3 + k] = s.delta[k];
+    }
+    scalars[2 * r] = s.sigE;
+    scalars[2 * r + 1] = s.sigF;
+    scalars[2 * r + 2] = s.sigH;
+  }
+  if ((rc = download_moments(c, r, mom))) return rc;
+  if (loglik && iter >= 0) HIPCHK(c, hipMemcpy(loglik, c->loglik + iter, sizeof(double), hipMemcpyDeviceToHost));
+  if (gram_nxt) HIPCHK(c, hipMemcpy(gram_nxt, c->gram[1], sizeof(double) * 2 * rr, hipMemcpyDeviceToHost));
+  if (vstate_out) HIPCHK(c, hipMemcpy(vstate_out, c->vstate, sizeof(double) * 2 * rr, hipMemcpyDeviceToHost));
+  if (gram_stats)
+    HIPCHK(c, hipMemcpy(gram_stats, c->stats + (size_t)r * (ldx + ldy), sizeof(double) * 4 * rr, hipMemcpyDeviceToHost));
   return PPLS_OK;
 }
 

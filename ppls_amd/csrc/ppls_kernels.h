@@ -62,7 +62,8 @@ struct PplsFinalizeArgs {
   double* loglik;
   int logl_index;        // <0: do not write
   double* work;          // 2 (p+q) r doubles
-  int* status;
+  int* status;           // 3 ints: [0] error word; [1], [2] the form that produced Wn, Cn (1 Cholesky-QR1,
+                         // 2 Cholesky-QR2, 3 Householder, 4 QR type), written by member 0 of each team
   int qr;                // orth type: 0 SVD (polar), 1 QR
   int mode;              // bit0: W/C update (polar), bit1: scalars (moments, loglik, M-step),
                          // bit2: Cholesky-QR1 fast path allowed for well-conditioned X'mu
@@ -83,6 +84,16 @@ struct PplsFinalizeArgs {
                          // (in the slack of the polar blocks) and writes it to stats' Gram slot
 };
 
+// How ppls_launch_finalize launches f (ppls_finalize_geometry: the launcher's own decision).
+struct PplsFinalizeGeometry {
+  int templated;         // 1: ppls_finalize_kernel<r> (r <= 10); 0: the runtime-r kernel (three blocks)
+  int KX, KY;            // workgroups per polar factor
+  int staged;            // the members stage their rows of S in LDS
+  size_t stage_bytes;    // r x (rows of the largest member) x 8
+  size_t stage_budget;   // dynamic LDS the instantiation leaves for it
+};
+
+#define PPLS_STATUS_INTS 3    // PplsFinalizeArgs::status: the error word and the two polar path codes
 #define PPLS_TEAM_ROWS 2048   // rows of S per polar team member (tools/team_rows_ab.py: p = 2000 in one block is 4 us faster than a team of 2; C5 equal at 1024 and 2048)
 #define PPLS_TEAM_MAX 32
 // finalize polar: Cholesky-QR1 (one pass, no second team barrier) when ||R1||_F ||R1^-1||_F <= this x r
@@ -157,6 +168,7 @@ hipError_t ppls_launch_panel_dots(const PplsSweepArgs* a, int dtype_f32, double*
 hipError_t ppls_launch_reduce(const double* part, int ngroups, int64_t ld, int64_t len, double* out,
                               int accumulate, hipStream_t st);
 hipError_t ppls_launch_finalize(const PplsFinalizeArgs* f, hipStream_t st);
+hipError_t ppls_finalize_geometry(const PplsFinalizeArgs* f, PplsFinalizeGeometry* g);
 int64_t ppls_reduce_tmp_len(int ngroups, int64_t len);
 hipError_t ppls_launch_reduce2(const double* part, int ngroups, int64_t ld, int64_t len, double* out,
                                double* tmp, const int* stop, hipStream_t st);

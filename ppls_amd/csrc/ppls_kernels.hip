@@ -1101,8 +1101,11 @@ __device__ __noinline__ void ppls_block_polar(const double* S, int64_t lds, int 
     ppls_block_sum(vals, 1, sh);
     const double sig = sqrt(vals[0]);
     const double akk = A[(int64_t)k * p + k];
-    const double alpha = (akk >= 0.0) ? -sig : sig;
-    const double vtv = 2.0 * sig * (sig + fabs(akk));
+    // (a last row has nothing to reflect: R_kk = a_kk, as LINPACK's dqrdc2 and LAPACK's dlarfg leave
+    // it -- with p = r, type "QR" would otherwise return the last column with the other sign)
+    const bool last = k == p - 1;
+    const double alpha = last ? akk : (akk >= 0.0) ? -sig : sig;
+    const double vtv = last ? 0.0 : 2.0 * sig * (sig + fabs(akk));
     __syncthreads();
     if (tid == 0) {
       A[(int64_t)k * p + k] = akk - alpha;
@@ -1540,19 +1543,24 @@ __device__ void ppls_team_sum(const PplsTeam& tm, int phase, double (&vals)[NG],
 // warm-started from vstate (the previous iteration's V; nullptr = identity).  sm: >= 2 R^2
 // doubles of LDS.  Returns false when S is numerically rank deficient (a Cholesky pivot fails or
 // sigma_min < 1e-14 sigma_max); the caller then falls back to Householder (which reports it).
+// path (nullable) receives 1 (Cholesky-QR1) or 2 (Cholesky-QR2) once the result is accepted.
 // The staged rows live in LDS: accessed through this type the compiler emits ds_read/ds_write
 // (a plain double* to LDS compiles to flat loads and stores, which take the vector-memory path).
 typedef __attribute__((address_space(3))) double ppls_lds_double;
 
 #ifndef PPLS_REG_RMAX
-#define PPLS_REG_RMAX 10   // the polar's Cholesky factors and inverses by one thread in registers up to this R
+// The polar's Cholesky factors and inverses by one thread in registers up to this R.  Not R = 10: with
+// both factorisations in registers (464 VGPRs) a team of K > 1 workgroups lost orthogonality in
+// proportion to kappa(S) (max|Q'Q - I| 5e-13 at kappa 1e4, one block 2e-15; either factorisation in
+// its wave form, or R <= 9, does not: tests/test_gpu_finalize_matrix.py, team2 / team16 at r = 10).
+#define PPLS_REG_RMAX 9
 #endif
 template <int R, int NT>
 __device__ bool ppls_block_polar_fast(const double* __restrict__ S, int64_t lds, int p,
                                       double* __restrict__ out, int64_t ldo, int ldo_rows, double* Sl,
                                       double* sh, double* sm, double* __restrict__ gram_out,
                                       double* __restrict__ vstate, long long* tr, const PplsTeam& tm,
-                                      bool polar1, double kbound, bool reorth) {
+                                      bool polar1, double kbound, bool reorth, int* path) {
   constexpr int NG = R * (R + 1) / 2;
   constexpr int NW = NT / 64;
   constexpr int G = PplsWaveBlk<R>::G, GG = G * G;
@@ -1878,6 +1886,7 @@ __device__ bool ppls_block_polar_fast(const double* __restrict__ S, int64_t lds,
   ppls_stamp(tr, 4);
   if (!ok) return false;
   }   // CholQR2 path
+  if (path && tid == 0) *path = use1 ? 1 : 2;   // diagnostics (member 0): the form that produced out
   // pass 3: out = Q1 P, or S F on the fast path (+ Gram of out)
   double F[R][R];
 #pragma unroll
@@ -2176,6 +2185,8 @@ __device__ void ppls_xp_gram_block(const double* __restrict__ M, const double* _
 
 // Block 0: W_next = orth(S_X); block 1: C_next = orth(S_Y); block 2: scalars (moments, loglik,
 // M-step).  stats = [SX ldx*R][SY ldy*R][G 4R^2];  ssq = {||X||^2, ||Y||^2}.
+// status: 3 ints, [0] the error word, [1] and [2] the form that produced W_next and C_next (written
+// by member 0 of each team: 1 Cholesky-QR1, 2 Cholesky-QR2, 3 Householder, 4 QR type; diagnostics).
 // gram_cur = [W'W | C'C] of the parameters the sweep used (written by the previous finalize or
 // by the host upload); the polar blocks write gram_nxt for the parameters they produce, so the
 // scalar block needs no pass over W and C.  Dynamic LDS (if any) stages S for the polar blocks.
@@ -2239,8 +2250,10 @@ __global__ __launch_bounds__(PPLS_FIN_THREADS) void ppls_finalize_kernel(
                                             sm, gacc, vs, tr, tm, (mode & 4) != 0,
                                             (double)((mode >> 8) & 255),
                                             logl_index < 0 || ((mode >> 16) & 255) <= 1 ||
-                                                logl_index % ((mode >> 16) & 255) == 0)) {
+                                                logl_index % ((mode >> 16) & 255) == 0,
+                                            tm.rank == 0 ? status + 1 + slot : nullptr)) {
       if (tm.rank != 0) return;   // the Householder fallback runs on one block
+      if (tid == 0) status[1 + slot] = qr ? 4 : 3;
       ppls_block_polar(S, ld, rows, R, out, ld, ld, w2, w2 + (int64_t)rows * R, status, qr);
       if (gacc) {
         __syncthreads();
@@ -2318,7 +2331,7 @@ __global__ __launch_bounds__(PPLS_FIN_THREADS) void ppls_finalize_kernel(
   }
 }
 
-// Generic finalize for r > 8 (runtime r; Householder polar).  Block 0: W_next = orth(S_X);
+// Generic finalize for r > 10 (runtime r; Householder polar).  Block 0: W_next = orth(S_X);
 // block 1: C_next = orth(S_Y); block 2: scalars.
 // stats = [SX ldx*r][SY ldy*r][G 4r^2];  ssq = {||X||^2, ||Y||^2}.
 __global__ __launch_bounds__(256) void ppls_finalize_generic_kernel(
@@ -2332,6 +2345,7 @@ __global__ __launch_bounds__(256) void ppls_finalize_generic_kernel(
   const double* SX = stats;
   const double* SY = stats + (int64_t)r * ldx;
   const double* G = SY + (int64_t)r * ldy;
+  if (blockIdx.x < 2 && (mode & 1) && threadIdx.x == 0) status[1 + blockIdx.x] = qr ? 4 : 3;
   if (blockIdx.x == 0) {
     if (mode & 1) ppls_block_polar(SX, ldx, p, r, Wn, ldx, ldx, work, work + (int64_t)p * r, status, qr);
     return;
@@ -2621,21 +2635,45 @@ hipError_t set_dyn_lds(const void* kern, int bytes) {
   return e;
 }
 
+// dynamic LDS left next to the templated finalize's static LDS (160 KB per WG); thread-safe static init
 template <int R>
-hipError_t launch_finalize_t(const PplsFinalizeArgs* f, hipStream_t st) {
-  auto kern = ppls_finalize_kernel<R>;
-  // dynamic LDS left next to the kernel's static LDS (160 KB per WG); thread-safe static init
+size_t finalize_dyn_max() {
   static const size_t dyn_max = []() -> size_t {
     hipFuncAttributes fa;
     if (hipFuncGetAttributes(&fa, (const void*)ppls_finalize_kernel<R>) != hipSuccess) return 0;
     const size_t budget = 160 * 1024 - fa.sharedSizeBytes - 1024;
     return budget < PPLS_FIN_STAGE_MAX ? budget : PPLS_FIN_STAGE_MAX;
   }();
-  if (dyn_max == 0) return hipErrorInvalidDeviceFunction;
-  {
-    const hipError_t e = set_dyn_lds((const void*)kern, (int)dyn_max);
-    if (e != hipSuccess) return e;
+  return dyn_max;
+}
+
+size_t finalize_dyn_max_r(int r) {
+  switch (r) {
+    case 1: return finalize_dyn_max<1>();
+    case 2: return finalize_dyn_max<2>();
+    case 3: return finalize_dyn_max<3>();
+    case 4: return finalize_dyn_max<4>();
+    case 5: return finalize_dyn_max<5>();
+    case 6: return finalize_dyn_max<6>();
+    case 7: return finalize_dyn_max<7>();
+    case 8: return finalize_dyn_max<8>();
+    case 9: return finalize_dyn_max<9>();
+    case 10: return finalize_dyn_max<10>();
+    default: return 0;
   }
+}
+}  // namespace
+
+// The launch geometry of one finalize: the launcher below takes it from here, and
+// ppls_finalize_plan (ppls_debug.h) reports it.
+extern "C" hipError_t ppls_finalize_geometry(const PplsFinalizeArgs* f, PplsFinalizeGeometry* g) {
+  g->templated = f->r >= 1 && f->r <= 10;
+  g->KX = g->KY = 1;
+  g->staged = 0;
+  g->stage_bytes = g->stage_budget = 0;
+  if (!g->templated) return hipSuccess;   // r = 11..16: three blocks, Householder, nothing staged
+  g->stage_budget = finalize_dyn_max_r(f->r);
+  if (g->stage_budget == 0) return hipErrorInvalidDeviceFunction;
   // teams for wide p: one member per PPLS_TEAM_ROWS rows (QR: one block, Householder)
   auto team = [&](int rows) {
     if (f->qr || !f->team_bar) return 1;
@@ -2645,9 +2683,25 @@ hipError_t launch_finalize_t(const PplsFinalizeArgs* f, hipStream_t st) {
   };
   const int KX = team(f->p), KY = team(f->q);
   const int mrows = (f->p + KX - 1) / KX > (f->q + KY - 1) / KY ? (f->p + KX - 1) / KX : (f->q + KY - 1) / KY;
-  const size_t stage = (size_t)R * mrows * sizeof(double);   // a member stages its own rows
-  const int use = stage <= dyn_max && !f->qr;
-  hipLaunchKernelGGL(kern, dim3(KX + KY + 1), dim3(PPLS_FIN_THREADS), use ? stage : 0, st, f->stats, f->ssq,
+  g->KX = KX;
+  g->KY = KY;
+  g->stage_bytes = (size_t)f->r * mrows * sizeof(double);   // a member stages its own rows
+  g->staged = g->stage_bytes <= g->stage_budget && !f->qr;
+  return hipSuccess;
+}
+
+namespace {
+template <int R>
+hipError_t launch_finalize_t(const PplsFinalizeArgs* f, hipStream_t st) {
+  auto kern = ppls_finalize_kernel<R>;
+  PplsFinalizeGeometry g;
+  {
+    hipError_t e = ppls_finalize_geometry(f, &g);
+    if (e == hipSuccess) e = set_dyn_lds((const void*)kern, (int)g.stage_budget);
+    if (e != hipSuccess) return e;
+  }
+  const int use = g.staged, KX = g.KX, KY = g.KY;
+  hipLaunchKernelGGL(kern, dim3(KX + KY + 1), dim3(PPLS_FIN_THREADS), use ? g.stage_bytes : 0, st, f->stats, f->ssq,
                      f->N, f->p, f->q, f->ldx, f->ldy, f->Wc, f->Cc, f->sc_cur, f->Wn, f->Cn, f->sc_nxt, f->mom,
                      f->loglik, f->logl_index, f->work, f->status, f->qr, f->mode, f->gram_cur,
                      f->gram_nxt, f->vstate, use, f->trace, f->stop, f->stop_mirror, f->stop_check,
