@@ -362,6 +362,26 @@ int ppls_set_data_from(ppls_ctx* dst, ppls_ctx* src, const int64_t* rows, int64_
  * the K re-reads of X[-fold, ] per EM step behind :48. */
 int ppls_xprod_downdate(ppls_ctx* dst, ppls_ctx* src, const int64_t* out_rows, int64_t n_out);
 
+/* Resampled cross-products: dst's S becomes sum_i count_i d_i d_i' over src's resident
+ * rows d_i = [x_i y_i] as they stand (scaled in place or not, either storage type) -- the S of the data
+ * with row i repeated count_i times, which is what a bootstrap replicate X[i, ], Y[i, ] with
+ * i = sample(N, replace = TRUE) is -- by the weighted instantiation of the fp64 MFMA Gram (option
+ * "gram_int8" does not apply), with no copy of the rows, all-reduced over src's ranks in the same order
+ * on every rank (src's stream, Gram queue and communicator, as ppls_xprod_downdate).  count: this
+ * rank's n_local non-negative counts (host).  src is left as it was: rows, its own S if formed, options,
+ * an open ppls_em_begin session.  dst ends "streamed" (ppls_stream_info state 2, rows_local 0, no
+ * folds): p, q, the paddings and the scaling record are src's, n_total = sum count over all ranks,
+ * ||X||^2, ||Y||^2 the traces of S_c's diagonal blocks; every fit that reads only S runs on it and
+ * what needs rows is refused as on any streamed context.  A repeated call on the same dst of unchanged
+ * shape reuses dst's S, its device counts and its Gram partials (no allocation per replicate) and ends
+ * an ppls_em_begin session of dst.
+ * PPLS_E_ARG: a negative count on any rank (every rank returns it: the flag rides in the reduction of
+ * sum count), sum count = 0 over all ranks, dst == src, contexts on different devices, count == NULL
+ * with n_local > 0.  PPLS_E_STATE: src without data or streamed.  After such a refusal dst holds what
+ * it held before; an allocation or HIP error leaves dst without data, never with a half-formed S.  A
+ * rank with n_local = 0 takes part in the collectives. */
+int ppls_xprod_resample(ppls_ctx* dst, ppls_ctx* src, const int32_t* count /* host, src's n_local */);
+
 /* predict.PPLS (:12-24): xory 0 ("X") pred = newdata W diag(B) C' (n x q), xory 1 ("Y") pred =
  * newdata C diag(1/B) W' (n x p); W p x k, C q x k column-major, B k, with p, q the shape of the
  * data last loaded into ctx (newdata itself is independent of the resident rows: it is streamed
@@ -414,10 +434,12 @@ int ppls_cv_ppls(ppls_ctx* ctx, int a, int nfolds, const int32_t* fold_of_row /*
  *   - PPLS_E_STATE "the rows were streamed and are not resident", before any work: mu_T / mu_U asked of
  *     ppls_estep, ppls_em_step or ppls_em_run; ppls_mstep (X'mu_T of caller-supplied mu needs the rows);
  *     ppls_scores; ppls_get_data / _rows; ppls_variances; ppls_heldout_sse; ppls_cv_ppls;
- *     ppls_set_data_from / ppls_xprod_downdate with a streamed source; ppls_scale_data;
+ *     ppls_set_data_from / ppls_xprod_downdate / ppls_xprod_resample with a streamed source;
+ *     ppls_scale_data;
  *     ppls_meta_emstep / ppls_meta_ppls (a context streamed with folds fits the multi-population
  *     model with ppls_meta_emstep_stream / ppls_meta_ppls_stream instead); ppls_comm_init and
  *     ppls_set_reducer (set them before ppls_stream_begin); option "dtype";
+ *   - ppls_xprod_resample leaves its dst in this state too (S_c of src's resampled rows, no stream);
  *   - ppls_xprod_release, ppls_set_data, ppls_generate_synthetic and ppls_stream_begin end the state
  *     (after ppls_xprod_release the context has no data).
  * While a stream is open (between begin and end) the context has no data: every fit and data entry

@@ -130,6 +130,14 @@ int ppls_rank1_mu_coefficients(const double* params5, double* coef4);
  * meta_PPLSi: G (p x p, q x q or (p + q) x (p + q) without padding columns, column-major,
  * nullable), *ms = the MFMA kernel's duration. */
 int ppls_gram(ppls_ctx* ctx, int xory, int nsplit, double* G, double* ms);
+/* The weighted instantiation of that kernel alone: G = sum_i count_i d_i d_i' over this rank's rows
+ * (count: n_local host counts >= 0, else PPLS_E_ARG), xory and nsplit as for ppls_gram -- the Gram of
+ * the rows with row i repeated count_i times (ppls_xprod_resample). */
+int ppls_gram_weighted(ppls_ctx* ctx, int xory, int nsplit, const int32_t* count, double* G, double* ms);
+/* Workgroups of the Gram kernel one compute unit holds at once: the unweighted instantiation for the
+ * storage type (f32 0 / 1), which sizes the grid and the split plan, and the weighted one -- equal. */
+int ppls_gram_occupancy(int f32);
+int ppls_gram_occupancy_weighted(int f32);
 /* Inverse of a batch of symmetric positive definite matrices (host A: a x p x p, column-major, stride
  * p^2) as variances.PPLS_simult inverts the observed information: method 1 the hand-written blocked
  * Cholesky + inverse (ppls_linalg.hip), 2 rocSOLVER potrf + potri.  out: the full symmetric inverses;

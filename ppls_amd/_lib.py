@@ -101,6 +101,9 @@ SIGNATURES = {
     "ppls_variances": (ct.c_int, [ct.c_void_p, _dp, _dp, ct.c_double, ct.c_int, ct.c_int, _dp, _dp, _dp, _dp,
                                   _dp, _dp]),
     "ppls_gram": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, _dp, _dp]),
+    "ppls_gram_weighted": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(ct.c_int32), _dp, _dp]),
+    "ppls_gram_occupancy": (ct.c_int, [ct.c_int]),
+    "ppls_gram_occupancy_weighted": (ct.c_int, [ct.c_int]),
     "ppls_spd_inverse": (ct.c_int, [ct.c_void_p, _dp, ct.c_int, ct.c_int, ct.c_int, _dp, ct.POINTER(ct.c_int), _dp]),
     "ppls_xprod_prepare": (ct.c_int, [ct.c_void_p, _dp, _dp]),
     "ppls_xprod_release": (ct.c_int, [ct.c_void_p]),
@@ -138,6 +141,7 @@ SIGNATURES = {
     "ppls_mu_coefficients": (ct.c_int, [ct.POINTER(PplsTheta), ct.c_int, _dp]),
     "ppls_set_data_from": (ct.c_int, [ct.c_void_p, ct.c_void_p, _i64p, ct.c_int64, ct.c_int64]),
     "ppls_xprod_downdate": (ct.c_int, [ct.c_void_p, ct.c_void_p, _i64p, ct.c_int64]),
+    "ppls_xprod_resample": (ct.c_int, [ct.c_void_p, ct.c_void_p, ct.POINTER(ct.c_int32)]),
     "ppls_predict": (ct.c_int, [ct.c_void_p, _dp, _dp, _dp, ct.c_int, ct.c_int, _dp, ct.c_int64, ct.c_int, _dp]),
     "ppls_heldout_sse": (ct.c_int, [ct.c_void_p, _dp, _dp, _dp, ct.c_int, _i64p, ct.c_int64, _dp]),
     "ppls_cv_ppls": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(ct.c_int32), _i64p, ct.c_int,

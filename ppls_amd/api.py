@@ -53,6 +53,7 @@ class Context:
             raise PplsError(rc, f"ppls_ctx_create(device={device}) failed: "
                                 f"{self._L.ppls_strerror(rc).decode()} (is a GPU visible?)")
         self.h = h
+        self.device = int(device)
         self.p = self.q = None
         self.n_local = self.n_total = None
         self.row0 = 0
@@ -583,14 +584,25 @@ class Context:
         tr = (lambda A: None if A is None else np.transpose(A, (0, 2, 1)))
         return W, Bx, tr(V), se, tr(SE), tr(SS)
 
-    def gram(self, xory=0, nsplit=0, want=True):
+    def gram(self, xory=0, nsplit=0, want=True, count=None):
         """D'D (D = X, Y, or xory = 2 the joint [X Y], (p + q) x (p + q)) on the fp64 MFMA Gram kernel
-        alone, this rank's rows -> (G or None, kernel ms)."""
+        alone, this rank's rows -> (G or None, kernel ms).  ``count`` (one integer >= 0 per local row):
+        the weighted instantiation instead, sum_i count_i d_i d_i' (ppls_gram_weighted)."""
         p = self.p + self.q if xory == 2 else self.q if xory else self.p
         G = np.zeros((p, p), order="F") if want else None
         ms = ct.c_double()
-        self._chk(self._L.ppls_gram(self.h, int(xory), int(nsplit), dptr(G), ct.byref(ms)))
+        if count is None:
+            self._chk(self._L.ppls_gram(self.h, int(xory), int(nsplit), dptr(G), ct.byref(ms)))
+        else:
+            cnt, cp = self._counts(count, self.n_local)
+            self._chk(self._L.ppls_gram_weighted(self.h, int(xory), int(nsplit), cp, dptr(G), ct.byref(ms)))
         return G, ms.value
+
+    def gram_occupancy(self, f32=False, weighted=False):
+        """Workgroups of the MFMA Gram kernel per compute unit, for fp64 or fp32 storage: the
+        unweighted instantiation (it sizes the grid and the split plan) or the weighted one."""
+        fn = self._L.ppls_gram_occupancy_weighted if weighted else self._L.ppls_gram_occupancy
+        return int(fn(int(bool(f32))))
 
     def gram_int8(self, which=2, want=True):
         """The Gram by the int8-MFMA Chinese-remainder form alone (which: 0 X'X, 1 Y'Y, 2 the joint
@@ -794,6 +806,30 @@ class Context:
         ``out_rows`` (ppls_xprod_downdate); this context must hold ``src``'s other rows."""
         rows, rp = self._rows(out_rows)
         self._chk(self._L.ppls_xprod_downdate(self.h, src.h, rp, rows.shape[0]))
+
+    @staticmethod
+    def _counts(count, n):
+        a = np.asarray(count)
+        if a.ndim != 1 or a.shape[0] != n:
+            raise ValueError(f"counts: one per local row ({n}), got shape {a.shape}")
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("counts must be integers")
+        if a.size and (a.max() > np.iinfo(np.int32).max or a.min() < np.iinfo(np.int32).min):
+            raise ValueError("counts must fit 32 bits")
+        cnt = np.ascontiguousarray(a, dtype=np.int32)
+        return cnt, (cnt.ctypes.data_as(ct.POINTER(ct.c_int32)) if cnt.size else None)
+
+    def xprod_resample(self, src: "Context", count):
+        """This context's cross-products := sum_i count_i d_i d_i' over ``src``'s resident rows
+        (ppls_xprod_resample): the S of ``src``'s data with row i repeated ``count[i]`` times, formed by
+        the weighted MFMA Gram with no copy of the rows.  This context ends streamed (S, no rows), with
+        ``src``'s shape and scaling record and ``n_total = sum(count)`` over all ranks; ``src`` is left
+        as it was.  Collective over ``src``'s ranks, each passing the counts of its own rows."""
+        cnt, cp = self._counts(count, src.n_local)
+        self._chk(self._L.ppls_xprod_resample(self.h, src.h, cp))
+        self.p, self.q, self.n_local, self.row0 = src.p, src.q, 0, 0
+        self.n_total = self.stream_info()["n_total"]
+        self._stream_folds = None
 
     @staticmethod
     def _fit_arrays(W, C, B):
@@ -1611,6 +1647,137 @@ def PPLS_simult(X, Y, a, EMsteps=10, atol=1e-4, type=("SVD", "QR"), init=None, c
     out["class"] = "PPLS_simult"
     if timings is not None:
         timings.update(init=t1 - t0, loop=time.perf_counter() - t1, init_steps=init_steps)
+    return out
+
+
+# ---------------------------------------------------------------------------- bootstrap
+def bootstrap_counts(N, nboot, rng=None):
+    """``nboot`` bootstrap resamples of ``N`` rows as counts: an ``(nboot, N)`` int32 array whose row b
+    holds how often each row occurs in replicate b -- ``rng.multinomial(N, rep(1/N, N))``, the counts of
+    R's ``sample(N, replace = TRUE)``.  ``rng``: a numpy Generator, or a seed for one."""
+    N, nboot = int(N), int(nboot)
+    if N < 1 or nboot < 0:
+        raise ValueError(f"bootstrap_counts: N = {N}, nboot = {nboot}")
+    rng = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+    pv = np.full(N, 1.0 / N)
+    out = np.empty((nboot, N), dtype=np.int32)
+    for b in range(nboot):
+        out[b] = rng.multinomial(N, pv)
+    return out
+
+
+def align_signs(W, W0):
+    """``W`` with each column's sign set so that it points along the same column of ``W0``:
+    ``W %*% diag(sign(diag(t(W) %*% W0)))``, a zero inner product counting as +1 -- the alignment the
+    reference sketches in its commented mseLoadings (EM_W_multi.R:809-816).  Nothing is reordered."""
+    W = np.array(W, dtype=np.float64, ndmin=2)
+    W0 = np.array(W0, dtype=np.float64, ndmin=2)
+    if W.shape != W0.shape:
+        raise ValueError(f"align_signs: shapes {W.shape} and {W0.shape}")
+    s = np.sign(np.einsum("ij,ij->j", W, W0))
+    s[s == 0] = 1.0
+    return W * s
+
+
+_BOOT_KEYS = ("W", "C", "B", "sigE", "sigF", "sigH", "sigT")
+
+
+def _boot_value(est, key):
+    v = np.asarray(est[key], dtype=np.float64)
+    if key in ("B", "sigT"):      # diagonal matrices in the R list: taken as their diagonals
+        return np.diag(v).copy() if v.ndim == 2 else np.atleast_1d(v).astype(np.float64)
+    if key in ("sigE", "sigF", "sigH"):
+        return np.float64(np.ravel(v)[0])
+    return v
+
+
+def bootstrap_summary(replicates, level=0.95):
+    """``(se, ci)`` of a list of estimate dicts (W, C, B, sigE, sigF, sigH, sigT): per key the standard
+    deviation over the replicates with ``ddof = 1`` and the ``(lo, hi)`` pair of ``np.quantile`` at
+    ``(1 - level) / 2`` and ``(1 + level) / 2``; B and sigT enter as their diagonals."""
+    if len(replicates) < 2:
+        raise ValueError(f"bootstrap: {len(replicates)} replicate(s) succeeded, a standard error needs two")
+    if not 0.0 < level < 1.0:
+        raise ValueError(f"level = {level} outside (0, 1)")
+    se, ci = {}, {}
+    for k in _BOOT_KEYS:
+        A = np.stack([_boot_value(r, k) for r in replicates])
+        se[k] = np.std(A, axis=0, ddof=1)
+        ci[k] = (np.quantile(A, (1.0 - level) / 2.0, axis=0), np.quantile(A, (1.0 + level) / 2.0, axis=0))
+    return se, ci
+
+
+def bootstrap_PPLS_simult(fit, X, Y, nboot=200, EMsteps=100, atol=1e-4, type="SVD", init="fit", level=0.95, rng=None,
+                          ctx=None, work=None, keep=False, counts=None):
+    """Bootstrap standard errors and percentile intervals of a PPLS_simult fit: what users of the
+    reference get from ``i = sample(N, replace = TRUE); PPLS_simult(X[i, ], Y[i, ], ...)`` in a loop,
+    without copying a row.  Replicate b is the data with row i repeated ``counts[b, i]`` times; its
+    cross-products come from the weighted MFMA Gram over the resident rows
+    (``work.xprod_resample(ctx, counts[b])``) and the fit reads only them
+    (``PPLS_simult(None, None, a, EMsteps, atol, type, init=..., ctx=work)``).
+
+    ``fit``: the PPLS_simult list whose estimates are assessed.  ``X``, ``Y``: the data, or
+    ``None, None`` with ``ctx`` holding the rows.  Sharded, every rank calls this with its own rows
+    and passes ``counts``: this rank's columns of one draw all ranks share.  ``work``: the replicate
+    context (default: a new Context on ``ctx``'s device, closed at the end).  ``init = "fit"``
+    warm-starts every replicate from ``fit["estimates"]``; ``init = None`` runs the reference's own
+    default initialiser per replicate, drawing from ``rng``.  ``counts`` (nboot x n_local integers):
+    default ``bootstrap_counts(N, nboot, rng)``.  W and C of each replicate are aligned to the fit's
+    with ``align_signs``, each against its own original; nothing is reordered.
+
+    A warm start with few ``EMsteps`` understates the spread: a replicate that has not converged is
+    still near the estimates it started from.  ``ctx``'s rows are resampled as they stand, with no
+    re-centring or re-scaling per replicate, exactly like ``X[i, ]`` after ``scale()``.
+
+    Returns ``dict(se, ci, nboot, failed, steps[, replicates])``: ``se`` and ``ci`` with the keys W, C,
+    B, sigE, sigF, sigH, sigT (``bootstrap_summary``, over the replicates that succeeded); ``failed``
+    the indices of replicates whose fit raised PplsError (skipped; ValueError if fewer than two
+    succeed); ``steps`` the EM steps per replicate (0 for a failed one); ``replicates`` (``keep=True``)
+    the aligned estimate dicts."""
+    if init is not None and init != "fit":
+        raise ValueError("init must be 'fit' or None")
+    ctx = _ctx_with(X, Y, ctx)
+    est0 = fit["estimates"]
+    W0, C0 = np.array(est0["W"], dtype=np.float64, ndmin=2), np.array(est0["C"], dtype=np.float64, ndmin=2)
+    a = W0.shape[1]
+    rng = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+    if counts is None:
+        if ctx.n_local != ctx.n_total:
+            raise ValueError("sharded rows: pass counts, this rank's columns of a draw all ranks share")
+        counts = bootstrap_counts(ctx.n_total, nboot, rng)
+    counts = np.asarray(counts)
+    if counts.ndim != 2 or counts.shape[1] != ctx.n_local:
+        raise ValueError(f"counts: nboot x {ctx.n_local} (this rank's rows), got shape {counts.shape}")
+    nboot = counts.shape[0]
+    theta0 = None if init is None else dict(W=W0, C=C0, B=est0["B"], sigE=est0["sigE"], sigF=est0["sigF"],
+                                            sigH=est0["sigH"], sigT=est0["sigT"])
+    own = work is None
+    work = Context(ctx.device) if own else work
+    reps, failed, steps = [], [], []
+    try:
+        for b in range(nboot):
+            try:
+                work.xprod_resample(ctx, counts[b])
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")     # "Negative increments of likelihood", per replicate
+                    f = PPLS_simult(None, None, a, EMsteps, atol, type, init=theta0, ctx=work, rng=rng)
+            except PplsError:
+                failed.append(b)
+                steps.append(0)
+                continue
+            e = dict(f["estimates"])
+            e["W"], e["C"] = align_signs(e["W"], W0), align_signs(e["C"], C0)
+            reps.append(e)
+            steps.append(int(len(f["loglik"])))
+    finally:
+        if own:
+            work.close()
+    if len(reps) < 2:
+        raise ValueError(f"bootstrap: {len(reps)} of {nboot} replicates succeeded, a standard error needs two")
+    se, ci = bootstrap_summary(reps, level)
+    out = dict(se=se, ci=ci, nboot=nboot, failed=failed, steps=steps)
+    if keep:
+        out["replicates"] = reps
     return out
 
 

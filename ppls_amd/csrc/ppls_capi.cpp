@@ -228,6 +228,12 @@ struct ppls_ctx {
   std::vector<int*> st_fq;        // per staging buffer and fold: the segment Gram's work queue (device)
   std::vector<int64_t> st_fq_len;
   int st_sel = -1;                // the fold xp_S leaves out (-1: none)
+  // ppls_xprod_resample with this context as dst: the row counts on the device and the weighted Gram's
+  // split partials, kept from call to call (a bootstrap allocates nothing per replicate)
+  int32_t* rs_cnt = nullptr;
+  int64_t rs_cnt_len = 0;
+  double* rs_part = nullptr;
+  int64_t rs_part_len = 0;
 };
 
 namespace {
@@ -838,8 +844,10 @@ int gram_queue(ppls_ctx* c, const GramShape& g, int64_t n, int req, int** q, int
 // G (device, p x p column-major) = the Gram of this rank's n rows: the MFMA kernel into per-item
 // partials, then the finish (sum over splits, mirrored).  ms: the MFMA kernel's duration (HIP
 // events), if not null.  The partials are allocated here and freed, unless the caller passes them
-// (part_in, ppls_gram_part_doubles(g.p, nsplit) doubles; the caller frees them).
-int gram_run(ppls_ctx* c, const GramShape& g, int64_t n, int req, double* G, float* ms, double* part_in = nullptr) {
+// (part_in, ppls_gram_part_doubles(g.p, nsplit) doubles; the caller frees them).  cnt: NULL, or n device
+// counts, one per row: the weighted Gram sum_i cnt[i] d_i d_i' (DESIGN §19).
+int gram_run(ppls_ctx* c, const GramShape& g, int64_t n, int req, double* G, float* ms, double* part_in = nullptr,
+             const int32_t* cnt = nullptr) {
   int rc;
   const int nsplit = gram_nsplit(c, g, n, req);
   double* part = part_in;
@@ -855,7 +863,7 @@ int gram_run(ppls_ctx* c, const GramShape& g, int64_t n, int req, double* G, flo
   }
   if (e == hipSuccess)
     e = ppls_launch_gram_joint(g.X, g.ldx, g.xcols, g.xreal, g.Y, g.ldy, g.ycols, g.yreal, c->dtype, n, g.p, nsplit, part,
-                               q, c->stream);
+                               q, cnt, c->stream);
   if (e == hipSuccess && ms) e = hipEventRecord(e1, c->stream);
   if (e == hipSuccess) e = ppls_launch_gram_finish(part, nsplit, g.p, g.xreal, g.xcols, g.yreal, G, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1475,6 +1483,8 @@ void ppls_ctx_destroy(ppls_ctx* c) {
   dfree(c->team_bar);
   dfree(c->team_part);
   dfree(c->gram_q);
+  dfree(c->rs_cnt);
+  dfree(c->rs_part);
   if (c->stop_mirror) (void)hipHostFree(c->stop_mirror);
   for (auto& e : c->ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (auto& e : c->ev_ar) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -3381,7 +3391,12 @@ int ppls_spd_inverse(ppls_ctx* c, const double* A, int p, int a, int method, dou
 // nsplit equal row splits (0 = the automatic halving splits, as in ppls_variances); G (p x p,
 // column-major) may be NULL.
 // *ms receives the Gram kernel's duration (HIP events on the context stream).
-int ppls_gram(ppls_ctx* c, int xory, int nsplit, double* G, double* ms) {
+}  // extern "C"
+
+namespace {
+
+// ppls_gram (count NULL, weighted false) and ppls_gram_weighted.
+int gram_debug(ppls_ctx* c, int xory, int nsplit, bool weighted, const int32_t* count, double* G, double* ms) {
   if (!c) return PPLS_E_ARG;
   if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
   NEED_ROWS(c);
@@ -3391,10 +3406,21 @@ int ppls_gram(ppls_ctx* c, int xory, int nsplit, double* G, double* ms) {
   const size_t pp = (size_t)g.p * g.p;
   if (c->n_local <= 0) return fail(c, PPLS_E_STATE, "no rows on this rank");
   int rc;
+  struct Counts {
+    int32_t* d = nullptr;
+    ~Counts() { dfree(d); }
+  } cnt;
+  if (weighted) {
+    if (!count) return fail(c, PPLS_E_ARG, "NULL counts for %lld rows", (long long)c->n_local);
+    for (int64_t i = 0; i < c->n_local; ++i)
+      if (count[i] < 0) return fail(c, PPLS_E_ARG, "count %d of row %lld is negative", (int)count[i], (long long)i);
+    if ((rc = dalloc(c, &cnt.d, (size_t)c->n_local))) return rc;
+    HIPCHK(c, hipMemcpy(cnt.d, count, sizeof(int32_t) * c->n_local, hipMemcpyHostToDevice));
+  }
   double* dG = nullptr;
   if ((rc = dalloc(c, &dG, pp))) return rc;
   float t = 0.f;
-  rc = gram_run(c, g, c->n_local, nsplit > 0 ? nsplit : 0, dG, &t);
+  rc = gram_run(c, g, c->n_local, nsplit > 0 ? nsplit : 0, dG, &t, nullptr, cnt.d);
   if (!rc && G) {
     if (xory < 2) {
       if (hipMemcpy(G, dG, sizeof(double) * pp, hipMemcpyDeviceToHost) != hipSuccess)
@@ -3414,6 +3440,18 @@ int ppls_gram(ppls_ctx* c, int xory, int nsplit, double* G, double* ms) {
   dfree(dG);
   if (!rc && ms) *ms = t;
   return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ppls_gram(ppls_ctx* c, int xory, int nsplit, double* G, double* ms) {
+  return gram_debug(c, xory, nsplit, false, nullptr, G, ms);
+}
+
+int ppls_gram_weighted(ppls_ctx* c, int xory, int nsplit, const int32_t* count, double* G, double* ms) {
+  return gram_debug(c, xory, nsplit, true, count, G, ms);
 }
 
 // scores.PPLS (EM_W_multi.R:411-420): T = X W, U = Y C (local rows, column-major n_local x k) in
@@ -4643,7 +4681,7 @@ int stream_merge_rows(ppls_ctx* c, double* Xs, double* Ys, int64_t n, double* S,
   } else if ((rc = gram_queue(c, g, n, 0, &q, 0, s))) {
     return stream_fail(c, rc);
   }
-  STREAMCHK(c, ppls_launch_gram_joint(Xs, c->ldx, c->ldx, c->p, Ys, c->ldy, c->ldy, c->q, 0, n, P, nsplit, c->st_part, q, s));
+  STREAMCHK(c, ppls_launch_gram_joint(Xs, c->ldx, c->ldx, c->p, Ys, c->ldy, c->ldy, c->q, 0, n, P, nsplit, c->st_part, q, nullptr, s));
   STREAMCHK(c, ppls_launch_stream_merge(S, c->p, c->ldx, c->q, c->ldy, c->st_part, nsplit,
                                         c->st_center ? delta : nullptr, N * nc / (N + nc), s));
   return PPLS_OK;
@@ -5175,6 +5213,181 @@ int ppls_stream_end(ppls_ctx* c) {
   c->xp_active = false;
   c->em_active = false;
   c->have_data = true;
+  return PPLS_OK;
+}
+
+}  // extern "C"
+
+// ============================================================================ resampled cross-products
+// A bootstrap replicate is the resident rows with row i repeated count_i times, so its cross-products
+// are S_c = sum_i count_i d_i d_i': the weighted instantiation of the MFMA Gram over src's rows, no copy
+// of them, into a context that holds S_c and no rows -- the streamed state.
+namespace {
+
+// dst without data after an allocation or HIP error past the point of no return: never a half-formed S.
+int resample_drop(ppls_ctx* dst, int rc) {
+  if (!dst->st_state) dst->st_state = 2;   // (xprod_free then clears have_data and any EM session)
+  xprod_free(dst);
+  dst->have_data = false;
+  return rc;
+}
+
+// dst takes src's shape and S (a P x P buffer it owns from here) as a streamed context with no rows.
+int resample_adopt(ppls_ctx* dst, const ppls_ctx* src, double* S) {
+  int rc;
+  dst->dtype = src->dtype;   // the paddings follow the storage type and the padding option (ld_of)
+  dst->ldpad = src->ldpad;
+  if ((rc = alloc_data(dst, 0, src->p, src->q, 0))) { dfree(S); return rc; }
+  xprod_free(dst);
+  if (dst->ldx != src->ldx || dst->ldy != src->ldy) {
+    dfree(S);
+    return fail(dst, PPLS_E_STATE, "resample: paddings %d, %d differ from the source's %d, %d", dst->ldx, dst->ldy, src->ldx,
+                src->ldy);
+  }
+  dst->xp_S = S;
+  dst->st_state = 2;
+  dst->st_rows = dst->st_chunks = 0;
+  dst->st_center = dst->st_scale = 0;
+  dst->n_local = 0;
+  return PPLS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ppls_xprod_resample(ppls_ctx* dst, ppls_ctx* src, const int32_t* count) {
+  if (!dst || !src) return dst ? fail(dst, PPLS_E_ARG, "NULL source context") : PPLS_E_ARG;
+  if (dst == src) return fail(dst, PPLS_E_ARG, "source and destination are the same context");
+  if (!src->have_data) return fail(dst, PPLS_E_STATE, "the source context has no data");
+  if (src->st_state == 2) return fail(dst, PPLS_E_STATE, PPLS_STREAMED_MSG);
+  if (dst->device != src->device)
+    return fail(dst, PPLS_E_ARG, "contexts on different devices (%d, %d)", dst->device, src->device);
+  HIPCHK(dst, hipSetDevice(src->device));
+  int rc;
+  const bool coll = collective(src);
+  const int64_t n = src->n_local;
+  const int P = src->ldx + src->ldy;
+  const size_t PP = (size_t)P * P;
+  // this rank's verdict on its counts joins the agreement below (with sum count), so ranks return together
+  int bad = PPLS_OK;
+  double sum = 0.0;
+  if (n > 0 && !count) {
+    bad = fail(dst, PPLS_E_ARG, "NULL counts for %lld local rows", (long long)n);
+  } else {
+    for (int64_t i = 0; i < n; ++i) {
+      if (count[i] < 0) {
+        bad = fail(dst, PPLS_E_ARG, "count %d of local row %lld is negative", (int)count[i], (long long)i);
+        break;
+      }
+      sum += (double)count[i];
+    }
+  }
+  const std::string bad_err = dst->err;
+  if (bad && !coll) return bad;
+  // every allocation of the call before the ranks agree (as xprod_setup does for S): a new S only when
+  // dst does not already hold resampled (or plainly streamed) cross-products of this shape, the kept
+  // counts and partials only when they have to grow, the Gram's queue on src (kept there per shape)
+  const bool reuse = dst->have_data && dst->st_state == 2 && dst->st_nfolds == 0 && dst->xp_ready && dst->xp_S &&
+                     dst->p == src->p && dst->q == src->q && dst->ldx == src->ldx && dst->ldy == src->ldy;
+  const GramShape g = gram_shape(src, true, 0);
+  const int64_t nrun = bad ? 0 : n;
+  double* Snew = nullptr;
+  int rc_alloc = reuse ? PPLS_OK : dalloc(dst, &Snew, PP);
+  if (!rc_alloc && nrun > 0) {
+    const int64_t need = ppls_gram_part_doubles(P, gram_nsplit(src, g, nrun, 0));
+    if (dst->rs_part_len < need) {
+      dst->rs_part_len = 0;
+      if (!(rc_alloc = dalloc(dst, &dst->rs_part, (size_t)need))) dst->rs_part_len = need;
+    }
+    if (!rc_alloc && dst->rs_cnt_len < nrun) {
+      dst->rs_cnt_len = 0;
+      if (!(rc_alloc = dalloc(dst, &dst->rs_cnt, (size_t)nrun))) dst->rs_cnt_len = nrun;
+    }
+    if (!rc_alloc) {
+      int* q = nullptr;
+      if ((rc_alloc = gram_queue(src, g, nrun, 0, &q))) dst->err = src->err;
+    }
+  }
+  double f[3] = {rc_alloc ? 1.0 : 0.0, bad ? 1.0 : 0.0, bad ? 0.0 : sum};
+  if (coll && (rc = agree(src, f, 3))) {
+    dfree(Snew);
+    dst->err = src->err;
+    return rc;
+  }
+  if (f[0] > 0.0) {
+    dfree(Snew);
+    if (!rc_alloc) rc_alloc = fail(dst, PPLS_E_NOMEM, "resampled S: %d other rank(s) could not allocate it", (int)f[0]);
+    return resample_drop(dst, rc_alloc);
+  }
+  if (f[1] > 0.0) {
+    dfree(Snew);
+    if (bad) dst->err = bad_err;
+    return bad ? bad : fail(dst, PPLS_E_ARG, "resampled S: %d other rank(s) passed bad counts", (int)f[1]);
+  }
+  if (!(f[2] >= 1.0)) {
+    dfree(Snew);
+    return fail(dst, PPLS_E_ARG, "the counts sum to 0 over all ranks: a replicate needs rows");
+  }
+  // From here dst ends streamed on S_c, or without data.  Its own pending work first (an EM session may
+  // still read the S that is about to be overwritten); the Gram then runs on src's stream, behind
+  // whatever src has queued, and the sum over ranks goes through src's communicator.
+  int local = hipStreamSynchronize(dst->stream) == hipSuccess ? PPLS_OK : fail(dst, PPLS_E_HIP, "resample: dst's stream failed");
+  if (!reuse) {
+    // (alloc_data / xprod_free inside would not know the kept buffers: they are dst's, not the data's)
+    if (!local) local = resample_adopt(dst, src, Snew);
+    else dfree(Snew);
+    Snew = nullptr;
+  } else {
+    meta_xp_free(dst);
+    dst->st_rows = dst->st_chunks = 0;
+  }
+  dst->have_data = false;
+  dst->em_active = false;
+  dst->xp_active = false;
+  dst->xp_pending_gram = false;
+  if (!local && n > 0) {
+    hipError_t e = hipMemcpyAsync(dst->rs_cnt, count, sizeof(int32_t) * n, hipMemcpyHostToDevice, src->stream);
+    if (e != hipSuccess) local = fail(dst, PPLS_E_HIP, "resample: upload of the counts: %s", hipGetErrorString(e));
+    // always the fp64 MFMA Gram (the int8 form does not take weights); src's record of how its own S was
+    // formed (oz_used) is not touched
+    if (!local && (local = gram_run(src, g, n, 0, dst->xp_S, nullptr, dst->rs_part, dst->rs_cnt))) dst->err = src->err;
+  } else if (!local) {
+    if (hipMemsetAsync(dst->xp_S, 0, sizeof(double) * PP, src->stream) != hipSuccess)
+      local = fail(dst, PPLS_E_HIP, "resample: zeroing S failed");
+  }
+  if (coll) {   // nobody enters the all-reduce of S_c alone
+    double b = local ? 1.0 : 0.0;
+    if ((rc = agree(src, &b, 1))) {
+      dst->err = src->err;
+      return resample_drop(dst, rc);
+    }
+    if (b > 0.0 && !local) local = fail(dst, PPLS_E_HIP, "resampled S failed on %d other rank(s)", (int)b);
+  }
+  if (local) return resample_drop(dst, local);
+  if ((rc = allreduce(src, dst->xp_S, PP))) {
+    dst->err = src->err;
+    return resample_drop(dst, rc);
+  }
+  // ||X||^2, ||Y||^2: the traces of S_c's diagonal blocks, in column order (as fold_select takes them)
+  std::vector<double> diag;
+  double s2[2];
+  hipError_t e = hipStreamSynchronize(src->stream);
+  if (e == hipSuccess) e = diag_to_host(dst->xp_S, P, diag);
+  if (e == hipSuccess) {
+    diag_traces(dst, diag, s2);
+    e = hipMemcpy(dst->ssq, s2, sizeof s2, hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) return resample_drop(dst, fail(dst, PPLS_E_HIP, "resample: traces of S: %s", hipGetErrorString(e)));
+  dst->ssq_host[0] = s2[0];
+  dst->ssq_host[1] = s2[1];
+  dst->n_total = (int64_t)f[2];
+  dst->sc_center = src->sc_center;   // the rows keep the transform they carry in src
+  dst->sc_scale = src->sc_scale;
+  dst->mem_free_min = src->mem_free_min;
+  dst->xp_ready = true;
+  dst->xp_explicit = true;
+  dst->have_data = true;
   return PPLS_OK;
 }
 

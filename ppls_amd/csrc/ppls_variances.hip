@@ -144,10 +144,15 @@ struct PplsGramOps<float> {
 // garbage only meets its own output rows / columns, which the finish never reads, so the steady
 // state needs no masks; rows past the split's end are zeros (the one partial k-step).
 // Output: part[item][a][b], a quadrant-local row, b column (64 x 64 doubles per item).
-template <typename T>
+// WEIGHTED: sum_i cnt[i] d_i d_i' -- the lane that feeds row r0 + kr + 4 step loads that
+// row's count with the step's operands, into the same ring, and multiplies its four A operands by it
+// (B stays as loaded: each term is (c x_a) x_b); everything else, the item's sum order included, is
+// the unweighted form's.
+template <typename T, bool WEIGHTED>
 __device__ __forceinline__ void ppls_gram_wave_item(const T* __restrict__ X, int ldx, int xcols, const T* __restrict__ Y,
                                                     int ldy, int ycols, int p, int ntiles, int it,
-                                                    const int64_t* __restrict__ bounds, double* __restrict__ part) {
+                                                    const int64_t* __restrict__ bounds, const int32_t* __restrict__ cnt,
+                                                    double* __restrict__ part) {
   typedef double d4 __attribute__((ext_vector_type(4)));
   typedef PplsGramOps<T> Op;
   constexpr int D = PPLS_GRING;
@@ -175,9 +180,18 @@ __device__ __forceinline__ void ppls_gram_wave_item(const T* __restrict__ X, int
     base(J * PPLS_GT + (quad & 1) * PPLS_GQ + Op::lcol(l, li), &pb[l], &sb[l]);
   }
   Op ra[D], rb[D];
+  int32_t rw[D];   // WEIGHTED: the lane's row count of each k-step in flight (kept as loaded, converted at use)
+  // (a wave-uniform base that advances with the steps plus the lane's constant row kr: the address costs
+  // the ring no 64-bit per-lane pointer -- the fp64 form sits at the 256-VGPR limit of 2 waves per SIMD)
+  const int32_t* pw = nullptr;
+  if constexpr (WEIGHTED) pw = cnt + r0;
   auto ld_step = [&](int d) {
     ra[d].load(pa);
     rb[d].load(pb);
+    if constexpr (WEIGHTED) {
+      rw[d] = pw[kr];
+      pw += 4;
+    }
 #pragma unroll
     for (int l = 0; l < Op::NL; ++l) {
       pa[l] += sa[l];
@@ -189,10 +203,16 @@ __device__ __forceinline__ void ppls_gram_wave_item(const T* __restrict__ X, int
   for (int m = 0; m < 4; ++m)
 #pragma unroll
     for (int q = 0; q < 4; ++q) acc[m][q] = d4{0.0, 0.0, 0.0, 0.0};
-  auto mma = [&](const Op& A, const Op& B) {
+  auto mma = [&](const Op& A, const Op& B, int32_t c) {
     double a[4], b[4];
+    if constexpr (WEIGHTED) {
+      const double w = (double)c;
 #pragma unroll
-    for (int m = 0; m < 4; ++m) a[m] = A.op(m);
+      for (int m = 0; m < 4; ++m) a[m] = A.op(m) * w;
+    } else {
+#pragma unroll
+      for (int m = 0; m < 4; ++m) a[m] = A.op(m);
+    }
 #pragma unroll
     for (int q = 0; q < 4; ++q) b[q] = B.op(q);
 #pragma unroll
@@ -213,18 +233,18 @@ __device__ __forceinline__ void ppls_gram_wave_item(const T* __restrict__ X, int
     for (; kk + 2 * D <= nfull; kk += D) {
 #pragma unroll
       for (int d = 0; d < D; ++d) {
-        mma(ra[d], rb[d]);
+        mma(ra[d], rb[d], rw[d]);
         ld_step(d);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
 #pragma unroll
-    for (int d = 0; d < D; ++d) mma(ra[d], rb[d]);
+    for (int d = 0; d < D; ++d) mma(ra[d], rb[d], rw[d]);
     kk += D;
   }
   for (; kk < nfull; ++kk) {   // the last < D whole k-steps
     ld_step(0);
-    mma(ra[0], rb[0]);
+    mma(ra[0], rb[0], rw[0]);
   }
   if (r1 - r0 > 4 * nfull) {   // a partial last k-step: rows past r1 are zeros
     Op A, B;
@@ -233,11 +253,13 @@ __device__ __forceinline__ void ppls_gram_wave_item(const T* __restrict__ X, int
       A.v[l] = {};
       B.v[l] = {};
     }
-    if (r0 + 4 * nfull + kr < r1) {
+    int32_t c = 0;
+    if (r0 + 4 * nfull + kr < r1) {   // (also the only rows whose count is read: none past r1)
       A.load(pa);
       B.load(pb);
+      if constexpr (WEIGHTED) c = pw[kr];
     }
-    mma(A, B);
+    mma(A, B, c);
   }
   double* out = part + (int64_t)it * (PPLS_GQ * PPLS_GQ);
 #pragma unroll
@@ -253,11 +275,13 @@ __device__ __forceinline__ void ppls_gram_wave_item(const T* __restrict__ X, int
 
 // Persistent: one workgroup per resident slot (4 independent waves); every wave takes work items
 // from the queues (ppls_gram_next) until they are empty.  Each item's sums depend only on the item,
-// so the result is the same bit for bit whichever wave runs it.
-template <typename T>
+// so the result is the same bit for bit whichever wave runs it.  rowcnt: one count per local row
+// (WEIGHTED; unread otherwise).
+template <typename T, bool WEIGHTED>
 __global__ __launch_bounds__(256, 2) void ppls_gram_mfma_kernel(const T* __restrict__ X, int ldx, int xcols,
                                                                  const T* __restrict__ Y, int ldy, int ycols, int p,
                                                                  int ntiles, int nsplit, int* __restrict__ queue,
+                                                                 const int32_t* __restrict__ rowcnt,
                                                                  double* __restrict__ part) {
   // queue = [qoff (9) | counters (8, zeroed before the launch) | pad | row bounds (nsplit + 1 int64) | items]
   const int* qoff = queue;
@@ -270,7 +294,7 @@ __global__ __launch_bounds__(256, 2) void ppls_gram_mfma_kernel(const T* __restr
     if (lane == 0) it = ppls_gram_next(cnt, qoff, items, g);
     it = __builtin_amdgcn_readfirstlane(it);
     if (it < 0) return;
-    ppls_gram_wave_item<T>(X, ldx, xcols, Y, ldy, ycols, p, ntiles, it, bounds, part);
+    ppls_gram_wave_item<T, WEIGHTED>(X, ldx, xcols, Y, ldy, ycols, p, ntiles, it, bounds, rowcnt, part);
   }
 }
 
@@ -409,8 +433,15 @@ int ppls_gram_tiles(int p) {
 
 int ppls_gram_occupancy(int f32) {
   int occ = 0;
-  hipError_t e = f32 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ppls_gram_mfma_kernel<float>, 256, 0)
-                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ppls_gram_mfma_kernel<double>, 256, 0);
+  hipError_t e = f32 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ppls_gram_mfma_kernel<float, false>, 256, 0)
+                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ppls_gram_mfma_kernel<double, false>, 256, 0);
+  return e == hipSuccess && occ > 0 ? occ : 1;
+}
+
+int ppls_gram_occupancy_weighted(int f32) {
+  int occ = 0;
+  hipError_t e = f32 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ppls_gram_mfma_kernel<float, true>, 256, 0)
+                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ppls_gram_mfma_kernel<double, true>, 256, 0);
   return e == hipSuccess && occ > 0 ? occ : 1;
 }
 
@@ -500,7 +531,7 @@ hipError_t ppls_gram_queue_prepare(int* queue, int p, int xreal, int xcols, int 
 
 hipError_t ppls_launch_gram_joint(const void* X, int ldx, int xcols, int xreal, const void* Y, int ldy, int ycols,
                                   int yreal, int f32, int64_t n, int p, int nsplit, double* part, int* queue,
-                                  hipStream_t st) {
+                                  const int32_t* cnt, hipStream_t st) {
   if (n <= 0 || p <= 0 || nsplit < 1 || !queue || xcols + ycols < 1 || xreal > xcols || yreal > ycols)
     return hipErrorInvalidValue;
   const int ev = f32 ? 4 : 2;
@@ -512,18 +543,27 @@ hipError_t ppls_launch_gram_joint(const void* X, int ldx, int xcols, int xreal, 
   const int grid = (cus * ppls_gram_occupancy(f32) + 7) / 8 * 8;
   hipError_t e = hipMemsetAsync(queue + 9, 0, 8 * sizeof(int), st);   // the queue counters
   if (e != hipSuccess) return e;
-  if (f32)
-    hipLaunchKernelGGL(ppls_gram_mfma_kernel<float>, dim3((unsigned)grid), dim3(256), 0, st, (const float*)X, ldx, xcols,
-                       (const float*)Y, ldy, ycols, p, ntiles, nsplit, queue, part);
+  // cnt (n device counts, one per row): the weighted instantiation; the grid is the unweighted one's
+  // (the occupancies are equal, tests/test_gpu_resample.py), so are the queues and the split plan
+  const dim3 gd((unsigned)grid), bd(256);
+  if (f32 && cnt)
+    hipLaunchKernelGGL((ppls_gram_mfma_kernel<float, true>), gd, bd, 0, st, (const float*)X, ldx, xcols, (const float*)Y,
+                       ldy, ycols, p, ntiles, nsplit, queue, cnt, part);
+  else if (f32)
+    hipLaunchKernelGGL((ppls_gram_mfma_kernel<float, false>), gd, bd, 0, st, (const float*)X, ldx, xcols, (const float*)Y,
+                       ldy, ycols, p, ntiles, nsplit, queue, cnt, part);
+  else if (cnt)
+    hipLaunchKernelGGL((ppls_gram_mfma_kernel<double, true>), gd, bd, 0, st, (const double*)X, ldx, xcols,
+                       (const double*)Y, ldy, ycols, p, ntiles, nsplit, queue, cnt, part);
   else
-    hipLaunchKernelGGL(ppls_gram_mfma_kernel<double>, dim3((unsigned)grid), dim3(256), 0, st, (const double*)X, ldx, xcols,
-                       (const double*)Y, ldy, ycols, p, ntiles, nsplit, queue, part);
+    hipLaunchKernelGGL((ppls_gram_mfma_kernel<double, false>), gd, bd, 0, st, (const double*)X, ldx, xcols,
+                       (const double*)Y, ldy, ycols, p, ntiles, nsplit, queue, cnt, part);
   return hipGetLastError();
 }
 
 hipError_t ppls_launch_gram(const void* X, int f32, int64_t n, int ld, int p, int nsplit, double* part, int* queue,
                             hipStream_t st) {
-  return ppls_launch_gram_joint(X, ld, ld, p, nullptr, 0, 0, 0, f32, n, p, nsplit, part, queue, st);
+  return ppls_launch_gram_joint(X, ld, ld, p, nullptr, 0, 0, 0, f32, n, p, nsplit, part, queue, nullptr, st);
 }
 
 hipError_t ppls_launch_gram_finish(const double* part, int nsplit, int p, int xreal, int xcols, int yreal, double* G,

@@ -1,6 +1,7 @@
 """Summarise tools/pmc_compute.sh: per kernel, counter-based MFMA / VALU utilisation and fp64 rates.
 
     python tools/pmc_compute_summary.py <tag> <workload> <kernel_substring,...> [--trace <stats.csv>]
+    (separate the substrings with ";" instead when they contain commas)
 
 Definitions (gfx950, 256 CUs x 4 SIMDs; rocprofv3 sums a dispatch's counters over XCDs/SEs):
   cycles      = GRBM_GUI_ACTIVE / 8                (the kernel's duration in GPU cycles, per XCD)
@@ -65,7 +66,8 @@ def main():
         with open(path) as f:
             ordinals[sub] = set(json.load(f)["ordinals"]["timed"])
         del args[i:i + 2]
-    tag, workload, subs = args[0], args[1], args[2].split(",")
+    # (";" separates substrings that hold commas themselves, e.g. template argument lists)
+    tag, workload, subs = args[0], args[1], args[2].split(";" if ";" in args[2] else ",")
     base = os.path.join(ROOT, "gpurun_out", f"pmcc_{tag}")
     out = dict(workload=workload, kernels={}, definitions=__doc__.split("Definitions")[1].split("Writes")[0].strip(),
                source=f"tools/pmc_compute.sh {tag} (rocprofv3 --pmc, 2 passes, separate runs)",
