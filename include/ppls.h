@@ -326,6 +326,26 @@ int ppls_variances(ppls_ctx* ctx, const double* mu, const double* Cdiag, double 
                    double* W, double* B_exp, double* varMatrix, double* SSt_exp, double* SSt_star,
                    double* seLoad);
 
+/* The same list from the cross-products S = [X Y]'[X Y] alone, for contexts that hold no rows: the
+ * rows enter :830-860 only through N Ctt_ii X'X (S's diagonal block), Cxt = X'mu_T and
+ * W = orth(X'mu_T) (the statistic and the polar factor of one cross-product EM step at th) and
+ * crossprod(mu_T[, i]) (a quadratic form in that step's Gram of [XW YC]).  th: the theta at which the
+ * reference's Expectations are taken (fit$estimates); r: its components; xory 0 "X" / 1 "Y" (th->sigE
+ * for both, like the reference).  Outputs as ppls_variances (W p x r, B_exp r, varMatrix / SSt_exp /
+ * SSt_star r consecutive column-major p x p, seLoad p x r) plus Cdiag (r: the Ctt_ii or Cuu_ii used);
+ * Cdiag, varMatrix, SSt_exp and SSt_star are nullable.  Option "var_chol" as in ppls_variances: a
+ * matrix that is not positive definite sends the batch to LU.
+ * Works on every context that holds S: streamed (a fold stream: the working S and N of the current
+ * ppls_stream_select), the destination of ppls_xprod_resample, resident with S formed.  Resident
+ * without S: S is formed as by ppls_xprod_prepare and kept -- the call's only collective; with S
+ * present no rank communicates, and every rank returns the same bits.
+ * PPLS_E_STATE: no data, or a stream is open.  PPLS_E_ARG: th, W, B_exp or seLoad NULL, xory not 0 or
+ * 1, r outside [1, 16] or above the block's columns.  PPLS_E_NUMERIC: a rank-deficient orth or an
+ * exactly singular matrix (ppls_variances' messages).  A refused call leaves the context's data and S
+ * as they were (like every call that stages a theta it ends an ppls_em_begin session). */
+int ppls_variances_xprod(ppls_ctx* ctx, const ppls_theta* th, int r, int xory, double* W, double* Cdiag,
+                         double* B_exp, double* varMatrix, double* SSt_exp, double* SSt_star, double* seLoad);
+
 /* ---- cross-product form (option "xprod") ----------------------------------------------------
  * Form S = [X Y]'[X Y] now (*ms = the MFMA Gram kernel time, *total_ms = with the all-reduce and
  * allocation; both nullable) -- otherwise the first run that reads S forms it.  Collective when the
@@ -433,7 +453,8 @@ int ppls_cv_ppls(ppls_ctx* ctx, int a, int nfolds, const int32_t* fold_of_row /*
  *     context would recompute a cancelled one from the rows);
  *   - PPLS_E_STATE "the rows were streamed and are not resident", before any work: mu_T / mu_U asked of
  *     ppls_estep, ppls_em_step or ppls_em_run; ppls_mstep (X'mu_T of caller-supplied mu needs the rows);
- *     ppls_scores; ppls_get_data / _rows; ppls_variances; ppls_heldout_sse; ppls_cv_ppls;
+ *     ppls_scores; ppls_get_data / _rows; ppls_variances (whose mu are rows: the standard errors of a
+ *     streamed context come from ppls_variances_xprod); ppls_heldout_sse; ppls_cv_ppls;
  *     ppls_set_data_from / ppls_xprod_downdate / ppls_xprod_resample with a streamed source;
  *     ppls_scale_data;
  *     ppls_meta_emstep / ppls_meta_ppls (a context streamed with folds fits the multi-population

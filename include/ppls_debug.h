@@ -182,6 +182,24 @@ int ppls_scale_timing(ppls_ctx* ctx, double* ms3, double* bytes3);
  * *n the fold's rows over all ranks. */
 int ppls_stream_fold_get(ppls_ctx* ctx, int fold, double* S, double* mean, int64_t* n);
 
+/* ppls_variances_xprod's information kernel alone on host inputs, uploaded and downloaded around one
+ * launch: S (row-major P x P; only the p x p block at (off, off) is read, apart from the padding
+ * column next to an odd block, whose value is dropped; P and off even, off + p (+ 1 for odd p) <= P),
+ * a <= 16 components with cxt and w (p x a, column-major) and the scalars ctt, k1, k2, bstar (a
+ * each); the kernel divides by s4 = (sigE sigE) (sigE sigE) and by N.  Out, a consecutive column-major
+ * p x p matrices each: J = SSt_exp - bstar I, and the nullable sst_exp and sst_star. */
+int ppls_varinfo(ppls_ctx* ctx, const double* S, int P, int off, int p, int a, const double* cxt, const double* w,
+                 const double* ctt, const double* k1, const double* k2, const double* bstar, double sigE, double N,
+                 double* J, double* sst_exp, double* sst_star);
+/* Benchmark (tools/bench_variances_xprod.py): that kernel (J only) against the launches it replaces in
+ * ppls_variances' S path -- the block copy out of S, a ppls_varmat_kernel launches, the copy of the
+ * batch and the negate -- on the context's S, after a ppls_variances_xprod call with a components:
+ * reps times each between HIP events after one untimed round; *ms_new, *ms_old = the averages.  It reads
+ * the statistics and loadings that call left on the context (PPLS_E_STATE without it) and runs with
+ * every scalar set to 1: the times do not depend on the values, and the matrices it forms in its own
+ * scratch are meaningless and freed on return; no output of the context changes. */
+int ppls_varinfo_timing(ppls_ctx* ctx, int xory, int a, int reps, double* ms_new, double* ms_old);
+
 #ifdef __cplusplus
 }
 #endif

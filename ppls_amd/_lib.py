@@ -100,6 +100,11 @@ SIGNATURES = {
                                   ct.POINTER(PplsTheta), ct.POINTER(PplsMetaFit)]),
     "ppls_variances": (ct.c_int, [ct.c_void_p, _dp, _dp, ct.c_double, ct.c_int, ct.c_int, _dp, _dp, _dp, _dp,
                                   _dp, _dp]),
+    "ppls_variances_xprod": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsTheta), ct.c_int, ct.c_int, _dp, _dp, _dp, _dp,
+                                        _dp, _dp, _dp]),
+    "ppls_varinfo": (ct.c_int, [ct.c_void_p, _dp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _dp, _dp, _dp, _dp, _dp,
+                                _dp, ct.c_double, ct.c_double, _dp, _dp, _dp]),
+    "ppls_varinfo_timing": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, _dp, _dp]),
     "ppls_gram": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, _dp, _dp]),
     "ppls_gram_weighted": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(ct.c_int32), _dp, _dp]),
     "ppls_gram_occupancy": (ct.c_int, [ct.c_int]),

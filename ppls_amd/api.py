@@ -584,6 +584,63 @@ class Context:
         tr = (lambda A: None if A is None else np.transpose(A, (0, 2, 1)))
         return W, Bx, tr(V), se, tr(SE), tr(SS)
 
+    def variances_xprod(self, th: Theta, xory, full=True, want_var=True):
+        """variances.PPLS_simult (EM_W_multi.R:830-860) from the cross-products S alone
+        (ppls_variances_xprod): ``th`` is the theta at which the reference's Expectations are taken.
+        Works on every context that holds S -- streamed, a fold stream's current selection, the
+        destination of ``xprod_resample``, resident (S is formed and kept if it is not there).
+        Returns (W, Cdiag, B_exp scalars, varMatrix a x p x p, seLoad p x a, SSt_exp, SSt_star):
+        Cdiag = the Ctt_ii (xory 0) or Cuu_ii (xory 1) used; varMatrix only with want_var, the last
+        two only with full (else None)."""
+        a = th.r
+        p = self.q if xory else self.p
+        if p is None:
+            p = 1          # no data: the library refuses before it writes
+        elif th.W.shape[0] != self.p or th.C.shape[0] != self.q:
+            raise ValueError(f"theta is {th.W.shape[0]} x {th.C.shape[0]}, the context's data {self.p} x {self.q}")
+        W = np.zeros((p, a), order="F")
+        Cd = np.zeros(a)
+        Bx = np.zeros(a)
+        se = np.zeros((p, a), order="F")
+        V = np.zeros((a, p, p)) if want_var else None   # component i: the column-major p x p as its transpose
+        SE = np.zeros((a, p, p)) if full else None
+        SS = np.zeros((a, p, p)) if full else None
+        s = th.struct()
+        self._chk(self._L.ppls_variances_xprod(self.h, ct.byref(s), int(a), int(xory), dptr(W), dptr(Cd), dptr(Bx),
+                                               dptr(V), dptr(SE), dptr(SS), dptr(se)))
+        tr = (lambda A: None if A is None else np.transpose(A, (0, 2, 1)))
+        return W, Cd, Bx, tr(V), se, tr(SE), tr(SS)
+
+    def varinfo(self, S, off, p, cxt, w, ctt, k1, k2, bstar, sigE, N, full=True):
+        """ppls_variances_xprod's information kernel alone on host inputs (ppls_varinfo): S (P x P), the
+        p x p block at (off, off), cxt and w (p x a), the scalars ctt, k1, k2, bstar (a each) ->
+        (J, SSt_exp, SSt_star), a x p x p each as stored (column-major per matrix: entry [i, b, a] is
+        element (a, b)); the last two None without ``full``."""
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        P = S.shape[0]
+        cxt = np.asfortranarray(np.asarray(cxt, dtype=np.float64).reshape(p, -1))
+        w = np.asfortranarray(np.asarray(w, dtype=np.float64).reshape(p, -1))
+        a = cxt.shape[1]
+        sc = [np.ascontiguousarray(np.ravel(v), dtype=np.float64) for v in (ctt, k1, k2, bstar)]
+        if S.shape != (P, P) or w.shape != (p, a) or any(v.shape[0] != a for v in sc):
+            raise ValueError("varinfo: inconsistent shapes")
+        J = np.zeros((a, p, p))
+        SE = np.zeros((a, p, p)) if full else None
+        SS = np.zeros((a, p, p)) if full else None
+        self._chk(self._L.ppls_varinfo(self.h, dptr(S), int(P), int(off), int(p), int(a), dptr(cxt), dptr(w), dptr(sc[0]),
+                                       dptr(sc[1]), dptr(sc[2]), dptr(sc[3]), float(sigE), float(N), dptr(J), dptr(SE),
+                                       dptr(SS)))
+        return J, SE, SS
+
+    def varinfo_timing(self, xory, a, reps=5):
+        """(ms of the information kernel, ms of the launches it replaces: block copy, ``a`` varmat
+        kernels, batch copy, negate), HIP events, averages over ``reps`` (ppls_varinfo_timing); after a
+        ``variances_xprod`` call with ``a`` components, whose statistics and loadings it reads; it runs with
+        every scalar set to 1 (times do not depend on the values) and returns no matrix."""
+        new, old = ct.c_double(), ct.c_double()
+        self._chk(self._L.ppls_varinfo_timing(self.h, int(xory), int(a), int(reps), ct.byref(new), ct.byref(old)))
+        return new.value, old.value
+
     def gram(self, xory=0, nsplit=0, want=True, count=None):
         """D'D (D = X, Y, or xory = 2 the joint [X Y], (p + q) x (p + q)) on the fp64 MFMA Gram kernel
         alone, this rank's rows -> (G or None, kernel ms).  ``count`` (one integer >= 0 per local row):
@@ -1556,19 +1613,42 @@ def meta_PPLSi(X, Y, Ipopu, EMsteps=100, atol=1e-4, initialGuess=("equal", "o2m"
     return dict(W=W, C=C, params=_params_list(levels, P), log=lg[1:], logvalue=lg)
 
 
-def variances_PPLS_simult(fit, data, XorY=("X", "Y"), ctx=None, full=True):
+def variances_PPLS_simult(fit, data, XorY=("X", "Y"), ctx=None, full=True, from_xprod=False):
     """variances.PPLS_simult (EM_W_multi.R:830-860) on the GPU: asymptotic standard errors of the
     loadings.  ``fit``: a PPLS_simult list (Expectations, estimates); ``data``: X (XorY = "X") or Y
     (XorY = "Y"), or None to use the context's resident X / Y.  Returns the reference's list: per
     component dict(B_exp, SSt_exp, SSt_star), then varMatrix (list of p x p) and seLoad (p x a);
     full=False skips the p x p B_exp / SSt_exp / SSt_star matrices (B_exp is then its scalar).
     The reference's t(X) %*% diag(Ctt, N) %*% X is Ctt X'X, computed once on MFMA; like the reference
-    it uses estimates$sigE for XorY = "Y" as well."""
+    it uses estimates$sigE for XorY = "Y" as well.
+
+    ``from_xprod=True`` (``data`` must be None): everything comes from the cross-products S that
+    ``ctx`` holds (``Context.variances_xprod``), so it also serves a context without rows -- streamed,
+    a fold stream's selection, a bootstrap replicate of ``xprod_resample``.  The Expectations are
+    recomputed at ``fit["estimates"]`` on S (``fit["Expectations"]`` is not read), and the result
+    carries the ``Ctt`` (or Cuu) diagonal used as well.  Two differences from the reference's call on
+    its own fit follow from that:
+      - the components come in the order of ``estimates``; the reference orders them as its
+        Expectations, i.e. as the last iterate before the final rotLoad reordering;
+      - the reference's final sign step flips W, C and B together, which is not a symmetry of the
+        model, so where it flipped a component (a negative sigT B at the last iterate) the result is
+        that of the flipped theta, not the reference's."""
     if isinstance(XorY, (list, tuple)):
         raise ValueError("the condition has length > 1")   # if(XorY=="X") with the default c("X","Y")
     if XorY not in ("X", "Y"):
         return None                                        # neither branch: W undefined in R
     xory = 0 if XorY == "X" else 1
+    if from_xprod:
+        if data is not None:
+            raise ValueError("from_xprod=True reads the context's cross-products: data must be None")
+        c = ctx or default_context()
+        e = fit["estimates"]
+        th = Theta(e["W"], e["C"], e["B"], e["sigE"], e["sigF"], e["sigH"], e["sigT"])
+        W, Cd, Bx, V, se, SE, SS = c.variances_xprod(th, xory, full)
+        p = W.shape[0]
+        comps = [dict(B_exp=(Bx[i] * np.eye(p) if full else float(Bx[i])),
+                      SSt_exp=(SE[i] if full else None), SSt_star=(SS[i] if full else None)) for i in range(len(Bx))]
+        return dict(components=comps, varMatrix=[V[i] for i in range(len(Bx))], seLoad=se, W=W, Ctt=np.diag(Cd))
     E = fit["Expectations"]
     mu = np.asarray(E["mu_T"] if xory == 0 else E["mu_U"])
     Cd = np.diag(np.asarray(E["Ctt"] if xory == 0 else E["Cuu"]))

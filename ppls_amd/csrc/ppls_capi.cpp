@@ -28,6 +28,7 @@
 #include "ppls_scale.h"
 #include "ppls_cvstream.h"
 #include "ppls_stream.h"
+#include "ppls_varxprod.h"
 #include "ppls_xprod.h"
 #include "ppls_xprod_meta.h"
 
@@ -3332,6 +3333,278 @@ int ppls_variances(ppls_ctx* c, const double* mu, const double* Cdiag, double si
   VCHK(hipStreamSynchronize(c->stream));
 #undef VCHK
 #undef VRC
+  return done(PPLS_OK);
+}
+
+// variances.PPLS_simult from the cross-products S alone: the rows enter :830-860 through
+// t(X) diag(Ctt) X = N Ctt_ii X'X (S's diagonal block), Cxt = X'mu_T and W = orth(X'mu_T) (the SX
+// statistic and the polar factor of one cross-product EM step at theta) and crossprod(mu_T[, i]) (a
+// quadratic form in that step's 2r x 2r Gram).  Statistics, finalize, all r observed-information
+// matrices (one launch), their batched inverse and the mirror + seLoad launch stay on the device; the
+// host reads 4 r^2 + 2 r doubles for the scalars and synchronises once more before the copy-out.
+int ppls_variances_xprod(ppls_ctx* c, const ppls_theta* th, int r, int xory, double* W, double* Cdiag, double* B_exp,
+                         double* varMatrix, double* SSt_exp, double* SSt_star, double* seLoad) {
+  if (!c) return PPLS_E_ARG;
+  if (c->st_state == 1) return fail(c, PPLS_E_STATE, "a stream is open: S is complete only after ppls_stream_end");
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  if (!th || !W || !B_exp || !seLoad) return fail(c, PPLS_E_ARG, "NULL argument");
+  if (xory != 0 && xory != 1) return fail(c, PPLS_E_ARG, "XorY must be 0 (\"X\") or 1 (\"Y\")");
+  if (r < 1 || r > 16) return fail(c, PPLS_E_ARG, "number of components %d outside [1, 16]", r);
+  const int p = xory ? c->q : c->p, ld = xory ? c->ldy : c->ldx;
+  if (r > p) return fail(c, PPLS_E_ARG, "more components (%d) than columns (%d)", r, p);
+  int rc;
+  if ((rc = check_theta(c, th, r))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  // ---- one cross-product EM step at theta: SX / SY, the Gram, Ctt / Cuu, the new W / C ------------
+  if ((rc = ensure_r(c, r, 1))) return rc;
+  if ((rc = upload_theta(c, th, r, 0))) return rc;
+  HIPCHK(c, hipMemsetAsync(c->status, 0, PPLS_STATUS_INTS * sizeof(int), c->stream));
+  const bool had_S = c->xp_ready;
+  if ((rc = xprod_stats(c, r, 0))) return rc;   // forms S first where it is missing: the only collective
+  if (!had_S) c->xp_explicit = true;            // ... and then kept, as by ppls_xprod_prepare
+  if ((rc = finalize(c, r, 0, 1, -1, PPLS_ORTH_SVD))) return rc;
+  const int rr = r * r;
+  std::vector<double> G((size_t)4 * rr);
+  PplsMoments mom;
+  int st3[PPLS_STATUS_INTS];
+  HIPCHK(c, hipMemcpyAsync(G.data(), c->stats + (size_t)r * (c->ldx + c->ldy), sizeof(double) * 4 * rr,
+                           hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&mom, c->mom, sizeof mom, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(st3, c->status, sizeof st3, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (st3[0] == -7) {
+    if (c->team_bar) HIPCHK(c, hipMemset(c->team_bar, 0, 8 * sizeof(unsigned)));
+    return fail(c, PPLS_E_HIP, "finalize polar team barrier timed out (status -7)");
+  }
+  if (st3[0] != 0) return fail(c, PPLS_E_NUMERIC, "orth(t(data) %%*%% mu): rank-deficient");
+  // ---- the scalars of :840-848, from 4 r^2 + r numbers -------------------------------------------
+  const PplsScalars s = scalars_of(th, r);
+  const double N = (double)c->n_total;
+  const double s2 = th->sigE * th->sigE;   // sigE for "Y" too, like the reference
+  PplsVarinfoArgs va;
+  memset(&va, 0, sizeof va);
+  std::vector<double> cd((size_t)r);
+  for (int i = 0; i < r; ++i) {
+    const double c1 = xory ? s.gamma[i] : s.alpha[i], c2 = xory ? s.delta[i] : s.beta[i];
+    const double A = PPLS_GA(G.data(), r, i, i), D = PPLS_GD(G.data(), r, i, i), Bm = PPLS_GB(G.data(), r, i, i);
+    const double mu2 = c1 * c1 * A + 2.0 * c1 * c2 * D + c2 * c2 * Bm;   // crossprod(mu[, i])
+    cd[(size_t)i] = xory ? mom.Cuu[i] : mom.Ctt[i];
+    const double ctt = N * cd[(size_t)i];
+    const double Vt = ctt - mu2;
+    va.ctt[i] = ctt;
+    va.k1[i] = ctt + 2.0 * Vt;
+    va.k2[i] = ctt * ctt + 4.0 * mu2 * Vt + 2.0 * Vt * Vt;
+    va.bstar[i] = ctt / s2 / N;
+  }
+  va.S = c->xp_S;
+  va.P = c->ldx + c->ldy;
+  va.off = xory ? c->ldx : 0;
+  va.p = p;
+  va.a = r;
+  va.cxt = c->stats + (xory ? (size_t)r * c->ldx : 0);
+  va.ldc = ld;
+  va.w = xory ? c->C[1] : c->W[1];
+  va.ldw = ld;
+  va.s4 = s2 * s2;
+  va.N = N;
+  // ---- J_i for all i in one launch, the batched inverse, mirror + seLoad --------------------------
+  const size_t pp = (size_t)p * p;
+  double *dJ = nullptr, *dexp = nullptr, *dstar = nullptr, *dse = nullptr;
+  rocblas_int *ipiv = nullptr, *info = nullptr;
+  auto done = [&](int code) {
+    dfree(dJ); dfree(dexp); dfree(dstar); dfree(dse);
+    if (ipiv) (void)hipFree(ipiv);
+    if (info) (void)hipFree(info);
+    return code;
+  };
+#define VCHK(call)                                                                              \
+  do {                                                                                          \
+    hipError_t e_ = (call);                                                                     \
+    if (e_ != hipSuccess) return done(fail(c, PPLS_E_HIP, "%s: %s", #call, hipGetErrorString(e_))); \
+  } while (0)
+#define VRC(call)                  \
+  do {                             \
+    if ((rc = (call))) return done(rc); \
+  } while (0)
+  bool chol = c->var_chol != 0;
+  int chol_mode = c->var_chol;
+  if (chol_mode == 1) {   // the hand-written inverse works in a scratch behind the batch
+    if (hipMalloc((void**)&dJ, sizeof(double) * (pp * (size_t)r + (size_t)ppls_spd_inverse_work(p, r))) != hipSuccess) {
+      (void)hipGetLastError();   // (clear it) not enough HBM: rocSOLVER's in-place potrf/potri instead
+      dJ = nullptr;
+      chol_mode = 2;
+    }
+  }
+  if (!dJ) VRC(dalloc(c, &dJ, pp * (size_t)r));
+  if (SSt_exp) VRC(dalloc(c, &dexp, pp * (size_t)r));
+  if (SSt_star) VRC(dalloc(c, &dstar, pp * (size_t)r));
+  VRC(dalloc(c, &dse, (size_t)p * r));
+  VCHK(hipMalloc((void**)&info, sizeof(rocblas_int) * 2 * r));
+  va.J = dJ;
+  std::vector<double> Wp((size_t)ld * r);
+  std::vector<rocblas_int> inf((size_t)2 * r, 0);
+  for (int pass = 0;; ++pass) {
+    // pass 0: Cholesky (unless var_chol = 0); pass 1: some J_i was not positive definite, the batch
+    // takes R's solve() route, LU, from J formed again (the Cholesky worked in place)
+    va.sst_exp = pass == 0 ? dexp : nullptr;
+    va.sst_star = pass == 0 ? dstar : nullptr;
+    VCHK(ppls_launch_varinfo_batched(&va, c->stream));
+    if (pass == 0) {
+      if (SSt_exp) VCHK(hipMemcpyAsync(SSt_exp, dexp, sizeof(double) * pp * r, hipMemcpyDeviceToHost, c->stream));
+      if (SSt_star) VCHK(hipMemcpyAsync(SSt_star, dstar, sizeof(double) * pp * r, hipMemcpyDeviceToHost, c->stream));
+      VCHK(hipMemcpyAsync(Wp.data(), va.w, sizeof(double) * ld * r, hipMemcpyDeviceToHost, c->stream));
+    }
+    VCHK(hipMemsetAsync(info, 0, sizeof(rocblas_int) * 2 * r, c->stream));
+    if (!chol || chol_mode == 2) {   // the rocSOLVER routes
+      if (!c->blas && rocblas_create_handle(&c->blas) != rocblas_status_success)
+        return done(fail(c, PPLS_E_HIP, "rocblas_create_handle failed"));
+      if (rocblas_set_stream(c->blas, c->stream) != rocblas_status_success)
+        return done(fail(c, PPLS_E_HIP, "rocblas_set_stream failed"));
+    }
+    if (chol && chol_mode == 1) {
+      VCHK(ppls_spd_inverse_batched(dJ, p, r, dJ + pp * (size_t)r, (int*)info, c->stream));
+    } else if (chol) {   // (potri of a factorisation that failed is discarded below)
+      if (rocsolver_dpotrf_strided_batched(c->blas, rocblas_fill_lower, p, dJ, p, (rocblas_stride)pp, info, r) !=
+              rocblas_status_success ||
+          rocsolver_dpotri_strided_batched(c->blas, rocblas_fill_lower, p, dJ, p, (rocblas_stride)pp, info + r, r) !=
+              rocblas_status_success)
+        return done(fail(c, PPLS_E_HIP, "rocsolver potrf/potri (strided batched) failed"));
+    } else {
+      if (!ipiv) VCHK(hipMalloc((void**)&ipiv, sizeof(rocblas_int) * p * r));
+      if (rocsolver_dgetrf_strided_batched(c->blas, p, p, dJ, p, (rocblas_stride)pp, ipiv, p, info, r) !=
+              rocblas_status_success ||
+          rocsolver_dgetri_strided_batched(c->blas, p, dJ, p, (rocblas_stride)pp, ipiv, p, info + r, r) !=
+              rocblas_status_success)
+        return done(fail(c, PPLS_E_HIP, "rocsolver getrf/getri (strided batched) failed"));
+    }
+    VCHK(ppls_launch_varfinish_batched(dJ, p, r, chol ? 1 : 0, dse, c->stream));
+    if (varMatrix) VCHK(hipMemcpyAsync(varMatrix, dJ, sizeof(double) * pp * r, hipMemcpyDeviceToHost, c->stream));
+    VCHK(hipMemcpyAsync(seLoad, dse, sizeof(double) * p * r, hipMemcpyDeviceToHost, c->stream));
+    VCHK(hipMemcpyAsync(inf.data(), info, sizeof(rocblas_int) * 2 * r, hipMemcpyDeviceToHost, c->stream));
+    VCHK(hipStreamSynchronize(c->stream));
+    bool bad = false;
+    for (int i = 0; i < 2 * r; ++i) bad = bad || inf[(size_t)i] != 0;
+    if (!bad) break;
+    if (!chol) {   // solve(): "Lapack routine dgesv: system is exactly singular"
+      for (int i = 0; i < 2 * r; ++i)
+        if (inf[(size_t)i] != 0)
+          return done(fail(c, PPLS_E_NUMERIC, "component %d: B_exp - SSt_exp is exactly singular (U[%d,%d] = 0)",
+                           i % r + 1, (int)inf[(size_t)i], (int)inf[(size_t)i]));
+    }
+    chol = false;
+  }
+#undef VCHK
+#undef VRC
+  for (int k = 0; k < r; ++k)
+    for (int i = 0; i < p; ++i) W[(size_t)k * p + i] = Wp[(size_t)k * ld + i];
+  for (int i = 0; i < r; ++i) {
+    B_exp[i] = va.bstar[i];
+    if (Cdiag) Cdiag[i] = cd[(size_t)i];
+  }
+  return done(PPLS_OK);
+}
+
+// Diagnostics / tests: ppls_varinfo_batched_kernel alone on host inputs (tests/varinfo_bar.py).
+int ppls_varinfo(ppls_ctx* c, const double* S, int P, int off, int p, int a, const double* cxt, const double* w,
+                 const double* ctt, const double* k1, const double* k2, const double* bstar, double sigE, double N,
+                 double* J, double* sst_exp, double* sst_star) {
+  if (!c || !S || !cxt || !w || !ctt || !k1 || !k2 || !bstar || !J) return PPLS_E_ARG;
+  if (p < 1 || a < 1 || a > 16 || off < 0 || (P & 1) || (off & 1) || (int64_t)off + p + (p & 1) > P)
+    return fail(c, PPLS_E_ARG, "varinfo: P and off must be even, off + p (+ 1 for odd p) <= P, 1 <= a <= 16");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t pp = (size_t)p * p, PP = (size_t)P * P;
+  const int nout = 1 + (sst_exp ? 1 : 0) + (sst_star ? 1 : 0);
+  double *dS = nullptr, *dv = nullptr, *dout = nullptr;
+  auto done = [&](int code) {
+    dfree(dS); dfree(dv); dfree(dout);
+    return code;
+  };
+  int rc;
+  if ((rc = dalloc(c, &dS, PP)) || (rc = dalloc(c, &dv, (size_t)2 * p * a)) || (rc = dalloc(c, &dout, pp * a * nout)))
+    return done(rc);
+  PplsVarinfoArgs va;
+  memset(&va, 0, sizeof va);
+  for (int i = 0; i < a; ++i) {
+    va.ctt[i] = ctt[i];
+    va.k1[i] = k1[i];
+    va.k2[i] = k2[i];
+    va.bstar[i] = bstar[i];
+  }
+  const double s2 = sigE * sigE;
+  va.S = dS; va.P = P; va.off = off; va.p = p; va.a = a;
+  va.cxt = dv; va.ldc = p; va.w = dv + (size_t)p * a; va.ldw = p;
+  va.s4 = s2 * s2; va.N = N;
+  va.J = dout;
+  va.sst_exp = sst_exp ? dout + pp * a : nullptr;
+  va.sst_star = sst_star ? dout + pp * a * (sst_exp ? 2 : 1) : nullptr;
+  hipError_t e = hipMemcpy(dS, S, sizeof(double) * PP, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dv, cxt, sizeof(double) * p * a, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dv + (size_t)p * a, w, sizeof(double) * p * a, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemsetAsync(dout, 0xff, sizeof(double) * pp * a * nout, c->stream);   // unwritten reads NaN
+  if (e == hipSuccess) e = ppls_launch_varinfo_batched(&va, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = hipMemcpy(J, va.J, sizeof(double) * pp * a, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && sst_exp) e = hipMemcpy(sst_exp, va.sst_exp, sizeof(double) * pp * a, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && sst_star) e = hipMemcpy(sst_star, va.sst_star, sizeof(double) * pp * a, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return done(fail(c, PPLS_E_HIP, "varinfo: %s", hipGetErrorString(e)));
+  return done(PPLS_OK);
+}
+
+// Benchmark: the information kernel against the launches it replaces in ppls_variances' S path -- the
+// block copy out of S, a ppls_varmat_kernel launches, the copy of the batch and the negate -- reps
+// times each between HIP events, on the context's S with the statistics and loadings the last
+// ppls_variances_xprod left (the times do not depend on the values; the scalars are 1).
+// The matrices it forms live in its own scratch, are meaningless and are freed on return.
+int ppls_varinfo_timing(ppls_ctx* c, int xory, int a, int reps, double* ms_new, double* ms_old) {
+  if (!c || !ms_new || !ms_old || reps < 1 || (xory != 0 && xory != 1)) return PPLS_E_ARG;
+  if (!c->have_data || !c->xp_ready || !c->xp_S) return fail(c, PPLS_E_STATE, "the cross-products S are not formed");
+  if (a < 1 || a != c->r_alloc) return fail(c, PPLS_E_STATE, "call ppls_variances_xprod with %d components first", a);
+  HIPCHK(c, hipSetDevice(c->device));
+  const int p = xory ? c->q : c->p, ld = xory ? c->ldy : c->ldx;
+  const size_t pp = (size_t)p * p, P = (size_t)c->ldx + c->ldy, off = xory ? (size_t)c->ldx : 0;
+  double* buf = nullptr;   // [G | M batch | its copy]
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  auto done = [&](int code) {
+    dfree(buf);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    return code;
+  };
+  int rc;
+  if ((rc = dalloc(c, &buf, pp * (1 + 2 * (size_t)a)))) return done(rc);
+  double *dG = buf, *dM = buf + pp, *dMc = dM + pp * a;
+  PplsVarinfoArgs va;
+  memset(&va, 0, sizeof va);
+  for (int i = 0; i < a; ++i) va.ctt[i] = va.k1[i] = va.k2[i] = va.bstar[i] = 1.0;
+  va.S = c->xp_S; va.P = (int)P; va.off = (int)off; va.p = p; va.a = a;
+  va.cxt = c->stats + (xory ? (size_t)a * c->ldx : 0); va.ldc = ld;
+  va.w = xory ? c->C[1] : c->W[1]; va.ldw = ld;
+  va.s4 = 1.0; va.N = (double)c->n_total;
+  va.J = dM;
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipEventCreate(&ev[k]);
+  for (int pass = 0; pass < 2 && e == hipSuccess; ++pass) {   // pass 0: warm-up
+    e = hipEventRecord(ev[0], c->stream);
+    for (int k = 0; k < reps && e == hipSuccess; ++k) e = ppls_launch_varinfo_batched(&va, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
+    for (int k = 0; k < reps && e == hipSuccess; ++k) {
+      e = hipMemcpy2DAsync(dG, sizeof(double) * p, c->xp_S + off * P + off, sizeof(double) * P, sizeof(double) * p, p,
+                           hipMemcpyDeviceToDevice, c->stream);
+      for (int i = 0; i < a && e == hipSuccess; ++i)
+        e = ppls_launch_varmat(dG, va.cxt + (size_t)i * ld, va.w + (size_t)i * ld, p, 1.0, 1.0, 1.0, 1.0, 1.0, va.N,
+                               dM + pp * i, nullptr, nullptr, c->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(dMc, dM, sizeof(double) * pp * a, hipMemcpyDeviceToDevice, c->stream);
+      if (e == hipSuccess) e = ppls_launch_negate(dMc, (int64_t)pp * a, c->stream);
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev[2], c->stream);
+    if (e == hipSuccess) e = hipEventSynchronize(ev[2]);
+  }
+  float t0 = 0.f, t1 = 0.f;
+  if (e == hipSuccess) e = hipEventElapsedTime(&t0, ev[0], ev[1]);
+  if (e == hipSuccess) e = hipEventElapsedTime(&t1, ev[1], ev[2]);
+  if (e != hipSuccess) return done(fail(c, PPLS_E_HIP, "varinfo_timing: %s", hipGetErrorString(e)));
+  *ms_new = (double)t0 / reps;
+  *ms_old = (double)t1 / reps;
   return done(PPLS_OK);
 }
 
