@@ -258,6 +258,32 @@ typedef struct {
 } ppls_constraint;
 int ppls_ppls_ex(ppls_ctx* ctx, int a, int max_steps, double atol, int crit_abs, const ppls_theta* init,
                  const ppls_constraint* cons, ppls_seq_fit* out);
+/* ---- 'o2m' starting values from the cross-products S (initialGuess = "o2m_xprod") ----------------
+ * Replaces PPLSi's `initialGuess == "o2m"` branch (Package/PPLS/R/EM_W_multi.R:126-131; meta_PPLSi
+ * :520-525): W., C. = the first singular pair of Xc'Yc, B = Tt'U / Tt'Tt, sig and siglat from ssq(Xc),
+ * ssq(Yc), ssq(Tt), ssq(U), for Xc = X P_1 .. P_k, Yc = Y Q_1 .. Q_k, P_j = I - w_j w_j' (:270-271;
+ * Wprev p x k, Cprev q x k column-major, 0 <= k <= PPLS_RMAX - 1; NULL when k = 0; the loadings need not
+ * be orthonormal).  Everything is read off the context's working S = [X Y]'[X Y]: a streamed context,
+ * a fold stream's current selection, a resample destination, or resident data -- a resident context
+ * without S forms and keeps it exactly as ppls_xprod_prepare does (collective on row shards, with the
+ * same agreement on allocation).  The pair is the top eigenpair of M'M, M the deflated off-diagonal
+ * block with the shorter rows, by symmetric Lanczos (start 1/sqrt(L), full reorthogonalisation, host
+ * recurrence) on one device pass over the block per operator application (ppls_o2m.hip); it stops at
+ * a residual estimate <= 2^-43 theta, at a basis of L vectors, or after 200 passes (accepted there
+ * if <= 2^-26 theta, else PPLS_E_NUMERIC).  theta <= 2^-104 ssq(X) ssq(Y), with the sums of squares of
+ * the context's data before any deflation (sigma_1 within rounding of ||X|| ||Y||: the deflated X'Y
+ * vanishes, theta = 0 included): PPLS_E_NUMERIC.  S formed by this call costs 8 (ldx + ldy)^2 bytes of
+ * device memory (128 MB at p = q = 2000, 925 MB at p = 10^4, q = 500) and stays until
+ * ppls_xprod_release or new data; an S that option xprod had formed keeps that option's lifetime.
+ * Sign: the entry of W. of largest magnitude (lowest index on a tie) is positive, C. follows; R's svd
+ * fixes only the joint sign, so a comparison is up to it.  Every rank holds the same S and computes
+ * the same bits with no collective.  out: theta with r = 1 (W p, C q, B[1], sigT[1]). */
+int ppls_o2m_start(ppls_ctx* ctx, const double* Wprev, const double* Cprev, int k, ppls_theta* out);
+/* ppls_ppls_ex with component k's start taken from ppls_o2m_start on the loop's own deflation by the
+ * fitted components 1..k-1 (PPLS :256-257 with PPLSi :126-131), its constraints applied on top
+ * (:141-145): every component is fitted once.  The fits read S or sweep the rows as option xprod says. */
+int ppls_ppls_o2m(ppls_ctx* ctx, int a, int max_steps, double atol, int crit_abs, const ppls_constraint* cons,
+                  ppls_seq_fit* out);
 int ppls_synchronize(ppls_ctx* ctx);
 
 /* ---- multi-population rank-1 fits: meta_EMstep / meta_PPLSi ----------------------------------
@@ -437,6 +463,11 @@ int ppls_cv_ppls(ppls_ctx* ctx, int a, int nfolds, const int32_t* fold_of_row /*
                  const int64_t* fold_total /* nfolds: rows per fold over all ranks */,
                  int max_steps, double atol, int crit_abs, const ppls_theta* init /* nfolds x a */,
                  double* rmsep /* nfolds x a, fold-major */, int* ncomp /* nfolds */);
+/* The same loop with initialGuess = "o2m_xprod" (crossval_PPLS.R:47 with PPLSi :126-131 on the
+ * training rows): no init; each fold's fit is ppls_ppls_o2m on the training context, whose S always
+ * comes from ppls_xprod_downdate (formed from the training rows where the fold outnumbers them). */
+int ppls_cv_ppls_o2m(ppls_ctx* ctx, int a, int nfolds, const int32_t* fold_of_row, const int64_t* fold_total,
+                     int max_steps, double atol, int crit_abs, double* rmsep, int* ncomp);
 
 /* ---- streamed data: fit from row chunks, no rows resident -------------------------------------
  * Since the cross-product form a PPLS_simult iteration and every rank-1 step of PPLS read only
@@ -563,6 +594,10 @@ int ppls_heldout_sse_fold(ppls_ctx* ctx, const double* W, const double* C, const
 int ppls_cv_ppls_stream(ppls_ctx* ctx, int a, int max_steps, double atol, int crit_abs,
                         const ppls_theta* init /* nfolds x a */, double* rmsep /* nfolds x a */,
                         int* ncomp /* nfolds */, double* cond /* nfolds x a, nullable */);
+/* The same loop with initialGuess = "o2m_xprod" (crossval_PPLS.R:47 with PPLSi :126-131): no init; each
+ * fold's fit is ppls_ppls_o2m on the selection that leaves the fold out. */
+int ppls_cv_ppls_stream_o2m(ppls_ctx* ctx, int a, int max_steps, double atol, int crit_abs, double* rmsep,
+                            int* ncomp, double* cond);
 
 /* ---- host-side algebra (no GPU; the same code the device finalize runs) ------------------------ */
 /* From the all-reduced sufficient statistics of one sweep with theta (stats = [X'mu_T p x r |

@@ -200,6 +200,22 @@ int ppls_varinfo(ppls_ctx* ctx, const double* S, int P, int off, int p, int a, c
  * scratch are meaningless and freed on return; no output of the context changes. */
 int ppls_varinfo_timing(ppls_ctx* ctx, int xory, int a, int reps, double* ms_new, double* ms_old);
 
+/* The 'o2m_xprod' pass alone (ppls_o2m.hip) on a host matrix S (row-major P x ld, uploaded and
+ * downloaded around one launch): for the block of `rows` rows from row0 and L columns from col0 (row0
+ * + rows <= P, col0 even, ld even, col0 + L rounded up to 2 <= ld), u_i = a_i . v - d_i (rows values)
+ * and z = sum_i u_i a_i (L values); d may be NULL (0).  Option "o2m_path" picks the path; *path = the
+ * one taken (1 fused, 2 two-phase).  Forcing the fused path past its budget is PPLS_E_ARG. */
+int ppls_o2m_pass(ppls_ctx* ctx, const double* S, int P, int ld, int row0, int col0, int rows, int L, const double* v,
+                  const double* d, double* u, double* z, int* path);
+/* The last ppls_o2m_start (or the last start inside ppls_ppls_o2m): side (0: the block's rows are X's
+ * columns, q <= p; 1: Y's), path of its passes, Lanczos passes (operator applications), the residual
+ * estimate |beta_m s_m| and theta = sigma_1^2; *fits = rank-1 device fits of the last ppls_ppls_o2m,
+ * counted by the sequential loop after each fit (not by the starts). */
+int ppls_o2m_info(ppls_ctx* ctx, int* side, int* path, int* passes, double* resid, double* theta, int* fits);
+/* Benchmark (tools/bench_o2m.py): reps back-to-back passes on the context's S (which must be ready)
+ * between HIP events after one untimed pass; *ms = the average, *bytes = the 8 rows L bytes of A. */
+int ppls_o2m_pass_timing(ppls_ctx* ctx, int reps, double* ms, double* bytes, int* path);
+
 #ifdef __cplusplus
 }
 #endif

@@ -178,6 +178,18 @@ SIGNATURES = {
     "ppls_rank1_mu_coefficients": (ct.c_int, [_dp, _dp]),
     "ppls_xprod_meta_nt": (ct.c_int, [ct.c_int, ct.c_int]),
     "ppls_xprod_meta_timing": (ct.c_int, [ct.c_void_p, ct.c_int, _dp]),
+    "ppls_o2m_start": (ct.c_int, [ct.c_void_p, _dp, _dp, ct.c_int, ct.POINTER(PplsTheta)]),
+    "ppls_ppls_o2m": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.c_double, ct.c_int, ct.POINTER(PplsConstraint),
+                                 ct.POINTER(PplsSeqFit)]),
+    "ppls_cv_ppls_o2m": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(ct.c_int32), _i64p, ct.c_int,
+                                    ct.c_double, ct.c_int, _dp, ct.POINTER(ct.c_int)]),
+    "ppls_cv_ppls_stream_o2m": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.c_double, ct.c_int, _dp,
+                                           ct.POINTER(ct.c_int), _dp]),
+    "ppls_o2m_pass": (ct.c_int, [ct.c_void_p, _dp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _dp, _dp,
+                                 _dp, _dp, ct.POINTER(ct.c_int)]),
+    "ppls_o2m_info": (ct.c_int, [ct.c_void_p, ct.POINTER(ct.c_int), ct.POINTER(ct.c_int), ct.POINTER(ct.c_int), _dp, _dp,
+                                 ct.POINTER(ct.c_int)]),
+    "ppls_o2m_pass_timing": (ct.c_int, [ct.c_void_p, ct.c_int, _dp, _dp, ct.POINTER(ct.c_int)]),
 }
 
 

@@ -412,6 +412,21 @@ class Context:
         if len(ths) != a:
             raise ValueError(f"{len(ths)} starting values for nr_comp = {a}")
         arr = (_lib.PplsTheta * a)(*[t.struct() for t in ths])
+        return self._seq_fit(a, max_steps, atol, arr, constraints, crit_abs)
+
+    def ppls_o2m(self, a: int, max_steps: int, atol: float, constraints=None, crit_abs=False):
+        """``ppls`` with ``initialGuess="o2m_xprod"`` (ppls_ppls_o2m): component k starts from the o2m
+        values of the data deflated by the fitted components 1 .. k-1, read off the context's
+        cross-products S on the device, and every component is fitted once.  Works wherever S is all
+        there is (streamed, a fold selection, a resample destination); a resident context forms S and
+        keeps it, as after ``xprod_prepare``.  Returns ``ppls``'s dict."""
+        if self.p is None:   # no data: the library says so
+            self._chk(self._L.ppls_ppls_o2m(self.h, int(a), int(max_steps), float(atol), 0, None, None))
+        return self._seq_fit(a, max_steps, atol, None, constraints, crit_abs)
+
+    def _seq_fit(self, a, max_steps, atol, arr, constraints, crit_abs):
+        """ppls_ppls_ex from the starting values ``arr``, or ppls_ppls_o2m (``arr`` None)."""
+        p, q = self.p, self.q
         W = np.zeros((p, a), order="F")
         C = np.zeros((q, a), order="F")
         B = np.zeros(a)
@@ -438,8 +453,12 @@ class Context:
                         raise ValueError(f"constraint {key} of component {k + 1} has {arrv.shape[0]} values, not {size}")
                     keep.append(arrv)
                     setattr(cons[k], key, dptr(arrv))
-        self._chk(self._L.ppls_ppls_ex(self.h, int(a), int(max_steps), float(atol), int(bool(crit_abs)), arr,
-                                       cons, ct.byref(fit)))
+        if arr is None:
+            self._chk(self._L.ppls_ppls_o2m(self.h, int(a), int(max_steps), float(atol), int(bool(crit_abs)), cons,
+                                            ct.byref(fit)))
+        else:
+            self._chk(self._L.ppls_ppls_ex(self.h, int(a), int(max_steps), float(atol), int(bool(crit_abs)), arr,
+                                           cons, ct.byref(fit)))
         del keep
         k = fit.ncomp
         return dict(W=W[:, :k].copy(), C=C[:, :k].copy(), B=B[:k].copy(), sig=sig[:k].copy(),
@@ -715,6 +734,87 @@ class Context:
         that reads S forms it again."""
         self._chk(self._L.ppls_xprod_release(self.h))
         self._stream_folds = None
+
+    def o2m_start(self, Wprev=None, Cprev=None):
+        """PPLSi's 'o2m' starting values (EM_W_multi.R:126-131) for the data deflated by the loadings
+        ``Wprev`` (p x k), ``Cprev`` (q x k), from the context's cross-products S (ppls_o2m_start): the
+        starting-value dict (W, C, B, sigE, sigF, sigH, sigT).  The entry of W of largest magnitude is
+        positive and C follows."""
+        if self.p is None:   # no data: the library says so
+            self._chk(self._L.ppls_o2m_start(self.h, None, None, 0, None))
+        p, q = self.p, self.q
+        Wp = np.zeros((p, 0)) if Wprev is None else np.asarray(Wprev, dtype=np.float64).reshape(p, -1)
+        Cp = np.zeros((q, 0)) if Cprev is None else np.asarray(Cprev, dtype=np.float64).reshape(q, -1)
+        if Wp.shape[1] != Cp.shape[1]:
+            raise ValueError(f"{Wp.shape[1]} earlier W loadings but {Cp.shape[1]} C loadings")
+        k = Wp.shape[1]
+        Wp, Cp = np.asfortranarray(Wp), np.asfortranarray(Cp)
+        th = Theta.empty(p, q, 1)
+        s = th.struct()
+        self._chk(self._L.ppls_o2m_start(self.h, dptr(Wp) if k else None, dptr(Cp) if k else None, int(k), ct.byref(s)))
+        th.pull(s)
+        return dict(W=th.W[:, 0].copy(), C=th.C[:, 0].copy(), B=float(th.B[0]), sigE=th.sigE, sigF=th.sigF,
+                    sigH=th.sigH, sigT=float(th.sigT[0]))
+
+    def o2m_pass(self, S, row0, col0, rows, L, v, d=None):
+        """The 'o2m_xprod' pass alone (ppls_o2m_pass) on a host matrix ``S`` (row-major, an even row
+        length): for the ``rows x L`` block A at (row0, col0), ``u = A v - d`` and ``z = A'u``.
+        Returns (u, z, path): path 1 fused, 2 two-phase (option "o2m_path")."""
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        v = np.ascontiguousarray(np.ravel(v), dtype=np.float64)
+        dd = None if d is None else np.ascontiguousarray(np.ravel(d), dtype=np.float64)
+        if v.shape[0] != L or (dd is not None and dd.shape[0] != rows):
+            raise ValueError("v has L values and d has one per row")
+        u, z = np.zeros(int(rows)), np.zeros(int(L))
+        path = ct.c_int()
+        self._chk(self._L.ppls_o2m_pass(self.h, dptr(S), int(S.shape[0]), int(S.shape[1]), int(row0), int(col0),
+                                        int(rows), int(L), dptr(v), dptr(dd), dptr(u), dptr(z), ct.byref(path)))
+        return u, z, path.value
+
+    def o2m_info(self):
+        """The last 'o2m_xprod' start (ppls_o2m_info): side (0: the block's rows are X's columns),
+        path of its passes, Lanczos passes, residual estimate, theta = sigma_1^2, and the rank-1
+        device fits of the last ``ppls_o2m``."""
+        side, path, passes, fits = ct.c_int(), ct.c_int(), ct.c_int(), ct.c_int()
+        resid, theta = ct.c_double(), ct.c_double()
+        self._chk(self._L.ppls_o2m_info(self.h, ct.byref(side), ct.byref(path), ct.byref(passes), ct.byref(resid),
+                                        ct.byref(theta), ct.byref(fits)))
+        return dict(side=side.value, path=path.value, passes=passes.value, resid=resid.value, theta=theta.value,
+                    fits=fits.value)
+
+    def o2m_pass_timing(self, reps=50):
+        """Average ms of the 'o2m_xprod' pass over reps back-to-back launches on the context's S
+        (HIP events around the batch, after one untimed pass) -> dict(ms, bytes, path)."""
+        ms, nbytes = ct.c_double(), ct.c_double()
+        path = ct.c_int()
+        self._chk(self._L.ppls_o2m_pass_timing(self.h, int(reps), ct.byref(ms), ct.byref(nbytes), ct.byref(path)))
+        return dict(ms=ms.value, bytes=nbytes.value, path=path.value)
+
+    def cv_ppls_o2m(self, a: int, fold_of_row, fold_total, max_steps: int, atol: float, crit_abs=False):
+        """``cv_ppls`` with ``initialGuess="o2m_xprod"`` (ppls_cv_ppls_o2m): no starting values."""
+        fold_of_row = np.ascontiguousarray(np.ravel(np.asarray(fold_of_row, dtype=np.int32)))
+        fold_total = np.ascontiguousarray(np.ravel(np.asarray(fold_total, dtype=np.int64)))
+        K = fold_total.shape[0]
+        if fold_of_row.shape[0] != self.n_local:
+            raise ValueError(f"{fold_of_row.shape[0]} fold labels for {self.n_local} local rows")
+        rmsep = np.full((K, a), np.nan)
+        ncomp = np.zeros(K, dtype=np.int32)
+        self._chk(self._L.ppls_cv_ppls_o2m(self.h, int(a), int(K), fold_of_row.ctypes.data_as(ct.POINTER(ct.c_int32)),
+                                           fold_total.ctypes.data_as(_lib._i64p), int(max_steps), float(atol),
+                                           int(bool(crit_abs)), dptr(rmsep), ncomp.ctypes.data_as(ct.POINTER(ct.c_int))))
+        return rmsep, ncomp
+
+    def cv_ppls_stream_o2m(self, a: int, max_steps: int, atol: float, crit_abs=False):
+        """``cv_ppls_stream`` with ``initialGuess="o2m_xprod"`` (ppls_cv_ppls_stream_o2m)."""
+        K = self.stream_fold_info()["nr_folds"]
+        rmsep, cond = np.full((K, a), np.nan), np.full((K, a), np.nan)
+        ncomp = np.zeros(K, dtype=np.int32)
+        try:
+            self._chk(self._L.ppls_cv_ppls_stream_o2m(self.h, int(a), int(max_steps), float(atol), int(bool(crit_abs)),
+                                                      dptr(rmsep), ncomp.ctypes.data_as(ct.POINTER(ct.c_int)), dptr(cond)))
+        finally:
+            self.n_total = self.stream_info()["n_total"]
+        return rmsep, ncomp, cond
 
     def xprod_matrix(self, padded=False):
         """The cross-products S the context holds (formed, prepared, downdated or streamed):
@@ -1179,8 +1279,8 @@ def initial_guess(p, q, kind="equal", rng=None):
             sig = rng.chisquare(10, size=2) / 100
         return dict(W=W / np.linalg.norm(W), C=C / np.linalg.norm(C), B=float(B), sigE=float(sig[0]),
                     sigF=float(sig[1]), sigH=float(siglat[0]), sigT=float(siglat[1]))
-    if kind == "o2m":
-        raise ValueError("initialGuess='o2m' depends on the data: PPLS / PPLSi / meta_PPLSi compute it "
+    if kind in ("o2m", "o2m_xprod"):
+        raise ValueError(f"initialGuess={kind!r} depends on the data: PPLS / PPLSi / meta_PPLSi compute it "
                          "(o2m_guess_from_gram)")
     raise ValueError(f"unknown initialGuess {kind!r}")
 
@@ -1315,12 +1415,19 @@ def _crit_abs(critfunc):
     raise NotImplementedError("critfunc must be the identity (default) or abs")
 
 
-def PPLS(X, Y, nr_comp=1, EMsteps=100, atol=1e-4, initialGuess=("equal", "o2m", "random", "custom"),
+def PPLS(X, Y, nr_comp=1, EMsteps=100, atol=1e-4, initialGuess=("equal", "o2m", "random", "custom", "o2m_xprod"),
          customGuess=None, critfunc=None, constraints=None, rng=None, ctx=None):
     """PPLS (EM_W_multi.R:229-279) on the GPU: nr_comp sequential rank-1 EM fits on deflated data.
     Same return list (W, C, B, sig, Other_output); class "PPLS".  customGuess: one dict (used for
     every component, as in R) or a list of per-component dicts; critfunc: identity (default) or abs;
-    constraints: None or a list of nr_comp fconstraint(...) dicts (:230, :255)."""
+    constraints: None or a list of nr_comp fconstraint(...) dicts (:230, :255).
+
+    ``initialGuess="o2m_xprod"`` takes the 'o2m' starts from the cross-products S on the
+    device and fits every component once; it also runs where S is all the context holds.  On a resident
+    context without S the call forms S first (one MFMA Gram pass over the rows; about 0.23 s at n = 1e6,
+    p = q = 2000) and leaves it on the context -- 8 (p + q)^2 bytes of device memory, 128 MB there,
+    925 MB at p = 1e4, q = 500 -- until ``ctx.xprod_release()`` or new data; with option ``xprod`` = 1
+    or -1 the fits share that S."""
     ctx = _ctx_with(X, Y, ctx)
     kind = initialGuess if isinstance(initialGuess, str) else initialGuess[0]
     if customGuess is not None:
@@ -1332,6 +1439,9 @@ def PPLS(X, Y, nr_comp=1, EMsteps=100, atol=1e-4, initialGuess=("equal", "o2m", 
     elif kind == "o2m":
         out = _ppls_o2m(ctx, int(nr_comp), int(EMsteps), float(atol), constraints, _crit_abs(critfunc))
         return _ppls_finish(out, nr_comp)
+    elif kind == "o2m_xprod":   # the same starts from the cross-products S on the device, each component fitted once
+        return _ppls_finish(ctx.ppls_o2m(int(nr_comp), int(EMsteps), float(atol), constraints, _crit_abs(critfunc)),
+                            nr_comp)
     else:
         rng = rng if rng is not None else np.random.default_rng()
         inits = [initial_guess(ctx.p, ctx.q, kind, rng) for _ in range(nr_comp)]
@@ -1351,7 +1461,7 @@ def _ppls_finish(out, nr_comp):
     return out
 
 
-def PPLSi(X, Y, EMsteps=100, atol=1e-4, initialGuess=("equal", "o2m", "random", "custom"),
+def PPLSi(X, Y, EMsteps=100, atol=1e-4, initialGuess=("equal", "o2m", "random", "custom", "o2m_xprod"),
           customGuess=None, critfunc=None, constraints=None, rng=None, ctx=None):
     """PPLSi (EM_W_multi.R:116-180): one direction; returns W, C, B, sig, logvalue, Last_increment,
     Number_steps (W = NA when sigE or sigF collapse, :152-154).  constraints: one fconstraint dict."""
@@ -1562,7 +1672,7 @@ def meta_EMstep(X, Y, W, C, Ipopu, params, ctx=None):
     return dict(pops=out, **{"W.": Wo.reshape(-1, 1), "C.": Co.reshape(-1, 1)})
 
 
-def meta_PPLSi(X, Y, Ipopu, EMsteps=100, atol=1e-4, initialGuess=("equal", "o2m", "random", "custom"),
+def meta_PPLSi(X, Y, Ipopu, EMsteps=100, atol=1e-4, initialGuess=("equal", "o2m", "random", "custom", "o2m_xprod"),
                customGuess=None, critfunc=None, constraints=None, rng=None, ctx=None):
     """meta_PPLSi (EM_W_multi.R:509-589) on the GPU: a rank-1 PPLS fit with loadings shared across
     populations and per-population scalars.  Returns the reference's list (W, C, params, log) where
@@ -1576,7 +1686,8 @@ def meta_PPLSi(X, Y, Ipopu, EMsteps=100, atol=1e-4, initialGuess=("equal", "o2m"
     ``population_labels`` -- fits the stream's K populations from their cross-products
     (ppls_meta_ppls_stream): data larger than device memory, no rows resident; ``params`` are in label
     order 0 .. K-1.  Passing an ``Ipopu`` there raises ``ValueError``, and ``initialGuess="o2m"`` stays
-    refused on streamed contexts.  One population cannot be streamed this way (a fold stream needs
+    refused on streamed contexts; ``"o2m_xprod"`` takes the same start from the cross-products of all
+    rows on the device (``Context.o2m_start``), resident or streamed.  One population cannot be streamed this way (a fold stream needs
     K >= 2): ``PPLSi`` on a plain stream is that fit."""
     streamed = _meta_streamed(ctx, X, Ipopu)
     if streamed:
@@ -1593,6 +1704,10 @@ def meta_PPLSi(X, Y, Ipopu, EMsteps=100, atol=1e-4, initialGuess=("equal", "o2m"
                     sigH=g["sigH"], sigT=g["sigT"])
     elif kind == "o2m":
         init = o2m_guess_from_gram(_joint_gram(ctx), ctx.n_total, ctx.p, ctx.q)   # :520-525
+    elif kind == "o2m_xprod":   # :520-525 from the cross-products of all rows (a fold stream: selection -1)
+        if streamed and ctx.stream_fold_info()["selected"] != -1:
+            ctx.stream_select(-1)
+        init = ctx.o2m_start()
     else:
         init = initial_guess(ctx.p, ctx.q, kind, rng if rng is not None else np.random.default_rng())
     if constraints:
@@ -2021,7 +2136,7 @@ def _cv_args(ppls_args):
     if kind == "o2m":
         raise NotImplementedError("initialGuess='o2m' inside cross-validation is not implemented "
                                   "(its starting values come from per-fold SVDs of the training rows)")
-    if kind not in ("equal", "random", "custom"):
+    if kind not in ("equal", "random", "custom", "o2m_xprod"):
         raise ValueError(f"unknown initialGuess {kind!r}")
     if kind == "custom" and custom is None:
         raise ValueError("initialGuess='custom' needs customGuess")
@@ -2068,8 +2183,10 @@ def _cv_run(ctx, a, nr_folds, folds, rng, ppls_args):
     N, K = int(ctx.n_total), int(nr_folds)
     fold_of = fold_labels(N, K, folds, rng)
     fold_total = np.bincount(fold_of, minlength=K).astype(np.int64)
-    inits = _cv_inits(ctx, a, K, kind, custom, rng)
     lo = int(ctx.row0)
+    if kind == "o2m_xprod":   # the starts come from each training set's cross-products, on the device
+        return ctx.cv_ppls_o2m(a, fold_of[lo: lo + ctx.n_local], fold_total, steps, atol, crit_abs)
+    inits = _cv_inits(ctx, a, K, kind, custom, rng)
     return ctx.cv_ppls(a, fold_of[lo: lo + ctx.n_local], fold_total, steps, atol, inits, crit_abs)
 
 
@@ -2085,8 +2202,11 @@ def _cv_run_stream(ctx, a, nr_folds, folds, rng, ppls_args):
         raise ValueError(f"nr_folds={int(nr_folds)}, but the rows were streamed with {K} folds")
     if folds is not None:
         raise ValueError("folds= cannot be given: the folds are those the rows were streamed with")
-    inits = _cv_inits(ctx, a, K, kind, custom, rng)
-    rmsep, ncomp, cond = ctx.cv_ppls_stream(a, steps, atol, inits, crit_abs)
+    if kind == "o2m_xprod":
+        rmsep, ncomp, cond = ctx.cv_ppls_stream_o2m(a, steps, atol, crit_abs)
+    else:
+        inits = _cv_inits(ctx, a, K, kind, custom, rng)
+        rmsep, ncomp, cond = ctx.cv_ppls_stream(a, steps, atol, inits, crit_abs)
     with np.errstate(invalid="ignore"):
         bad = np.argwhere(np.abs(cond) * 64 * 2.0 ** -53 > _COND_LIMIT)
     for f, j in bad:
@@ -2110,8 +2230,9 @@ def cv_PPLS(X, Y, nr_comp, nr_folds, folds=None, rng=None, ctx=None, per_fold=Fa
     fit, cross-validated over nr_folds folds, averaged over the folds (``mean(err)``); with
     ``per_fold=True`` also the per-fold errors.  ``folds``: the permutation R's ``sample(N)`` would
     give, 0-based (default ``rng.permutation(N)``); fold i holds ``folds[cv_blocks(N, K) == i]``.
-    ``ppls_args``: PPLS's EMsteps, atol, initialGuess ('equal', 'random', 'custom'), customGuess,
-    critfunc; 'random' starts are drawn from ``rng`` fold by fold, component by component.  The folds
+    ``ppls_args``: PPLS's EMsteps, atol, initialGuess ('equal', 'random', 'custom', 'o2m_xprod'),
+    customGuess, critfunc; 'random' starts are drawn from ``rng`` fold by fold, component by component,
+    'o2m_xprod' starts come from each training set's cross-products on the device.  The folds
     run on the device (ppls_cv_ppls).  mse(x, y) = mean((x - y)^2) as in OmicsPLS.
     ``cv_PPLS(None, None, nr_comp, K, ctx=ctx)`` on a context streamed with ``nr_folds=K`` runs on
     the stream's folds from their cross-products (ppls_cv_ppls_stream): ``nr_folds`` must be that K

@@ -16,6 +16,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -25,6 +26,7 @@
 #include "ppls_kernels.h"
 #include "ppls_math.h"
 #include "ppls_cv.h"
+#include "ppls_o2m.h"
 #include "ppls_scale.h"
 #include "ppls_cvstream.h"
 #include "ppls_stream.h"
@@ -235,6 +237,15 @@ struct ppls_ctx {
   int64_t rs_cnt_len = 0;
   double* rs_part = nullptr;
   int64_t rs_part_len = 0;
+  // 'o2m_xprod' starting values (ppls_o2m.hip): option "o2m_path" (0 auto, 1 fused,
+  // 2 two-phase), the pass's device vectors [v (L) | d (rows) | u (rows) | z (L) | workspace], and the
+  // last start's record {side (0: rows = p, 1: rows = q), path, passes, fits} / {residual estimate, theta}
+  int o2m_path = 0;
+  double* o2m_buf = nullptr;
+  int64_t o2m_buf_len = 0;
+  int o2m_last[4] = {0, 0, 0, 0};
+  int seq_fits = 0;   // rank-1 device fits the last sequential loop (seq_fit) ran
+  double o2m_last_d[2] = {0, 0};
 };
 
 namespace {
@@ -1486,6 +1497,7 @@ void ppls_ctx_destroy(ppls_ctx* c) {
   dfree(c->gram_q);
   dfree(c->rs_cnt);
   dfree(c->rs_part);
+  dfree(c->o2m_buf);
   if (c->stop_mirror) (void)hipHostFree(c->stop_mirror);
   for (auto& e : c->ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (auto& e : c->ev_ar) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -1614,6 +1626,9 @@ int ppls_set_option(ppls_ctx* c, const char* key, int64_t value) {
     if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8)
       return fail(c, PPLS_E_ARG, "xprod_rw must be 0, 1, 2, 4 or 8");
     c->xprod_rw = (int)value;
+  } else if (!strcmp(key, "o2m_path")) {
+    if (value < 0 || value > 2) return fail(c, PPLS_E_ARG, "o2m_path must be 0 (auto), 1 (fused) or 2 (two-phase)");
+    c->o2m_path = (int)value;
   } else if (!strcmp(key, "timing")) {
     if (value < 0) return fail(c, PPLS_E_ARG, "timing must be >= 0");
     c->timing = (int)value;
@@ -2357,6 +2372,10 @@ int deflated_ssq(ppls_ctx* c, const std::vector<double>& Wp, int m, bool isx, do
   return rc;
 }
 
+using SeqStart = std::function<int(int, const std::vector<double>&, const std::vector<double>&, double, double, Rank1&)>;
+int seq_fit(ppls_ctx* c, int a, int max_steps, double atol, int crit_abs, const ppls_constraint* cons,
+            ppls_seq_fit* out, const SeqStart& start);
+
 }  // namespace
 
 extern "C" {
@@ -2369,16 +2388,50 @@ int ppls_ppls_ex(ppls_ctx* c, int a, int max_steps, double atol, int crit_abs, c
                  const ppls_constraint* cons, ppls_seq_fit* out) {
   if (!c) return PPLS_E_ARG;
   if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
-  if (!init || !out || !out->W || !out->C || !out->B || !out->sig) return fail(c, PPLS_E_ARG, "NULL argument");
+  if (!init) return fail(c, PPLS_E_ARG, "NULL argument");
+  const int p = c->p, q = c->q;
+  return seq_fit(c, a, max_steps, atol, crit_abs, cons, out,
+                 [&](int k, const std::vector<double>&, const std::vector<double>&, double, double, Rank1& t) {
+                   if (k < 0) {   // the loop's argument check, after its own
+                     for (int j = 0; j < a; ++j)
+                       if (!init[j].W || !init[j].C || !init[j].B || !init[j].sigT)
+                         return fail(c, PPLS_E_ARG, "init[%d] has NULL fields", j);
+                     return (int)PPLS_OK;
+                   }
+                   t.w.assign(init[k].W, init[k].W + p);
+                   t.c.assign(init[k].C, init[k].C + q);
+                   t.B = init[k].B[0];
+                   t.sigT = init[k].sigT[0];
+                   t.sigE = init[k].sigE;
+                   t.sigF = init[k].sigF;
+                   t.sigH = init[k].sigH;
+                   return (int)PPLS_OK;
+                 });
+}
+
+}  // extern "C"
+
+namespace {
+
+// PPLS's loop (EM_W_multi.R:229-279) behind ppls_ppls_ex and ppls_ppls_o2m: start(k, Wp, Cp, ssqX,
+// ssqY, t) supplies component k's starting values, given the fitted loadings w_1..w_k, c_1..c_k
+// (column-major) and ||Xc||^2, ||Yc||^2 of the data they deflate.
+int seq_fit(ppls_ctx* c, int a, int max_steps, double atol, int crit_abs, const ppls_constraint* cons,
+            ppls_seq_fit* out, const SeqStart& start) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  if (!out || !out->W || !out->C || !out->B || !out->sig) return fail(c, PPLS_E_ARG, "NULL argument");
   if (a < 1 || a > PPLS_RMAX) return fail(c, PPLS_E_ARG, "nr_comp=%d outside [1,%d]", a, PPLS_RMAX);
   if (c->p < a || c->q < a)   // stopifnot(ncol(X) >= nr_comp, ncol(Y) >= nr_comp) (:245)
     return fail(c, PPLS_E_ARG, "ncol(X)=%d, ncol(Y)=%d must be >= number of components %d", c->p, c->q, a);
   if (max_steps < 1) return fail(c, PPLS_E_ARG, "EMsteps must be >= 1");
   int rc;
   if ((rc = check_fit_data(c))) return rc;
-  for (int k = 0; k < a; ++k)
-    if (!init[k].W || !init[k].C || !init[k].B || !init[k].sigT)
-      return fail(c, PPLS_E_ARG, "init[%d] has NULL fields", k);
+  {
+    Rank1 none;
+    static const std::vector<double> empty;
+    if ((rc = start(-1, empty, empty, 0.0, 0.0, none))) return rc;   // the start's own argument check
+  }
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = ensure_r(c, 1, max_steps))) return rc;
   // the rank-1 steps' statistics from the cross-products S (option xprod): the sweep's weights are
@@ -2402,17 +2455,12 @@ int ppls_ppls_ex(ppls_ctx* c, int a, int max_steps, double atol, int crit_abs, c
     return rc;
   out->ncomp = 0;
   out->not_monotone = 0;
+  c->seq_fits = 0;
   if (out->logvalue)
     for (size_t e = 0; e < (size_t)a * (max_steps + 1); ++e) out->logvalue[e] = NAN;
   for (int k = 0; k < a; ++k) {
     Rank1 t;
-    t.w.assign(init[k].W, init[k].W + p);
-    t.c.assign(init[k].C, init[k].C + q);
-    t.B = init[k].B[0];
-    t.sigT = init[k].sigT[0];
-    t.sigE = init[k].sigE;
-    t.sigF = init[k].sigF;
-    t.sigH = init[k].sigH;
+    if ((rc = start(k, Wp, Cp, ssqX, ssqY, t))) return rc;
     // PPLSi's constraints (fconstraint, :85-92): fixed values replace the estimates at the start
     // (:141-145) and after every EM step (:165-169)
     const ppls_constraint* ck = cons ? &cons[k] : nullptr;
@@ -2439,6 +2487,7 @@ int ppls_ppls_ex(ppls_ctx* c, int a, int max_steps, double atol, int crit_abs, c
     bool na = false;
     if ((rc = rank1_fit_device(c, dev, t, ck, k, ssqX, ssqY, max_steps, atol, crit_abs, Wp, Cp, lv, &i, &na, G)))
       return rc;
+    ++c->seq_fits;
     if (na) break;   // PPLS: "residuals are of rank < 1e-14", keep components 1..k-1 (:258-263)
     if (i > max_steps) i = max_steps;
     for (int e = 0; e < p; ++e) out->W[(size_t)k * p + e] = t.w[e];
@@ -2516,6 +2565,475 @@ int ppls_ppls_ex(ppls_ctx* c, int a, int max_steps, double atol, int crit_abs, c
       out->loglikelihoods[k] = ppls_loglik_from_gram(Gf.data(), c->ssq_host[0], c->ssq_host[1], N, p, q, r, &s);
     }
   }
+  return PPLS_OK;
+}
+
+// ---- 'o2m' starting values from the cross-products (initialGuess = "o2m_xprod") ----
+
+// The largest eigenpair (theta, s) of the symmetric tridiagonal matrix with diagonal al[0..m) and
+// off-diagonal be[0..m-1): theta by bisection on the Sturm count, s (unit) by three inverse
+// iterations through a row-pivoted tridiagonal elimination (a zero pivot is replaced by eps ||T||).
+void tridiag_top(const std::vector<double>& al, const std::vector<double>& be, int m, double* theta,
+                 std::vector<double>& s) {
+  s.assign((size_t)m, 1.0 / std::sqrt((double)m));
+  if (m == 1) {
+    *theta = al[0];
+    return;
+  }
+  double lo = al[0], hi = al[0];
+  for (int i = 0; i < m; ++i) {
+    const double rad = (i > 0 ? std::fabs(be[i - 1]) : 0.0) + (i + 1 < m ? std::fabs(be[i]) : 0.0);
+    lo = std::min(lo, al[i] - rad);
+    hi = std::max(hi, al[i] + rad);
+  }
+  const double scale = std::max(std::fabs(lo), std::fabs(hi));
+  const double tiny = std::max(scale * 2.220446049250313e-16, 1e-300);
+  auto below = [&](double x) {   // eigenvalues < x
+    int cnt = 0;
+    double qv = 1.0;
+    for (int i = 0; i < m; ++i) {
+      qv = al[i] - x - (i > 0 ? be[i - 1] * be[i - 1] / qv : 0.0);
+      if (qv == 0.0) qv = -tiny;
+      if (qv < 0.0) ++cnt;
+    }
+    return cnt;
+  };
+  hi += tiny;   // below(hi) == m, below(lo) < m
+  for (int it = 0; it < 200; ++it) {
+    const double mid = 0.5 * (lo + hi);
+    if (!(mid > lo && mid < hi)) break;
+    if (below(mid) == m) hi = mid; else lo = mid;
+  }
+  const double th = 0.5 * (lo + hi);
+  *theta = th;
+  std::vector<double> dl((size_t)m), dd((size_t)m), du((size_t)m), du2((size_t)m);
+  for (int round = 0; round < 3; ++round) {
+    for (int i = 0; i < m; ++i) {
+      dd[i] = al[i] - th;
+      dl[i] = du[i] = i + 1 < m ? be[i] : 0.0;
+      du2[i] = 0.0;
+    }
+    std::vector<double>& b = s;
+    for (int i = 0; i + 1 < m; ++i) {
+      if (std::fabs(dd[i]) >= std::fabs(dl[i])) {
+        if (dd[i] == 0.0) dd[i] = tiny;
+        const double mult = dl[i] / dd[i];
+        dd[i + 1] -= mult * du[i];
+        b[i + 1] -= mult * b[i];
+      } else {   // rows i, i + 1 change places
+        const double mult = dd[i] / dl[i];
+        dd[i] = dl[i];
+        const double tmp = dd[i + 1];
+        dd[i + 1] = du[i] - mult * tmp;
+        if (i + 2 < m) {
+          du2[i] = du[i + 1];
+          du[i + 1] = -mult * du2[i];
+        }
+        du[i] = tmp;
+        const double tb = b[i];
+        b[i] = b[i + 1];
+        b[i + 1] = tb - mult * b[i + 1];
+      }
+    }
+    if (dd[m - 1] == 0.0) dd[m - 1] = tiny;
+    b[m - 1] /= dd[m - 1];
+    b[m - 2] = (b[m - 2] - du[m - 2] * b[m - 1]) / dd[m - 2];
+    for (int i = m - 3; i >= 0; --i) b[i] = (b[i] - du[i] * b[i + 1] - du2[i] * b[i + 2]) / dd[i];
+    double big = 0.0;
+    for (int i = 0; i < m; ++i) big = std::max(big, std::fabs(b[i]));
+    if (!(big > 0.0) || !std::isfinite(big)) {
+      s.assign((size_t)m, 1.0 / std::sqrt((double)m));
+      return;
+    }
+    double nn = 0.0;
+    for (int i = 0; i < m; ++i) {
+      b[i] /= big;
+      nn += b[i] * b[i];
+    }
+    nn = std::sqrt(nn);
+    for (int i = 0; i < m; ++i) b[i] /= nn;
+  }
+}
+
+double hdot(const double* a, const double* b, int n) {
+  double s = 0.0;
+  for (int i = 0; i < n; ++i) s += a[i] * b[i];
+  return s;
+}
+
+// The block of S the passes read and what the loop keeps from component to component.
+struct O2mState {
+  int side = 0;   // 0: q <= p, A = S[0:p, ldx:ldx+q]; 1: A = S[ldx:ldx+q, 0:p]
+  int rows = 0, L = 0;
+  int64_t row0 = 0, col0 = 0;
+  std::vector<double> AW;   // A'l_j (L each) for the left deflation vectors l_1.. seen so far
+  int kdone = 0;
+};
+
+void o2m_shape(const ppls_ctx* c, O2mState& st) {
+  st.side = c->q <= c->p ? 0 : 1;
+  st.rows = st.side ? c->q : c->p;
+  st.L = st.side ? c->p : c->q;
+  st.row0 = st.side ? c->ldx : 0;
+  st.col0 = st.side ? 0 : c->ldx;
+}
+
+inline int64_t even_up(int64_t n) { return (n + 1) & ~(int64_t)1; }
+
+int o2m_ensure_buf(ppls_ctx* c, int rows, int L) {
+  const int64_t need = 2 * even_up(L) + 2 * even_up(rows) + ppls_o2m_ws_doubles(rows, L, c->num_cus);
+  if (c->o2m_buf && c->o2m_buf_len >= need) return PPLS_OK;
+  int rc;
+  c->o2m_buf_len = 0;
+  if ((rc = dalloc(c, &c->o2m_buf, (size_t)need))) return rc;
+  c->o2m_buf_len = need;
+  return PPLS_OK;
+}
+
+// One pass over A (rows x L at (row0, col0) of S, row stride ld) with host vectors: v (L), d (rows, or
+// NULL = 0) in; u (rows) and z (L) out, either nullable.
+int o2m_pass_host(ppls_ctx* c, const double* S, int64_t ld, const O2mState& st, const double* v, const double* d,
+                  double* u, double* z, int* path) {
+  int rc;
+  if ((rc = o2m_ensure_buf(c, st.rows, st.L))) return rc;
+  double* dv = c->o2m_buf;
+  double* dd = dv + even_up(st.L);
+  double* du = dd + even_up(st.rows);
+  double* dz = du + even_up(st.rows);
+  double* ws = dz + even_up(st.L);
+  HIPCHK(c, hipMemcpyAsync(dv, v, sizeof(double) * st.L, hipMemcpyHostToDevice, c->stream));
+  if (d) HIPCHK(c, hipMemcpyAsync(dd, d, sizeof(double) * st.rows, hipMemcpyHostToDevice, c->stream));
+  int pth = 0;
+  const hipError_t e = ppls_launch_o2m_pass(S, ld, st.row0, st.col0, st.rows, st.L, dv, d ? dd : nullptr, du, dz, ws,
+                                            c->num_cus, c->o2m_path, &pth, c->stream);
+  if (e == hipErrorInvalidValue)
+    return fail(c, PPLS_E_ARG, "o2m pass over %d x %d (o2m_path=%d): the fused path holds rows of at most %d values, "
+                "and the block must start at an even column of rows of even length", st.rows, st.L, c->o2m_path,
+                PPLS_O2M_FUSED_LMAX);
+  HIPCHK(c, e);
+  if (u) HIPCHK(c, hipMemcpyAsync(u, du, sizeof(double) * st.rows, hipMemcpyDeviceToHost, c->stream));
+  if (z) HIPCHK(c, hipMemcpyAsync(z, dz, sizeof(double) * st.L, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (path) *path = pth;
+  return PPLS_OK;
+}
+
+// PPLSi's 'o2m' start (:126-131) for the data deflated by the k loadings Wp (p x k), Cp (q x k), from
+// the context's S (ready); ssqX, ssqY = ||Xc||^2, ||Yc||^2 of that deflation.
+int o2m_start_core(ppls_ctx* c, O2mState& st, const std::vector<double>& Wp, const std::vector<double>& Cp, int k,
+                   double ssqX, double ssqY, Rank1& t) {
+  int rc;
+  const int p = c->p, q = c->q, rows = st.rows, L = st.L;
+  const int64_t P = (int64_t)c->ldx + c->ldy;
+  const double* S = c->xp_S;
+  const std::vector<double>& Lv = st.side ? Cp : Wp;   // deflation of A's rows (rows x k)
+  const std::vector<double>& Rv = st.side ? Wp : Cp;   // ... of its columns (L x k)
+  int path = 0;
+  // A'l_j: one pass with v = 0, d = -l_j (u = l_j, z = A'l_j), kept across components
+  {
+    std::vector<double> zero((size_t)L, 0.0), neg((size_t)rows);
+    for (int j = st.kdone; j < k; ++j) {
+      for (int i = 0; i < rows; ++i) neg[i] = -Lv[(size_t)j * rows + i];
+      st.AW.resize((size_t)(j + 1) * L);
+      if ((rc = o2m_pass_host(c, S, P, st, zero.data(), neg.data(), nullptr, st.AW.data() + (size_t)j * L, &path)))
+        return rc;
+    }
+    st.kdone = k;
+  }
+  // P_k .. P_1 = I - Lv T Lv' (T lower triangular: row j = -(l_j'Lv_{<j}) T_{<j}, T_jj = 1), so
+  // (P_k .. P_1)'(P_k .. P_1) = I - Lv T' Lv' with T' = T + T' - T'(Lv'Lv)T
+  std::vector<double> Tp((size_t)k * k, 0.0);
+  if (k > 0) {
+    std::vector<double> G((size_t)k * k), T((size_t)k * k, 0.0), GT((size_t)k * k, 0.0);
+    for (int i = 0; i < k; ++i)
+      for (int j = 0; j < k; ++j) G[(size_t)i * k + j] = hdot(&Lv[(size_t)i * rows], &Lv[(size_t)j * rows], rows);
+    for (int j = 0; j < k; ++j) {
+      T[(size_t)j * k + j] = 1.0;
+      for (int e = 0; e < j; ++e) {
+        double sacc = 0.0;
+        for (int i = e; i < j; ++i) sacc += G[(size_t)j * k + i] * T[(size_t)i * k + e];
+        T[(size_t)j * k + e] = -sacc;
+      }
+    }
+    for (int i = 0; i < k; ++i)
+      for (int j = 0; j < k; ++j) {
+        double sacc = 0.0;
+        for (int e = 0; e < k; ++e) sacc += G[(size_t)i * k + e] * T[(size_t)e * k + j];
+        GT[(size_t)i * k + j] = sacc;
+      }
+    for (int i = 0; i < k; ++i)
+      for (int j = 0; j < k; ++j) {
+        double sacc = 0.0;
+        for (int e = 0; e < k; ++e) sacc += T[(size_t)e * k + i] * GT[(size_t)e * k + j];
+        Tp[(size_t)i * k + j] = T[(size_t)i * k + j] + T[(size_t)j * k + i] - sacc;
+      }
+  }
+  std::vector<double> vp((size_t)L), dvec((size_t)rows), h((size_t)std::max(k, 1)), g((size_t)std::max(k, 1));
+  // v' = Q_1 .. Q_k y and d = Lv T' (A'Lv)' v'
+  auto stage = [&](const double* y) {
+    std::copy(y, y + L, vp.begin());
+    deflate(Rv, k, L, vp.data(), false);
+    if (k == 0) return;
+    for (int j = 0; j < k; ++j) h[j] = hdot(&st.AW[(size_t)j * L], vp.data(), L);
+    for (int i = 0; i < k; ++i) {
+      g[i] = 0.0;
+      for (int j = 0; j < k; ++j) g[i] += Tp[(size_t)i * k + j] * h[j];
+    }
+    std::fill(dvec.begin(), dvec.end(), 0.0);
+    for (int j = 0; j < k; ++j)
+      for (int i = 0; i < rows; ++i) dvec[i] += g[j] * Lv[(size_t)j * rows + i];
+  };
+  // out = M'M y, one pass
+  auto apply = [&](const double* y, double* out) {
+    stage(y);
+    int r2 = o2m_pass_host(c, S, P, st, vp.data(), k ? dvec.data() : nullptr, nullptr, out, &path);
+    if (r2) return r2;
+    deflate(Rv, k, L, out, true);
+    return (int)PPLS_OK;
+  };
+  // symmetric Lanczos with full reorthogonalisation (twice) against the kept basis
+  constexpr int CAP = 200;
+  std::vector<std::vector<double>> Q;
+  Q.emplace_back((size_t)L, 1.0 / std::sqrt((double)L));
+  std::vector<double> al, be, s, r((size_t)L);
+  double theta = 0.0, est = 0.0;
+  int passes = 0;
+  for (int m = 1;; ++m) {
+    if ((rc = apply(Q[(size_t)m - 1].data(), r.data()))) return rc;
+    ++passes;
+    const double alpha = hdot(Q[(size_t)m - 1].data(), r.data(), L);
+    al.push_back(alpha);
+    for (int i = 0; i < L; ++i) r[i] -= alpha * Q[(size_t)m - 1][i];
+    if (m > 1)
+      for (int i = 0; i < L; ++i) r[i] -= be[(size_t)m - 2] * Q[(size_t)m - 2][i];
+    for (int twice = 0; twice < 2; ++twice)
+      for (int j = 0; j < m; ++j) {
+        const double dj = hdot(Q[(size_t)j].data(), r.data(), L);
+        for (int i = 0; i < L; ++i) r[i] -= dj * Q[(size_t)j][i];
+      }
+    const double beta = std::sqrt(hdot(r.data(), r.data(), L));
+    tridiag_top(al, be, m, &theta, s);
+    est = std::fabs(beta * s[(size_t)m - 1]);
+    if (!std::isfinite(theta) || !std::isfinite(beta))
+      return fail(c, PPLS_E_NUMERIC, "o2m start: the cross block of S is not finite (theta = %g after %d passes)", theta,
+                  passes);
+    if (est <= std::ldexp(theta, -43) || m == L) break;
+    if (m == CAP) {
+      if (est <= std::ldexp(theta, -26)) break;   // a starting value: accepted
+      return fail(c, PPLS_E_NUMERIC, "o2m start: no first singular pair after %d passes (residual estimate %g, theta %g)",
+                  CAP, est, theta);
+    }
+    be.push_back(beta);
+    Q.emplace_back((size_t)L);
+    for (int i = 0; i < L; ++i) Q.back()[i] = r[i] / beta;
+  }
+  c->o2m_last[0] = st.side;
+  c->o2m_last[1] = path;
+  c->o2m_last[2] = passes;
+  c->o2m_last_d[0] = est;
+  c->o2m_last_d[1] = theta;
+  // sigma_1 within rounding of ||X|| ||Y||: nothing of X'Y is left
+  if (!(theta > std::ldexp(c->ssq_host[0], -52) * std::ldexp(c->ssq_host[1], -52)))
+    return fail(c, PPLS_E_NUMERIC, "o2m start: the deflated X'Y vanishes (its largest squared singular value is %g "
+                "against ssq(X) ssq(Y) = %g): no first singular pair to start from", theta,
+                c->ssq_host[0] * c->ssq_host[1]);
+  const int m = (int)al.size();
+  std::vector<double> y((size_t)L, 0.0), x((size_t)rows);
+  for (int j = 0; j < m; ++j)
+    for (int i = 0; i < L; ++i) y[i] += s[(size_t)j] * Q[(size_t)j][i];
+  const double ny = std::sqrt(hdot(y.data(), y.data(), L));
+  for (int i = 0; i < L; ++i) y[i] /= ny;
+  // the other side: x = M y / ||M y||, M y = P_k .. P_1 A Q_1 .. Q_k y (one more pass, d = 0)
+  stage(y.data());
+  if ((rc = o2m_pass_host(c, S, P, st, vp.data(), nullptr, x.data(), nullptr, &path))) return rc;
+  deflate(Lv, k, rows, x.data(), true);
+  const double nx = std::sqrt(hdot(x.data(), x.data(), rows));
+  if (!(nx > 0.0)) return fail(c, PPLS_E_NUMERIC, "o2m start: the deflated X'Y vanishes on its first right singular vector");
+  for (int i = 0; i < rows; ++i) x[i] /= nx;
+  t.w = st.side ? y : x;
+  t.c = st.side ? x : y;
+  // sign: W's entry of largest magnitude (lowest index on a tie) is positive, C follows
+  int big = 0;
+  for (int i = 1; i < p; ++i)
+    if (std::fabs(t.w[(size_t)i]) > std::fabs(t.w[(size_t)big])) big = i;
+  if (t.w[(size_t)big] < 0.0) {
+    for (double& e : t.w) e = -e;
+    for (double& e : t.c) e = -e;
+  }
+  // ssq(Tt), Tt'U, ssq(U) for Tt = Xc W., U = Yc C.: one rank-1 statistics step from S
+  t.B = t.sigE = t.sigF = t.sigH = t.sigT = 1.0;
+  double G[4];
+  std::vector<double> SX, SY;
+  const bool was = c->xp_active;
+  c->xp_active = true;
+  rc = rank1_sweep(c, t, Wp, Cp, k, SX, SY, G);
+  c->xp_active = was;
+  if (rc) return rc;
+  const double N = (double)c->n_total, sst = G[0], tu = G[1], ssu = G[3];
+  t.B = tu / sst;
+  t.sigE = std::sqrt((ssqX - sst) / N / p);
+  t.sigF = std::sqrt((ssqY - ssu) / N / q);
+  t.sigH = std::sqrt((ssu - t.B * t.B * sst) / N);
+  t.sigT = std::sqrt(sst / N);
+  return PPLS_OK;
+}
+
+// The checks and the S every 'o2m_xprod' entry needs: data, no open stream, S formed (and kept, as
+// after ppls_xprod_prepare) where the context holds rows only.
+int o2m_ready(ppls_ctx* c) {
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  if (c->st_state == 1) return fail(c, PPLS_E_STATE, "a stream is open: call ppls_stream_end first");
+  int rc;
+  if (!c->xp_ready || !c->xp_S) {
+    if ((rc = xprod_setup(c))) return rc;
+    c->xp_explicit = true;
+  }
+  return PPLS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ppls_o2m_start(ppls_ctx* c, const double* Wprev, const double* Cprev, int k, ppls_theta* out) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  if (c->st_state == 1) return fail(c, PPLS_E_STATE, "a stream is open: call ppls_stream_end first");
+  if (!out || !out->W || !out->C || !out->B || !out->sigT) return fail(c, PPLS_E_ARG, "NULL argument");
+  if (k < 0 || k > PPLS_RMAX - 1) return fail(c, PPLS_E_ARG, "k=%d earlier components outside [0,%d]", k, PPLS_RMAX - 1);
+  if (k > 0 && (!Wprev || !Cprev)) return fail(c, PPLS_E_ARG, "NULL argument");
+  int rc;
+  if ((rc = check_fit_data(c))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = ensure_r(c, 1, 1))) return rc;
+  if ((rc = o2m_ready(c))) return rc;
+  const int p = c->p, q = c->q;
+  std::vector<double> Wp, Cp;
+  if (k > 0) {
+    Wp.assign(Wprev, Wprev + (size_t)p * k);
+    Cp.assign(Cprev, Cprev + (size_t)q * k);
+  }
+  // ||X P_1 .. P_k||^2 as the sequential loop runs it: ||A (I - w w')||^2 = ||A||^2 - (2 - w'w) ||A w||^2
+  double ssqX = c->ssq_host[0], ssqY = c->ssq_host[1];
+  c->xp_active = true;
+  for (int j = 0; j < k && !rc; ++j) {
+    Rank1 u;
+    u.w.assign(Wp.begin() + (size_t)j * p, Wp.begin() + (size_t)(j + 1) * p);
+    u.c.assign(Cp.begin() + (size_t)j * q, Cp.begin() + (size_t)(j + 1) * q);
+    u.B = u.sigE = u.sigF = u.sigH = u.sigT = 1.0;
+    double G[4];
+    std::vector<double> SX, SY;
+    if ((rc = rank1_sweep(c, u, Wp, Cp, j, SX, SY, G))) break;
+    ssqX -= (2.0 - hdot(u.w.data(), u.w.data(), p)) * G[0];
+    ssqY -= (2.0 - hdot(u.c.data(), u.c.data(), q)) * G[3];
+  }
+  O2mState st;
+  o2m_shape(c, st);
+  Rank1 t;
+  if (!rc) rc = o2m_start_core(c, st, Wp, Cp, k, ssqX, ssqY, t);
+  c->xp_active = false;
+  if (rc) return rc;
+  std::copy(t.w.begin(), t.w.end(), out->W);
+  std::copy(t.c.begin(), t.c.end(), out->C);
+  out->B[0] = t.B;
+  out->sigT[0] = t.sigT;
+  out->sigE = t.sigE;
+  out->sigF = t.sigF;
+  out->sigH = t.sigH;
+  return PPLS_OK;
+}
+
+int ppls_ppls_o2m(ppls_ctx* c, int a, int max_steps, double atol, int crit_abs, const ppls_constraint* cons,
+                  ppls_seq_fit* out) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  if (c->st_state == 1) return fail(c, PPLS_E_STATE, "a stream is open: call ppls_stream_end first");
+  O2mState st;
+  c->o2m_last[3] = c->seq_fits = 0;
+  const int rc = seq_fit(c, a, max_steps, atol, crit_abs, cons, out,
+                         [&](int k, const std::vector<double>& Wp, const std::vector<double>& Cp, double ssqX, double ssqY,
+                             Rank1& t) {
+                           if (k < 0) return (int)PPLS_OK;
+                           int r2;
+                           if (k == 0) {
+                             if ((r2 = o2m_ready(c))) return r2;
+                             o2m_shape(c, st);
+                           }
+                           return o2m_start_core(c, st, Wp, Cp, k, ssqX, ssqY, t);
+                         });
+  c->o2m_last[3] = c->seq_fits;   // counted by the loop after each rank1_fit_device, not by the starts
+  return rc;
+}
+
+int ppls_o2m_pass(ppls_ctx* c, const double* S, int P, int ld, int row0, int col0, int rows, int L, const double* v,
+                  const double* d, double* u, double* z, int* path) {
+  if (!c) return PPLS_E_ARG;
+  if (!S || !v || !u || !z) return fail(c, PPLS_E_ARG, "NULL argument");
+  if (P < 1 || ld < 1 || rows < 1 || L < 1 || row0 < 0 || col0 < 0 || (int64_t)row0 + rows > P ||
+      (int64_t)col0 + even_up(L) > ld || (ld & 1) || (col0 & 1))
+    return fail(c, PPLS_E_ARG, "o2m pass: block %d x %d at (%d, %d) does not lie in %d rows of %d (even column start "
+                "and row length; L is rounded up to 2)", rows, L, row0, col0, P, ld);
+  HIPCHK(c, hipSetDevice(c->device));
+  double* Sd = nullptr;
+  int rc;
+  if ((rc = dalloc(c, &Sd, (size_t)P * ld))) return rc;
+  O2mState st;
+  st.rows = rows;
+  st.L = L;
+  st.row0 = row0;
+  st.col0 = col0;
+  hipError_t e = hipMemcpy(Sd, S, sizeof(double) * (size_t)P * ld, hipMemcpyHostToDevice);
+  if (e != hipSuccess) rc = fail(c, PPLS_E_HIP, "o2m pass upload: %s", hipGetErrorString(e));
+  if (!rc) rc = o2m_pass_host(c, Sd, ld, st, v, d, u, z, path);
+  (void)hipStreamSynchronize(c->stream);
+  dfree(Sd);
+  return rc;
+}
+
+int ppls_o2m_info(ppls_ctx* c, int* side, int* path, int* passes, double* resid, double* theta, int* fits) {
+  if (!c) return PPLS_E_ARG;
+  if (side) *side = c->o2m_last[0];
+  if (path) *path = c->o2m_last[1];
+  if (passes) *passes = c->o2m_last[2];
+  if (fits) *fits = c->o2m_last[3];
+  if (resid) *resid = c->o2m_last_d[0];
+  if (theta) *theta = c->o2m_last_d[1];
+  return PPLS_OK;
+}
+
+int ppls_o2m_pass_timing(ppls_ctx* c, int reps, double* ms, double* bytes, int* path) {
+  if (!c || reps < 1 || !ms) return PPLS_E_ARG;
+  if (!c->have_data || !c->xp_ready || !c->xp_S) return fail(c, PPLS_E_STATE, "the cross-products S are not formed");
+  HIPCHK(c, hipSetDevice(c->device));
+  O2mState st;
+  o2m_shape(c, st);
+  int rc;
+  const int64_t P = (int64_t)c->ldx + c->ldy;
+  std::vector<double> v((size_t)st.L, 1.0 / std::sqrt((double)st.L)), d((size_t)st.rows, 0.0);
+  int pth = 0;
+  if ((rc = o2m_pass_host(c, c->xp_S, P, st, v.data(), d.data(), nullptr, nullptr, &pth))) return rc;   // untimed
+  double* dv = c->o2m_buf;
+  double* dd = dv + even_up(st.L);
+  double* du = dd + even_up(st.rows);
+  double* dz = du + even_up(st.rows);
+  double* ws = dz + even_up(st.L);
+  hipEvent_t e0, e1;
+  HIPCHK(c, hipEventCreate(&e0));
+  HIPCHK(c, hipEventCreate(&e1));
+  hipError_t e = hipEventRecord(e0, c->stream);
+  for (int i = 0; e == hipSuccess && i < reps; ++i)
+    e = ppls_launch_o2m_pass(c->xp_S, P, st.row0, st.col0, st.rows, st.L, dv, dd, du, dz, ws, c->num_cus, c->o2m_path,
+                             nullptr, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(e1, c->stream);
+  if (e == hipSuccess) e = hipEventSynchronize(e1);
+  float tms = 0.f;
+  if (e == hipSuccess) e = hipEventElapsedTime(&tms, e0, e1);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  HIPCHK(c, e);
+  *ms = (double)tms / reps;
+  if (bytes) *bytes = 8.0 * st.rows * st.L;
+  if (path) *path = pth;
   return PPLS_OK;
 }
 
@@ -4610,12 +5128,14 @@ int ppls_heldout_sse(ppls_ctx* c, const double* W, const double* C, const double
   return PPLS_OK;
 }
 
-int ppls_cv_ppls(ppls_ctx* c, int a, int nfolds, const int32_t* fold_of_row, const int64_t* fold_total, int max_steps,
-                 double atol, int crit_abs, const ppls_theta* init, double* rmsep, int* ncomp) {
+// ppls_cv_ppls (o2m = false: init holds nfolds * a starting values) and ppls_cv_ppls_o2m (o2m = true: every
+// fold's fit is ppls_ppls_o2m on the training context's S).
+static int cv_ppls_impl(ppls_ctx* c, int a, int nfolds, const int32_t* fold_of_row, const int64_t* fold_total, int max_steps,
+                        double atol, int crit_abs, const ppls_theta* init, bool o2m, double* rmsep, int* ncomp) {
   if (!c) return PPLS_E_ARG;
   if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
   NEED_ROWS(c);
-  if (!fold_total || !init || !rmsep || !ncomp || (c->n_local > 0 && !fold_of_row)) return fail(c, PPLS_E_ARG, "NULL argument");
+  if (!fold_total || (!o2m && !init) || !rmsep || !ncomp || (c->n_local > 0 && !fold_of_row)) return fail(c, PPLS_E_ARG, "NULL argument");
   if (a < 1 || a > PPLS_RMAX) return fail(c, PPLS_E_ARG, "nr_comp=%d outside [1,%d]", a, PPLS_RMAX);
   if (nfolds < 2) return fail(c, PPLS_E_ARG, "Cross-validation with 1 fold does not make sense, use 2 folds or more");
   int64_t tot = 0;
@@ -4632,7 +5152,7 @@ int ppls_cv_ppls(ppls_ctx* c, int a, int nfolds, const int32_t* fold_of_row, con
   for (int f = 0; f < nfolds; ++f)
     if ((int64_t)in_fold[(size_t)f].size() > fold_total[f])
       return fail(c, PPLS_E_ARG, "fold %d: %zu local rows, %lld over all ranks", f, in_fold[(size_t)f].size(), (long long)fold_total[f]);
-  for (int k = 0; k < nfolds * a; ++k)
+  for (int k = 0; !o2m && k < nfolds * a; ++k)
     if (!init[k].W || !init[k].C || !init[k].B || !init[k].sigT) return fail(c, PPLS_E_ARG, "init[%d] has NULL fields", k);
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
@@ -4642,6 +5162,7 @@ int ppls_cv_ppls(ppls_ctx* c, int a, int nfolds, const int32_t* fold_of_row, con
   t->xprod = c->xprod;
   t->xprod_rw = c->xprod_rw;
   t->xprod_fuse = c->xprod_fuse;
+  t->o2m_path = c->o2m_path;
   if (t->gram_int8 && !c->gram_int8) {
     HIPCHK(c, hipStreamSynchronize(t->stream));
     oz_free(t);
@@ -4670,7 +5191,8 @@ int ppls_cv_ppls(ppls_ctx* c, int a, int nfolds, const int32_t* fold_of_row, con
     if ((rc = ppls_set_data_from(t, c, train.data(), (int64_t)train.size(), n_train))) { c->err = t->err; return rc; }
     // fits that read S get it as S - S_fold; a fold larger than its training set (2 uneven folds)
     // is past the downdate's error statement: ppls_ppls_ex then forms S from the training rows
-    if (xprod_choose(t, a * max_steps, 1) && fold_total[f] <= n_train)
+    // (the o2m_xprod start reads S whatever the fits read)
+    if ((o2m || xprod_choose(t, a * max_steps, 1)) && fold_total[f] <= n_train)
       if ((rc = ppls_xprod_downdate(t, c, out.data(), (int64_t)out.size()))) { c->err = t->err; return rc; }
     ppls_seq_fit fit;
     memset(&fit, 0, sizeof fit);
@@ -4679,7 +5201,8 @@ int ppls_cv_ppls(ppls_ctx* c, int a, int nfolds, const int32_t* fold_of_row, con
     fit.B = B.data();
     fit.sig = sig.data();
     const auto t0 = std::chrono::steady_clock::now();
-    rc = ppls_ppls_ex(t, a, max_steps, atol, crit_abs, init + (size_t)f * a, nullptr, &fit);
+    rc = o2m ? ppls_ppls_o2m(t, a, max_steps, atol, crit_abs, nullptr, &fit)
+             : ppls_ppls_ex(t, a, max_steps, atol, crit_abs, init + (size_t)f * a, nullptr, &fit);
     c->cv_ms[2] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (rc) { c->err = t->err; return rc; }
     ncomp[f] = fit.ncomp;
@@ -4691,6 +5214,16 @@ int ppls_cv_ppls(ppls_ctx* c, int a, int nfolds, const int32_t* fold_of_row, con
     for (int j = 0; j < fit.ncomp; ++j) rmsep[(size_t)f * a + j] = std::sqrt(sse[j] / ((double)fold_total[f] * q));
   }
   return PPLS_OK;
+}
+
+int ppls_cv_ppls(ppls_ctx* c, int a, int nfolds, const int32_t* fold_of_row, const int64_t* fold_total, int max_steps,
+                 double atol, int crit_abs, const ppls_theta* init, double* rmsep, int* ncomp) {
+  return cv_ppls_impl(c, a, nfolds, fold_of_row, fold_total, max_steps, atol, crit_abs, init, false, rmsep, ncomp);
+}
+
+int ppls_cv_ppls_o2m(ppls_ctx* c, int a, int nfolds, const int32_t* fold_of_row, const int64_t* fold_total, int max_steps,
+                     double atol, int crit_abs, double* rmsep, int* ncomp) {
+  return cv_ppls_impl(c, a, nfolds, fold_of_row, fold_total, max_steps, atol, crit_abs, nullptr, true, rmsep, ncomp);
 }
 
 int ppls_cv_timing(ppls_ctx* c, double* out6, int reset) {
@@ -5723,17 +6256,18 @@ int ppls_heldout_sse_fold(ppls_ctx* c, const double* W, const double* C, const d
   return PPLS_OK;
 }
 
-int ppls_cv_ppls_stream(ppls_ctx* c, int a, int max_steps, double atol, int crit_abs, const ppls_theta* init, double* rmsep,
-                        int* ncomp, double* cond) {
+// ppls_cv_ppls_stream (o2m = false: init holds K * a starting values) and ppls_cv_ppls_stream_o2m.
+static int cv_ppls_stream_impl(ppls_ctx* c, int a, int max_steps, double atol, int crit_abs, const ppls_theta* init, bool o2m,
+                               double* rmsep, int* ncomp, double* cond) {
   if (!c) return PPLS_E_ARG;
   int rc;
   if ((rc = fold_state_check(c))) return rc;
   if (c->em_active)
     return fail(c, PPLS_E_STATE, "an ppls_em_begin session is active on the selected cross-products: finish it before cross-validating");
-  if (!init || !rmsep || !ncomp) return fail(c, PPLS_E_ARG, "NULL argument");
+  if ((!o2m && !init) || !rmsep || !ncomp) return fail(c, PPLS_E_ARG, "NULL argument");
   if (a < 1 || a > PPLS_RMAX) return fail(c, PPLS_E_ARG, "nr_comp=%d outside [1,%d]", a, PPLS_RMAX);
   const int K = c->st_nfolds, p = c->p, q = c->q;
-  for (int k = 0; k < K * a; ++k)
+  for (int k = 0; !o2m && k < K * a; ++k)
     if (!init[k].W || !init[k].C || !init[k].B || !init[k].sigT) return fail(c, PPLS_E_ARG, "init[%d] has NULL fields", k);
   std::vector<double> W((size_t)p * a), C((size_t)q * a), B((size_t)a), sig((size_t)4 * a), sse((size_t)a), mag((size_t)a);
   auto run = [&]() -> int {
@@ -5747,7 +6281,9 @@ int ppls_cv_ppls_stream(ppls_ctx* c, int a, int max_steps, double atol, int crit
       fit.C = C.data();
       fit.B = B.data();
       fit.sig = sig.data();
-      if ((r = ppls_ppls_ex(c, a, max_steps, atol, crit_abs, init + (size_t)f * a, nullptr, &fit))) return r;
+      if ((r = o2m ? ppls_ppls_o2m(c, a, max_steps, atol, crit_abs, nullptr, &fit)
+                   : ppls_ppls_ex(c, a, max_steps, atol, crit_abs, init + (size_t)f * a, nullptr, &fit)))
+        return r;
       ncomp[f] = fit.ncomp;
       for (int j = 0; j < a; ++j) {
         rmsep[(size_t)f * a + j] = NAN;
@@ -5768,6 +6304,16 @@ int ppls_cv_ppls_stream(ppls_ctx* c, int a, int max_steps, double atol, int crit
   const int rs = fold_select(c, -1);
   if (rc) c->err = err;
   return rc ? rc : rs;
+}
+
+int ppls_cv_ppls_stream(ppls_ctx* c, int a, int max_steps, double atol, int crit_abs, const ppls_theta* init, double* rmsep,
+                        int* ncomp, double* cond) {
+  return cv_ppls_stream_impl(c, a, max_steps, atol, crit_abs, init, false, rmsep, ncomp, cond);
+}
+
+int ppls_cv_ppls_stream_o2m(ppls_ctx* c, int a, int max_steps, double atol, int crit_abs, double* rmsep, int* ncomp,
+                            double* cond) {
+  return cv_ppls_stream_impl(c, a, max_steps, atol, crit_abs, nullptr, true, rmsep, ncomp, cond);
 }
 
 int ppls_stream_fold_get(ppls_ctx* c, int fold, double* S, double* mean, int64_t* n) {
