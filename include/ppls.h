@@ -428,6 +428,30 @@ int ppls_xprod_downdate(ppls_ctx* dst, ppls_ctx* src, const int64_t* out_rows, i
  * rank with n_local = 0 takes part in the collectives. */
 int ppls_xprod_resample(ppls_ctx* dst, ppls_ctx* src, const int32_t* count /* host, src's n_local */);
 
+/* Permuted cross-products: dst's S becomes [X Y_pi]'[X Y_pi] with Y_pi[i, ] = Y[perm[i], ]
+ * over src's resident rows as they stand (scaled in place or not, either storage type) -- the S of a
+ * permutation replicate, which pairs x_i with another row's y and so destroys the X-Y link while keeping
+ * both margins.  The diagonal blocks X'X and Y'Y do not depend on perm: they are copied device to device
+ * from src's S, bit for bit (src's S is formed first, and kept, if it is not ready, as by
+ * ppls_xprod_downdate).  Only the p x q block C_pi = sum_i x_i y_perm[i]' is formed, by a rectangular fp64
+ * MFMA kernel over the rows where they lie (no copy of them, fixed-order sums: the same call gives the
+ * same bits), and written into both off-diagonal blocks from one value, so S is exactly symmetric and
+ * its padding zero.  perm: a permutation of this rank's 0 .. n_local - 1 (host), checked in O(n) before
+ * any device work; at most 2^31 - 1 local rows (more: PPLS_E_ARG).  Sharded, each rank permutes its own
+ * rows -- a permutation within shards, which is still an exact test under exchangeability of the rows --
+ * and the ranks all-reduce the ldx x ldy block alone, in the same order on every rank (src's stream and
+ * communicator or reducer); a rank with n_local = 0 takes part.  src is left as it was: rows, its own S,
+ * options, an open ppls_em_begin session.  dst ends "streamed" (ppls_stream_info state 2, rows_local 0,
+ * no folds): p, q, the paddings, the scaling record, n_total, ||X||^2 and ||Y||^2 are src's; every fit
+ * that reads only S runs on it and what needs rows is refused as on any streamed context.  A repeated
+ * call on the same dst of unchanged shape reuses dst's S (the diagonal blocks are not copied again while
+ * src's S is the same), its device index array and its partials, and ends an ppls_em_begin session of dst.
+ * PPLS_E_ARG: an entry out of range or repeated on any rank (every rank returns it: the flag rides in
+ * the agreement that precedes the collective), perm == NULL with n_local > 0, dst == src, contexts on
+ * different devices.  PPLS_E_STATE: src without data or streamed.  After such a refusal dst holds what it
+ * held before; an allocation or HIP error leaves dst without data, never with a half-formed S. */
+int ppls_xprod_permute(ppls_ctx* dst, ppls_ctx* src, const int64_t* perm /* host, src's n_local */);
+
 /* predict.PPLS (:12-24): xory 0 ("X") pred = newdata W diag(B) C' (n x q), xory 1 ("Y") pred =
  * newdata C diag(1/B) W' (n x p); W p x k, C q x k column-major, B k, with p, q the shape of the
  * data last loaded into ctx (newdata itself is independent of the resident rows: it is streamed
@@ -492,6 +516,7 @@ int ppls_cv_ppls_o2m(ppls_ctx* ctx, int a, int nfolds, const int32_t* fold_of_ro
  *     model with ppls_meta_emstep_stream / ppls_meta_ppls_stream instead); ppls_comm_init and
  *     ppls_set_reducer (set them before ppls_stream_begin); option "dtype";
  *   - ppls_xprod_resample leaves its dst in this state too (S_c of src's resampled rows, no stream);
+ *   - so does ppls_xprod_permute (S of src's rows with Y's permuted against X's, no stream);
  *   - ppls_xprod_release, ppls_set_data, ppls_generate_synthetic and ppls_stream_begin end the state
  *     (after ppls_xprod_release the context has no data).
  * While a stream is open (between begin and end) the context has no data: every fit and data entry

@@ -134,6 +134,16 @@ int ppls_gram(ppls_ctx* ctx, int xory, int nsplit, double* G, double* ms);
  * (count: n_local host counts >= 0, else PPLS_E_ARG), xory and nsplit as for ppls_gram -- the Gram of
  * the rows with row i repeated count_i times (ppls_xprod_resample). */
 int ppls_gram_weighted(ppls_ctx* ctx, int xory, int nsplit, const int32_t* count, double* G, double* ms);
+/* The permuted cross block alone: C (p x q column-major, nullable) = sum_i x_i y_perm[i]' over this rank's
+ * rows (perm: a permutation of 0 .. n_local - 1 on the host, else PPLS_E_ARG; nsplit 0 = auto, at most 64),
+ * *ms = the MFMA kernel's duration (ppls_xprod_permute). */
+int ppls_xgram_permuted(ppls_ctx* ctx, int nsplit, const int64_t* perm, double* C /* p x q col-major */, double* ms);
+/* Workgroups of that kernel one compute unit holds at once (storage type f32 0 / 1). */
+int ppls_xperm_occupancy(int f32);
+/* Wall-clock milliseconds of the last ppls_xprod_permute with ctx as dst: ms4 = {the host check of perm,
+ * staging and upload of the indices, kernel + finish (with the copy of the diagonal blocks when it was
+ * due), the whole call}. */
+int ppls_xperm_timing(ppls_ctx* ctx, double* ms4);
 /* Workgroups of the Gram kernel one compute unit holds at once: the unweighted instantiation for the
  * storage type (f32 0 / 1), which sizes the grid and the split plan, and the weighted one -- equal. */
 int ppls_gram_occupancy(int f32);

@@ -147,6 +147,10 @@ SIGNATURES = {
     "ppls_set_data_from": (ct.c_int, [ct.c_void_p, ct.c_void_p, _i64p, ct.c_int64, ct.c_int64]),
     "ppls_xprod_downdate": (ct.c_int, [ct.c_void_p, ct.c_void_p, _i64p, ct.c_int64]),
     "ppls_xprod_resample": (ct.c_int, [ct.c_void_p, ct.c_void_p, ct.POINTER(ct.c_int32)]),
+    "ppls_xprod_permute": (ct.c_int, [ct.c_void_p, ct.c_void_p, _i64p]),
+    "ppls_xgram_permuted": (ct.c_int, [ct.c_void_p, ct.c_int, _i64p, _dp, _dp]),
+    "ppls_xperm_occupancy": (ct.c_int, [ct.c_int]),
+    "ppls_xperm_timing": (ct.c_int, [ct.c_void_p, _dp]),
     "ppls_predict": (ct.c_int, [ct.c_void_p, _dp, _dp, _dp, ct.c_int, ct.c_int, _dp, ct.c_int64, ct.c_int, _dp]),
     "ppls_heldout_sse": (ct.c_int, [ct.c_void_p, _dp, _dp, _dp, ct.c_int, _i64p, ct.c_int64, _dp]),
     "ppls_cv_ppls": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(ct.c_int32), _i64p, ct.c_int,

@@ -989,6 +989,51 @@ class Context:
         self._stream_folds = None
 
     @staticmethod
+    def _perm(perm, n):
+        """A permutation of the ``n`` local rows as a contiguous int64 vector and its ctypes pointer (NULL
+        when empty); whether it is one is checked by the library."""
+        a = np.asarray(perm)
+        if a.ndim != 1 or a.shape[0] != n:
+            raise ValueError(f"perm: one index per local row ({n}), got shape {a.shape}")
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("perm must hold integers")
+        idx = np.ascontiguousarray(a, dtype=np.int64)
+        return idx, (idx.ctypes.data_as(ct.POINTER(ct.c_int64)) if idx.size else None)
+
+    def xprod_permute(self, src: "Context", perm):
+        """This context's cross-products := [X Y_pi]'[X Y_pi] with ``Y_pi[i] = Y[perm[i]]`` over ``src``'s
+        resident rows (ppls_xprod_permute): X'X and Y'Y are copied from ``src``'s S (formed and kept if it
+        is not there), the p x q block sum_i x_i y_perm[i]' comes from a rectangular MFMA kernel over the
+        rows where they lie.  ``perm``: a permutation of ``src``'s local rows 0 .. n_local - 1.  This
+        context ends streamed (S, no rows) with ``src``'s shape, scaling record, ``n_total`` and sums of
+        squares; ``src`` is left as it was.  Collective over ``src``'s ranks, each permuting its own rows."""
+        idx, ip = self._perm(perm, src.n_local)
+        self._chk(self._L.ppls_xprod_permute(self.h, src.h, ip))
+        self.p, self.q, self.n_local, self.row0 = src.p, src.q, 0, 0
+        self.n_total = self.stream_info()["n_total"]
+        self._stream_folds = None
+
+    def gram_permuted(self, perm, nsplit=0, want=True):
+        """sum_i x_i y_perm[i]' (p x q) on the permuted cross-block kernel alone, this rank's rows ->
+        (C or None, kernel ms) (ppls_xgram_permuted).  ``nsplit`` 0: the automatic row splits."""
+        idx, ip = self._perm(perm, self.n_local)
+        C = np.zeros((self.p, self.q), order="F") if want else None
+        ms = ct.c_double()
+        self._chk(self._L.ppls_xgram_permuted(self.h, int(nsplit), ip, dptr(C), ct.byref(ms)))
+        return C, ms.value
+
+    def xperm_timing(self):
+        """Wall-clock ms of the last ``xprod_permute`` into this context: dict(check, upload, kernel, total)
+        (ppls_xperm_timing)."""
+        ms = np.zeros(4)
+        self._chk(self._L.ppls_xperm_timing(self.h, dptr(ms)))
+        return dict(check=ms[0], upload=ms[1], kernel=ms[2], total=ms[3])
+
+    def xperm_occupancy(self, f32=False):
+        """Workgroups of the permuted cross-block kernel per compute unit, for fp64 or fp32 storage."""
+        return int(self._L.ppls_xperm_occupancy(int(bool(f32))))
+
+    @staticmethod
     def _fit_arrays(W, C, B):
         W = np.asfortranarray(np.array(W, dtype=np.float64, ndmin=2))
         C = np.asfortranarray(np.array(C, dtype=np.float64, ndmin=2))
@@ -1971,6 +2016,129 @@ def bootstrap_PPLS_simult(fit, X, Y, nboot=200, EMsteps=100, atol=1e-4, type="SV
         raise ValueError(f"bootstrap: {len(reps)} of {nboot} replicates succeeded, a standard error needs two")
     se, ci = bootstrap_summary(reps, level)
     out = dict(se=se, ci=ci, nboot=nboot, failed=failed, steps=steps)
+    if keep:
+        out["replicates"] = reps
+    return out
+
+
+# ---------------------------------------------------------------------------- permutation test
+def permutation_indices(N, nperm, rng=None):
+    """``nperm`` permutations of ``N`` rows: an ``(nperm, N)`` int64 array whose row b is
+    ``rng.permutation(N)``, R's ``sample(N)``.  ``rng``: a numpy Generator, or a seed for one."""
+    N, nperm = int(N), int(nperm)
+    if N < 1 or nperm < 0:
+        raise ValueError(f"permutation_indices: N = {N}, nperm = {nperm}")
+    rng = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+    out = np.empty((nperm, N), dtype=np.int64)
+    for b in range(nperm):
+        out[b] = rng.permutation(N)
+    return out
+
+
+_PERM_KEYS = ("B", "cov", "loglik")
+
+
+def permutation_pvalues(observed, null):
+    """Per component k, ``(1 + #{b : null[b, k] >= observed[k]}) / (1 + nperm_ok[k])``, with ``nperm_ok[k]``
+    the replicates whose ``null[b, k]`` is not NaN (a skipped replicate counts on neither side): the
+    permutation p-value that counts the observed statistic among its own null draws, never 0; a tie
+    counts against the observed value.  ``observed``: (a,), ``null``: (nperm, a).  NaN where no replicate
+    has a value, or the observed one is NaN."""
+    obs = np.atleast_1d(np.asarray(observed, dtype=np.float64))
+    nul = np.asarray(null, dtype=np.float64).reshape(-1, obs.shape[0])
+    ok = ~np.isnan(nul)
+    with np.errstate(invalid="ignore"):
+        ge = ok & (nul >= obs[None, :])
+    n_ok = ok.sum(axis=0)
+    pv = (1.0 + ge.sum(axis=0)) / (1.0 + n_ok)
+    pv[(n_ok == 0) | np.isnan(obs)] = np.nan
+    return pv
+
+
+def _perm_stats(fit, a):
+    """The sign-free statistics of a PPLS fit's first ``a`` components, NaN for components it did not reach."""
+    out = {k: np.full(a, np.nan) for k in _PERM_KEYS}
+    B = np.ravel(np.asarray(fit["B"], dtype=np.float64))
+    k = min(a, B.shape[0])
+    if k:
+        sig = np.asarray(fit["sig"], dtype=np.float64).reshape(-1, 4)
+        out["B"][:k] = np.abs(B[:k])
+        out["cov"][:k] = np.abs(B[:k]) * sig[:k, 3] ** 2
+        out["loglik"][:k] = np.asarray(fit["Other_output"]["Loglikelihoods"], dtype=np.float64)[:k]
+    return out
+
+
+def permutation_PPLS(fit, X, Y, nperm=199, EMsteps=100, atol=1e-4, initialGuess="o2m_xprod", rng=None, ctx=None,
+                     work=None, perms=None, keep=False):
+    """Permutation test of the X-Y link of a PPLS fit: is there any joint signal at all?  Replicate b
+    pairs x_i with y_perm[i], which keeps both margins and destroys the link; its cross-products differ
+    from the data's in the p x q block alone (``work.xprod_permute(ctx, perms[b])``, no copy of a row) and
+    the fit reads only them (``PPLS(None, None, a, EMsteps, atol, initialGuess, rng=rng, ctx=work)``).
+
+    ``fit``: the observed PPLS list, whose ``a = len(fit["B"])`` components are assessed.  ``X``, ``Y``: the
+    data, or ``None, None`` with ``ctx`` holding the rows.  Sharded, every rank calls this with its own
+    rows and passes ``perms``, its own permutations within its shard (still an exact test when the rows
+    are exchangeable).  ``perms`` (nperm x n_local integers): default
+    ``permutation_indices(N, nperm, rng)``.  ``work``: the replicate context (default: a new Context on
+    ``ctx``'s device, closed at the end).
+
+    Statistics per component k, sign-free, larger = a stronger link: ``"B"`` = |B_k|, ``"cov"`` =
+    |B_k| sigT_k^2, ``"loglik"`` = the fit's log-likelihood after component k.  X'X and Y'Y are the same
+    bits in every replicate, so differences in ``loglik`` come from the joint part alone.  Every
+    component is tested against the global null -- X and Y unlinked -- not against a null that keeps
+    the earlier components: this is not a sequential test.
+
+    Returns ``dict(observed, null, pvalue, nperm, failed, steps[, replicates])``: ``observed[key]`` (a,),
+    ``null[key]`` (nperm, a) with NaN where a replicate was skipped, ``pvalue[key]`` from
+    ``permutation_pvalues`` (never 0); ``failed`` the replicates whose fit raised PplsError or stopped
+    before component a (skipped for the components they did not reach; ValueError if none succeeds);
+    ``steps`` the EM steps per replicate, summed over its components (0 for one that raised);
+    ``replicates`` (``keep=True``) the replicate fits (None for one that raised)."""
+    ctx = _ctx_with(X, Y, ctx)
+    a = int(np.ravel(np.asarray(fit["B"])).shape[0])
+    if a < 1:
+        raise ValueError("permutation_PPLS: the fit has no component")
+    kind = initialGuess if isinstance(initialGuess, str) else initialGuess[0]
+    rng = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+    if perms is None:
+        if ctx.n_local != ctx.n_total:
+            raise ValueError("sharded rows: pass perms, this rank's own permutations within its shard")
+        perms = permutation_indices(ctx.n_total, nperm, rng)
+    perms = np.asarray(perms)
+    if perms.ndim != 2 or perms.shape[1] != ctx.n_local:
+        raise ValueError(f"perms: nperm x {ctx.n_local} (this rank's rows), got shape {perms.shape}")
+    nperm = perms.shape[0]
+    observed = _perm_stats(fit, a)
+    null = {k: np.full((nperm, a), np.nan) for k in _PERM_KEYS}
+    own = work is None
+    work = Context(ctx.device) if own else work
+    reps, failed, steps = [], [], []
+    try:
+        for b in range(nperm):
+            try:
+                work.xprod_permute(ctx, perms[b])
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")     # rank and monotonicity warnings, per replicate
+                    f = PPLS(None, None, a, EMsteps, atol, kind, rng=rng, ctx=work)
+            except PplsError:
+                failed.append(b)
+                steps.append(0)
+                reps.append(None)
+                continue
+            st = _perm_stats(f, a)
+            for k in _PERM_KEYS:
+                null[k][b] = st[k]
+            if len(f["B"]) < a:
+                failed.append(b)
+            steps.append(int(np.sum(f["Other_output"]["Number_steps"])))
+            reps.append(f)
+    finally:
+        if own:
+            work.close()
+    if not np.any(~np.isnan(null["B"])):
+        raise ValueError(f"permutation test: none of the {nperm} replicates succeeded")
+    out = dict(observed=observed, null=null, pvalue={k: permutation_pvalues(observed[k], null[k]) for k in _PERM_KEYS},
+               nperm=nperm, failed=failed, steps=steps)
     if keep:
         out["replicates"] = reps
     return out

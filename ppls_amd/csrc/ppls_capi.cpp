@@ -11,6 +11,7 @@
 #include <rocsolver/rocsolver.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -27,6 +28,7 @@
 #include "ppls_math.h"
 #include "ppls_cv.h"
 #include "ppls_o2m.h"
+#include "ppls_permute.h"
 #include "ppls_scale.h"
 #include "ppls_cvstream.h"
 #include "ppls_stream.h"
@@ -237,6 +239,19 @@ struct ppls_ctx {
   int64_t rs_cnt_len = 0;
   double* rs_part = nullptr;
   int64_t rs_part_len = 0;
+  // ppls_xprod_permute with this context as dst: the device array [row indices | padding |
+  // split bounds] with its host staging, the ldx x ldy block the ranks all-reduce, and the host byte map
+  // of the permutation check, kept from call to call (the split partials are rs_part).  xp_serial numbers
+  // every formation of xp_S; dst's diagonal blocks are src's while pm_self_serial is dst's own serial and
+  // pm_src_serial is src's.
+  int32_t* pm_idx = nullptr;
+  int64_t pm_idx_len = 0;
+  double* pm_blk = nullptr;
+  int64_t pm_blk_len = 0;
+  std::vector<int32_t> pm_host;
+  std::vector<uint8_t> pm_seen;
+  uint64_t xp_serial = 0, pm_self_serial = 0, pm_src_serial = 0;
+  double pm_ms[4] = {0, 0, 0, 0};   // the last permute, wall clock: check, staging + upload, kernel + finish, whole call
   // 'o2m_xprod' starting values (ppls_o2m.hip): option "o2m_path" (0 auto, 1 fused,
   // 2 two-phase), the pass's device vectors [v (L) | d (rows) | u (rows) | z (L) | workspace], and the
   // last start's record {side (0: rows = p, 1: rows = q), path, passes, fits} / {residual estimate, theta}
@@ -249,6 +264,8 @@ struct ppls_ctx {
 };
 
 namespace {
+
+std::atomic<uint64_t> g_xp_serial{0};   // one number per formation of any context's S (ppls_ctx::xp_serial)
 
 int fail(ppls_ctx* c, int code, const char* fmt, ...) {
   char buf[512];
@@ -1099,6 +1116,7 @@ int xprod_setup(ppls_ctx* c) {
   c->xp_setup_ar_ms = collective(c) ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count() : 0.0;
   c->xp_setup_total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   c->xp_ready = true;
+  c->xp_serial = ++g_xp_serial;
   return PPLS_OK;
 }
 
@@ -1497,6 +1515,8 @@ void ppls_ctx_destroy(ppls_ctx* c) {
   dfree(c->gram_q);
   dfree(c->rs_cnt);
   dfree(c->rs_part);
+  dfree(c->pm_idx);
+  dfree(c->pm_blk);
   dfree(c->o2m_buf);
   if (c->stop_mirror) (void)hipHostFree(c->stop_mirror);
   for (auto& e : c->ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -5039,6 +5059,7 @@ int ppls_xprod_downdate(ppls_ctx* dst, ppls_ctx* src, const int64_t* out_rows, i
   if (e == hipSuccess) e = hipStreamSynchronize(src->stream);
   if (e != hipSuccess) { dfree(dst->xp_S); return fail(dst, PPLS_E_HIP, "downdate of S: %s", hipGetErrorString(e)); }
   dst->xp_ready = true;
+  dst->xp_serial = ++g_xp_serial;
   dst->xp_explicit = true;   // given by the caller, like ppls_xprod_prepare's: kept until new data or release
   src->cv_ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - gather_ms;
   return PPLS_OK;
@@ -6015,6 +6036,7 @@ int ppls_stream_end(ppls_ctx* c) {
   c->n_local = 0;
   c->n_total = (int64_t)N;
   c->xp_ready = true;
+  c->xp_serial = ++g_xp_serial;
   c->xp_explicit = true;
   c->xp_active = false;
   c->em_active = false;
@@ -6192,8 +6214,282 @@ int ppls_xprod_resample(ppls_ctx* dst, ppls_ctx* src, const int32_t* count) {
   dst->sc_scale = src->sc_scale;
   dst->mem_free_min = src->mem_free_min;
   dst->xp_ready = true;
+  dst->xp_serial = ++g_xp_serial;
   dst->xp_explicit = true;
   dst->have_data = true;
+  return PPLS_OK;
+}
+
+}  // extern "C"
+
+// ============================================================================ permuted cross-products
+// A permutation replicate pairs x_i with y_pi(i): of S = [X Y_pi]'[X Y_pi] only the p x q block
+// C_pi = sum_i x_i y_pi(i)' depends on pi (ppls_permute.hip); X'X and Y'Y are src's, bit for bit.
+namespace {
+
+// perm must be a permutation of 0 .. n - 1: checked with a byte map, O(n), before any device work.
+int perm_check(ppls_ctx* c, const int64_t* perm, int64_t n, std::vector<uint8_t>& seen) {
+  if (n > 0x7fffffffLL)
+    return fail(c, PPLS_E_ARG, "%lld local rows: the permuted cross-products take at most 2^31 - 1 per rank", (long long)n);
+  if (n > 0 && !perm) return fail(c, PPLS_E_ARG, "NULL permutation for %lld local rows", (long long)n);
+  try {
+    seen.assign((size_t)n, 0);
+  } catch (const std::bad_alloc&) {
+    return fail(c, PPLS_E_NOMEM, "permutation check: no host memory for %lld bytes", (long long)n);
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t v = perm[i];
+    if (v < 0 || v >= n)
+      return fail(c, PPLS_E_ARG, "entry %lld of the permutation is %lld: out of range 0 .. %lld", (long long)i, (long long)v,
+                  (long long)(n - 1));
+    if (seen[(size_t)v])
+      return fail(c, PPLS_E_ARG, "entry %lld of the permutation repeats row %lld: not a permutation", (long long)i,
+                  (long long)v);
+    seen[(size_t)v] = 1;
+  }
+  return PPLS_OK;
+}
+
+// The kernel's plan over n rows of c: splits, and the device index array [n indices | padding | bounds].
+struct PermPlan {
+  int nsplit;
+  int64_t idx_len;   // int32 entries before the int64 bounds (even)
+  int64_t ints;      // the array's whole length in int32
+  int64_t part;      // doubles of split partials
+};
+
+PermPlan perm_plan(const ppls_ctx* c, int64_t n, int req) {
+  PermPlan pl;
+  const int slots = c->num_cus * ppls_xperm_occupancy(c->dtype) * 4;
+  pl.nsplit = n > 0 ? ppls_xperm_plan(c->p, c->q, n, slots, req, nullptr) : 1;
+  pl.idx_len = (n + PPLS_XPERM_PAD + 1) / 2 * 2;
+  pl.ints = pl.idx_len + 2 * (PPLS_XPERM_MAXSPLIT + 1);
+  pl.part = ppls_xperm_part_doubles(c->p, c->q, pl.nsplit);
+  return pl;
+}
+
+// host: the staged array (pl.ints entries) for perm (validated) over c's n rows.
+void perm_stage(const ppls_ctx* c, const PermPlan& pl, int64_t n, int req, const int64_t* perm, int32_t* host) {
+  for (int64_t i = 0; i < n; ++i) host[i] = (int32_t)perm[i];
+  for (int64_t i = n; i < pl.ints; ++i) host[i] = 0;
+  const int slots = c->num_cus * ppls_xperm_occupancy(c->dtype) * 4;
+  int64_t bounds[PPLS_XPERM_MAXSPLIT + 1] = {0};
+  if (n > 0) ppls_xperm_plan(c->p, c->q, n, slots, req, bounds);
+  memcpy(host + pl.idx_len, bounds, sizeof bounds);
+}
+
+// blk (device, ldx x ldy) = C_perm over c's n > 0 rows, on c's stream (not waited for): the MFMA kernel
+// into part over the uploaded array d_idx, then the finish.  e0, e1 (may be NULL): events around the kernel.
+hipError_t perm_run(ppls_ctx* c, const PermPlan& pl, int64_t n, int32_t* d_idx, double* part, double* blk, hipEvent_t e0,
+                    hipEvent_t e1) {
+  hipError_t e = hipSuccess;
+  if (e0) e = hipEventRecord(e0, c->stream);
+  if (e == hipSuccess)
+    e = ppls_launch_xperm(c->X, c->ldx, c->p, c->Y, c->ldy, c->q, c->dtype, n, d_idx, (const int64_t*)(d_idx + pl.idx_len),
+                          pl.nsplit, part, c->stream);
+  if (e == hipSuccess && e1) e = hipEventRecord(e1, c->stream);
+  if (e == hipSuccess) e = ppls_launch_xperm_finish(part, pl.nsplit, c->p, c->q, c->ldx, c->ldy, blk, c->stream);
+  return e;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ppls_xgram_permuted(ppls_ctx* c, int nsplit, const int64_t* perm, double* C, double* ms) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
+  if (nsplit < 0 || nsplit > PPLS_XPERM_MAXSPLIT)
+    return fail(c, PPLS_E_ARG, "nsplit must be 0 (auto) .. %d", PPLS_XPERM_MAXSPLIT);
+  if (c->n_local <= 0) return fail(c, PPLS_E_STATE, "no rows on this rank");
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  const int64_t n = c->n_local;
+  std::vector<uint8_t> seen;
+  if ((rc = perm_check(c, perm, n, seen))) return rc;
+  const PermPlan pl = perm_plan(c, n, nsplit);
+  struct Bufs {
+    int32_t* idx = nullptr;
+    double *part = nullptr, *blk = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~Bufs() {
+      dfree(idx); dfree(part); dfree(blk);
+      if (e0) (void)hipEventDestroy(e0);
+      if (e1) (void)hipEventDestroy(e1);
+    }
+  } b;
+  const size_t len = (size_t)c->ldx * c->ldy;
+  if ((rc = dalloc(c, &b.idx, (size_t)pl.ints)) || (rc = dalloc(c, &b.part, (size_t)pl.part)) || (rc = dalloc(c, &b.blk, len)))
+    return rc;
+  HIPCHK(c, hipEventCreate(&b.e0));
+  HIPCHK(c, hipEventCreate(&b.e1));
+  std::vector<int32_t> host((size_t)pl.ints);
+  perm_stage(c, pl, n, nsplit, perm, host.data());
+  hipError_t e = hipMemcpy(b.idx, host.data(), sizeof(int32_t) * (size_t)pl.ints, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = perm_run(c, pl, n, b.idx, b.part, b.blk, b.e0, b.e1);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  float t = 0.f;
+  if (e == hipSuccess) e = hipEventElapsedTime(&t, b.e0, b.e1);
+  if (e != hipSuccess) return fail(c, PPLS_E_HIP, "permuted cross block: %s", hipGetErrorString(e));
+  if (C) {
+    std::vector<double> full(len);
+    HIPCHK(c, hipMemcpy(full.data(), b.blk, sizeof(double) * len, hipMemcpyDeviceToHost));
+    for (int j = 0; j < c->q; ++j)
+      for (int a = 0; a < c->p; ++a) C[(size_t)j * c->p + a] = full[(size_t)j * c->ldx + a];
+  }
+  if (ms) *ms = t;
+  return PPLS_OK;
+}
+
+int ppls_xprod_permute(ppls_ctx* dst, ppls_ctx* src, const int64_t* perm) {
+  if (!dst || !src) return dst ? fail(dst, PPLS_E_ARG, "NULL source context") : PPLS_E_ARG;
+  if (dst == src) return fail(dst, PPLS_E_ARG, "source and destination are the same context");
+  if (!src->have_data) return fail(dst, PPLS_E_STATE, "the source context has no data");
+  if (src->st_state == 2) return fail(dst, PPLS_E_STATE, PPLS_STREAMED_MSG);
+  if (dst->device != src->device)
+    return fail(dst, PPLS_E_ARG, "contexts on different devices (%d, %d)", dst->device, src->device);
+  HIPCHK(dst, hipSetDevice(src->device));
+  int rc;
+  const bool coll = collective(src);
+  const int64_t n = src->n_local;
+  const int P = src->ldx + src->ldy;
+  const size_t PP = (size_t)P * P, BL = (size_t)src->ldx * src->ldy;
+  // this rank's verdict on its permutation joins the agreement below, so that ranks return together
+  typedef std::chrono::steady_clock Clock;
+  auto ms_since = [](Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); };
+  const auto t_call = Clock::now();
+  const int bad = perm_check(dst, perm, n, dst->pm_seen);
+  dst->pm_ms[0] = ms_since(t_call);
+  dst->pm_ms[1] = dst->pm_ms[2] = dst->pm_ms[3] = 0.0;
+  const std::string bad_err = dst->err;
+  if (bad && !coll) return bad;
+  // src's own S, formed and kept if it is not there (a collective of its own when sharded: every rank is here)
+  if ((rc = xprod_setup(src))) {
+    dst->err = src->err;
+    return rc;
+  }
+  // every allocation of the call before the ranks agree: a new S only when dst does not already hold
+  // streamed cross-products of this shape; the index array, the block and the partials only to grow
+  const bool reuse = dst->have_data && dst->st_state == 2 && dst->st_nfolds == 0 && dst->xp_ready && dst->xp_S &&
+                     dst->p == src->p && dst->q == src->q && dst->ldx == src->ldx && dst->ldy == src->ldy;
+  // (dst's diagonal blocks are already src's when its S is the one the last permute left, of this very S of src)
+  const bool keep_diag = reuse && dst->pm_self_serial == dst->xp_serial && dst->pm_src_serial == src->xp_serial;
+  const int64_t nrun = bad ? 0 : n;
+  const PermPlan pl = perm_plan(src, nrun, 0);
+  double* Snew = nullptr;
+  int rc_alloc = reuse ? PPLS_OK : dalloc(dst, &Snew, PP);
+  if (!rc_alloc && dst->pm_blk_len < (int64_t)BL) {
+    dst->pm_blk_len = 0;
+    if (!(rc_alloc = dalloc(dst, &dst->pm_blk, BL))) dst->pm_blk_len = (int64_t)BL;
+  }
+  if (!rc_alloc && nrun > 0) {
+    if (dst->rs_part_len < pl.part) {
+      dst->rs_part_len = 0;
+      if (!(rc_alloc = dalloc(dst, &dst->rs_part, (size_t)pl.part))) dst->rs_part_len = pl.part;
+    }
+    if (!rc_alloc && dst->pm_idx_len < pl.ints) {
+      dst->pm_idx_len = 0;
+      if (!(rc_alloc = dalloc(dst, &dst->pm_idx, (size_t)pl.ints))) dst->pm_idx_len = pl.ints;
+    }
+    if (!rc_alloc) {
+      try {
+        dst->pm_host.resize((size_t)pl.ints);
+      } catch (const std::bad_alloc&) {
+        rc_alloc = fail(dst, PPLS_E_NOMEM, "permuted S: no host memory for %lld row indices", (long long)pl.ints);
+      }
+    }
+  }
+  double f[2] = {rc_alloc ? 1.0 : 0.0, bad ? 1.0 : 0.0};
+  if (coll && (rc = agree(src, f, 2))) {
+    dfree(Snew);
+    dst->err = src->err;
+    return rc;
+  }
+  if (f[1] > 0.0) {   // a refusal: dst holds what it held (buffers that grew above are not its data)
+    dfree(Snew);
+    if (bad) dst->err = bad_err;
+    return bad ? bad : fail(dst, PPLS_E_ARG, "permuted S: %d other rank(s) passed a bad permutation", (int)f[1]);
+  }
+  if (f[0] > 0.0) {
+    dfree(Snew);
+    if (!rc_alloc) rc_alloc = fail(dst, PPLS_E_NOMEM, "permuted S: %d other rank(s) could not allocate it", (int)f[0]);
+    return resample_drop(dst, rc_alloc);
+  }
+  // From here dst ends streamed on S_pi, or without data.  Its own pending work first (an EM session may
+  // still read the S that is about to be overwritten); everything else runs on src's stream, behind
+  // whatever src has queued, and the sum over ranks goes through src's communicator.
+  int local = hipStreamSynchronize(dst->stream) == hipSuccess ? PPLS_OK : fail(dst, PPLS_E_HIP, "permute: dst's stream failed");
+  if (!reuse) {
+    if (!local) local = resample_adopt(dst, src, Snew);
+    else dfree(Snew);
+    Snew = nullptr;
+  } else {
+    meta_xp_free(dst);
+    dst->st_rows = dst->st_chunks = 0;
+  }
+  dst->have_data = false;
+  dst->em_active = false;
+  dst->xp_active = false;
+  dst->xp_pending_gram = false;
+  dst->pm_self_serial = 0;
+  if (!local && !keep_diag &&
+      hipMemcpyAsync(dst->xp_S, src->xp_S, sizeof(double) * PP, hipMemcpyDeviceToDevice, src->stream) != hipSuccess)
+    local = fail(dst, PPLS_E_HIP, "permute: copy of the source's S failed");
+  auto t_run = Clock::now();
+  if (!local && n > 0) {
+    perm_stage(src, pl, n, 0, perm, dst->pm_host.data());
+    hipError_t e = hipMemcpyAsync(dst->pm_idx, dst->pm_host.data(), sizeof(int32_t) * (size_t)pl.ints, hipMemcpyHostToDevice,
+                                  src->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(src->stream);
+    dst->pm_ms[1] = ms_since(t_run);
+    t_run = Clock::now();
+    if (e == hipSuccess) e = perm_run(src, pl, n, dst->pm_idx, dst->rs_part, dst->pm_blk, nullptr, nullptr);
+    if (e != hipSuccess) local = fail(dst, PPLS_E_HIP, "permuted cross block: %s", hipGetErrorString(e));
+  } else if (!local) {
+    if (hipMemsetAsync(dst->pm_blk, 0, sizeof(double) * BL, src->stream) != hipSuccess)
+      local = fail(dst, PPLS_E_HIP, "permute: zeroing the block failed");
+  }
+  if (!local && hipStreamSynchronize(src->stream) != hipSuccess)
+    local = fail(dst, PPLS_E_HIP, "permuted cross block: the kernel failed");
+  dst->pm_ms[2] = ms_since(t_run);
+  if (coll) {   // nobody enters the all-reduce of the block alone
+    double b = local ? 1.0 : 0.0;
+    if ((rc = agree(src, &b, 1))) {
+      dst->err = src->err;
+      return resample_drop(dst, rc);
+    }
+    if (b > 0.0 && !local) local = fail(dst, PPLS_E_HIP, "permuted S failed on %d other rank(s)", (int)b);
+  }
+  if (local) return resample_drop(dst, local);
+  if ((rc = allreduce(src, dst->pm_blk, BL))) {   // the ldx x ldy block only: the diagonal blocks are global already
+    dst->err = src->err;
+    return resample_drop(dst, rc);
+  }
+  hipError_t e = ppls_launch_xperm_scatter(dst->pm_blk, src->ldx, src->ldy, dst->xp_S, src->stream);
+  // ||X||^2, ||Y||^2 are src's: a permutation of rows changes neither
+  if (e == hipSuccess) e = hipMemcpyAsync(dst->ssq, src->ssq, 2 * sizeof(double), hipMemcpyDeviceToDevice, src->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(src->stream);
+  if (e != hipSuccess) return resample_drop(dst, fail(dst, PPLS_E_HIP, "permute: writing S: %s", hipGetErrorString(e)));
+  dst->ssq_host[0] = src->ssq_host[0];
+  dst->ssq_host[1] = src->ssq_host[1];
+  dst->n_total = src->n_total;
+  dst->sc_center = src->sc_center;   // the rows keep the transform they carry in src
+  dst->sc_scale = src->sc_scale;
+  dst->mem_free_min = src->mem_free_min;
+  dst->xp_ready = true;
+  dst->xp_serial = ++g_xp_serial;
+  dst->pm_self_serial = dst->xp_serial;
+  dst->pm_src_serial = src->xp_serial;
+  dst->xp_explicit = true;
+  dst->have_data = true;
+  dst->pm_ms[3] = ms_since(t_call);
+  return PPLS_OK;
+}
+
+int ppls_xperm_timing(ppls_ctx* c, double* ms4) {
+  if (!c || !ms4) return PPLS_E_ARG;
+  for (int i = 0; i < 4; ++i) ms4[i] = c->pm_ms[i];
   return PPLS_OK;
 }
 
