@@ -624,6 +624,36 @@ int ppls_cv_ppls_stream(ppls_ctx* ctx, int a, int max_steps, double atol, int cr
 int ppls_cv_ppls_stream_o2m(ppls_ctx* ctx, int a, int max_steps, double atol, int crit_abs, double* rmsep,
                             int* ncomp, double* cond);
 
+/* ---- row diagnostics: which rows does the fitted model not explain? ----------------------------
+ * For a row (x, y) and a PPLS_simult fit theta with orthonormal W, C: a = W'x, b = C'y and, per
+ * component k, s11 = sigT_k^2 + sigE^2, s12 = B_k sigT_k^2, s22 = B_k^2 sigT_k^2 + sigH^2 + sigF^2,
+ * det = s11 s22 - s12^2.  Then
+ *   odx2 = ||x - W a||^2, ody2 = ||y - C b||^2          (orthogonal distances, formed from the residual)
+ *   sd2  = sum_k (s22 a_k^2 - 2 s12 a_k b_k + s11 b_k^2) / det     (score distance)
+ *   d2   = odx2 / sigE^2 + ody2 / sigF^2 + sd2          (the row's summand of loglC_fast's traceL)
+ *   loglik = -(p+q)/2 log 2 pi - ((p-r) log sigE^2 + (q-r) log sigF^2 + sum_k log det_k)/2 - d2/2,
+ * whose sum over all rows is ppls_loglik's value; mu_T, mu_U are Expect_M's posterior means.  Under the
+ * model odx2/sigE^2, ody2/sigF^2, sd2 and d2 are chi-square with p-r, q-r, 2r and p+q degrees of
+ * freedom.  One kernel pass over the rows, read in place; a row's results are bitwise the same
+ * whatever the other rows, the subset, the shard or the entry point (fp64 storage).  Every array of
+ * ppls_row_diag is nullable.  PPLS_E_ARG, with the outputs untouched: r outside 1..16 or above
+ * min(p, q), a non-finite theta, sigE, sigF or a det_k not above 0, a row index out of range, NULL or
+ * non-finite rows. */
+typedef struct {
+  double *odx2, *ody2, *sd2, *d2, *loglik; /* nrows each */
+  double *mu_T, *mu_U;                     /* nrows x r column-major */
+} ppls_row_diag;
+/* This rank's resident rows, either storage type; no collective.  rows: local indices in any order,
+ * repeats allowed; NULL: all n_local rows (nrows is not read).  PPLS_E_STATE when the context holds
+ * no rows (streamed). */
+int ppls_row_diagnostics(ppls_ctx* ctx, const ppls_theta* th, int r, const int64_t* rows, int64_t nrows,
+                         ppls_row_diag* out);
+/* n host rows in the fit's units, staged through the device in blocks as ppls_predict stages them;
+ * the context supplies the device and the shape (p, q) only: streamed, replicate and empty contexts
+ * work, and the context's own data are not touched. */
+int ppls_row_diagnostics_new(ppls_ctx* ctx, const ppls_theta* th, int r, const double* X, const double* Y, int64_t n,
+                             int layout, ppls_row_diag* out);
+
 /* ---- host-side algebra (no GPU; the same code the device finalize runs) ------------------------ */
 /* From the all-reduced sufficient statistics of one sweep with theta (stats = [X'mu_T p x r |
  * Y'mu_U q x r | Gram 2r x 2r], all column-major) compute Expect_M's moments, logl_W(theta) and

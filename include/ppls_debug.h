@@ -226,6 +226,12 @@ int ppls_o2m_info(ppls_ctx* ctx, int* side, int* path, int* passes, double* resi
  * between HIP events after one untimed pass; *ms = the average, *bytes = the 8 rows L bytes of A. */
 int ppls_o2m_pass_timing(ppls_ctx* ctx, int reps, double* ms, double* bytes, int* path);
 
+/* Benchmark (tools/rowdiag_timing.py): the row diagnostics kernel over all local rows with r
+ * components, reps launches between HIP events after one untimed launch; ms[0] = the average
+ * without, ms[1] with the posterior means written.  Unit loadings and scalars (the time does not
+ * depend on the values); the results go to scratch of the call. */
+int ppls_rowdiag_timing(ppls_ctx* ctx, int r, int reps, double* ms /* [2] */);
+
 #ifdef __cplusplus
 }
 #endif

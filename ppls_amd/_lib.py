@@ -43,6 +43,10 @@ class PplsConstraint(ct.Structure):
                 ("sigT", _dp)]
 
 
+class PplsRowDiag(ct.Structure):
+    _fields_ = [("odx2", _dp), ("ody2", _dp), ("sd2", _dp), ("d2", _dp), ("loglik", _dp), ("mu_T", _dp), ("mu_U", _dp)]
+
+
 class PplsMetaFit(ct.Structure):
     _fields_ = [("W", _dp), ("C", _dp), ("params", _dp), ("log", _dp), ("steps", ct.c_int)]
 
@@ -153,6 +157,11 @@ SIGNATURES = {
     "ppls_xperm_timing": (ct.c_int, [ct.c_void_p, _dp]),
     "ppls_predict": (ct.c_int, [ct.c_void_p, _dp, _dp, _dp, ct.c_int, ct.c_int, _dp, ct.c_int64, ct.c_int, _dp]),
     "ppls_heldout_sse": (ct.c_int, [ct.c_void_p, _dp, _dp, _dp, ct.c_int, _i64p, ct.c_int64, _dp]),
+    "ppls_row_diagnostics": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsTheta), ct.c_int, _i64p, ct.c_int64,
+                                        ct.POINTER(PplsRowDiag)]),
+    "ppls_row_diagnostics_new": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsTheta), ct.c_int, _dp, _dp, ct.c_int64, ct.c_int,
+                                            ct.POINTER(PplsRowDiag)]),
+    "ppls_rowdiag_timing": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, _dp]),
     "ppls_cv_ppls": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(ct.c_int32), _i64p, ct.c_int,
                                 ct.c_double, ct.c_int, ct.POINTER(PplsTheta), _dp, ct.POINTER(ct.c_int)]),
     "ppls_cv_timing": (ct.c_int, [ct.c_void_p, _dp, ct.c_int]),

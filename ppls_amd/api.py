@@ -1075,6 +1075,81 @@ class Context:
                                            dptr(sse)))
         return sse
 
+    # -- row diagnostics
+    _ROWDIAG_GUARD = 8   # doubles behind every output buffer, NaN before the call and checked after it
+
+    def _rowdiag_out(self, n, r, want_mu):
+        """The output buffers of one diagnostics call: every one ``_ROWDIAG_GUARD`` doubles longer than the
+        library is told and filled with NaN, so that a refusal (nothing written) and a write past the
+        end can both be seen.  Kept on the context as ``_rowdiag_last`` until the next call."""
+        g = self._ROWDIAG_GUARD
+        bufs = {k: np.full(n + g, np.nan) for k in ("odx2", "ody2", "sd2", "d2", "loglik")}
+        if want_mu:
+            bufs["mu_T"] = np.full(n * r + g, np.nan)
+            bufs["mu_U"] = np.full(n * r + g, np.nan)
+        self._rowdiag_last = bufs
+        s = _lib.PplsRowDiag(*[dptr(bufs.get(k)) for k in ("odx2", "ody2", "sd2", "d2", "loglik", "mu_T", "mu_U")])
+        return bufs, s
+
+    def _rowdiag_result(self, bufs, n, r):
+        g = self._ROWDIAG_GUARD
+        out = {}
+        for k, b in bufs.items():
+            if not np.all(np.isnan(b[b.shape[0] - g:])):
+                raise PplsError(-1, f"row diagnostics wrote past the end of {k}")
+            out[k] = b[: n * r].reshape((n, r), order="F") if k in ("mu_T", "mu_U") else b[:n]
+        return out
+
+    def row_diagnostics(self, th: Theta, rows=None, want_mu=False):
+        """Per resident row of this rank (ppls_row_diagnostics): the orthogonal distances ``odx2``,
+        ``ody2``, the score distance ``sd2``, the squared Mahalanobis distance ``d2`` under the fitted
+        covariance and the log-density ``loglik`` (its sum over all rows is ``loglik(th)``); with
+        ``want_mu`` Expect_M's ``mu_T``, ``mu_U`` from the same read.  ``rows``: local indices in any
+        order, repeats allowed (default: all).  No collective; a row's values are bitwise the same in
+        any subset or shard."""
+        if rows is None:
+            n, rp = int(self.n_local), None
+        else:
+            rows, rp = self._rows(rows)
+            n = rows.shape[0]
+            if n == 0:
+                rp = None
+        bufs, s = self._rowdiag_out(n, th.r, want_mu)
+        t = th.struct()
+        if rows is not None and n == 0:   # an empty list is not "all rows"
+            return self._rowdiag_result(bufs, 0, th.r)
+        self._chk(self._L.ppls_row_diagnostics(self.h, ct.byref(t), th.r, rp, n, ct.byref(s)))
+        return self._rowdiag_result(bufs, n, th.r)
+
+    def row_diagnostics_new(self, th: Theta, X, Y, want_mu=False):
+        """The same for host rows ``X, Y`` in the fit's units (ppls_row_diagnostics_new): staged through
+        the device in blocks; the context gives the device and the shape only, so a streamed context
+        or one without rows serves, and its own data are not touched."""
+        X = np.asarray(X, dtype=np.float64)
+        Y = np.asarray(Y, dtype=np.float64)
+        if X.ndim != 2 or Y.ndim != 2 or X.shape[0] != Y.shape[0]:
+            raise ValueError("X and Y must be matrices with the same number of rows")
+        if X.shape[1] != self.p or Y.shape[1] != self.q:
+            raise ValueError("Number of columns mismatch!")
+        if X.flags.f_contiguous and Y.flags.f_contiguous and not (X.flags.c_contiguous and Y.flags.c_contiguous):
+            layout = _lib.PPLS_LAYOUT_COLMAJOR
+        else:
+            X = np.ascontiguousarray(X)
+            Y = np.ascontiguousarray(Y)
+            layout = _lib.PPLS_LAYOUT_ROWMAJOR
+        n = X.shape[0]
+        bufs, s = self._rowdiag_out(n, th.r, want_mu)
+        t = th.struct()
+        self._chk(self._L.ppls_row_diagnostics_new(self.h, ct.byref(t), th.r, dptr(X), dptr(Y), n, layout, ct.byref(s)))
+        return self._rowdiag_result(bufs, n, th.r)
+
+    def rowdiag_timing(self, r, reps=20):
+        """The diagnostics kernel alone over all local rows, ms between HIP events averaged over ``reps``
+        launches (ppls_rowdiag_timing): dict(ms, ms_mu) without and with the posterior means."""
+        ms = np.zeros(2)
+        self._chk(self._L.ppls_rowdiag_timing(self.h, int(r), int(reps), dptr(ms)))
+        return dict(ms=ms[0], ms_mu=ms[1])
+
     def cv_ppls(self, a: int, fold_of_row, fold_total, max_steps: int, atol: float, inits, crit_abs=False):
         """cv_PPLS's loop for given folds (ppls_cv_ppls).  ``fold_of_row``: the fold of each local
         row; ``fold_total``: rows per fold over all ranks; ``inits``: per fold a list of ``a``
@@ -2472,4 +2547,109 @@ def crossval_PPLS(X, Y, a, nr_folds, nr_cores=1, shared_folds=False, ctx=None, *
     which = int(np.nanargmin(errors)) if np.any(np.isfinite(errors)) else 0
     out = dict(errors=errors, which_error=which, a_min=a[which], time=round(time.perf_counter() - tic, 2))
     out["class"] = "cvPPLS"
+    return out
+
+
+# ---------------------------------------------------------------------------- row diagnostics
+_DIAG_STATS = ("odx2", "ody2", "sd2", "d2")
+
+
+def diagnostics_df(p, q, r):
+    """Degrees of freedom of the four distances under the model: odx2 / sigE^2 has p - r, ody2 / sigF^2
+    q - r, sd2 2r and d2 p + q."""
+    return dict(odx2=int(p) - int(r), ody2=int(q) - int(r), sd2=2 * int(r), d2=int(p) + int(q))
+
+
+def chisq_upper(x, df):
+    """Upper chi-square tail P(chi2_df > x) in fp64, never NaN for finite ``x``: 1 for ``df = 0`` (a
+    statistic without degrees of freedom is zero up to rounding) and for ``x <= 0``."""
+    import scipy.special
+    x = np.asarray(x, dtype=np.float64)
+    if df <= 0:
+        return np.ones_like(x)
+    return np.asarray(scipy.special.gammaincc(0.5 * df, 0.5 * np.maximum(x, 0.0)), dtype=np.float64)
+
+
+def diagnostics_summary(res, p, q, r, sigE, sigF, alpha=0.01, adjust="none"):
+    """``df``, ``pvalue``, ``flag`` and ``outliers`` from the distances of one diagnostics call (the host
+    part of ``diagnostics_PPLS``).  ``adjust="bonferroni"`` tests at ``alpha / n``, n the rows of this call."""
+    if adjust not in ("none", "bonferroni"):
+        raise ValueError("adjust should be one of \"none\", \"bonferroni\"")
+    n = int(np.asarray(res["d2"]).shape[0])
+    level = float(alpha) / n if adjust == "bonferroni" and n > 0 else float(alpha)
+    df = diagnostics_df(p, q, r)
+    stat = dict(odx2=np.asarray(res["odx2"]) / (float(sigE) * float(sigE)),
+                ody2=np.asarray(res["ody2"]) / (float(sigF) * float(sigF)), sd2=np.asarray(res["sd2"]),
+                d2=np.asarray(res["d2"]))
+    pv = {k: chisq_upper(stat[k], df[k]) for k in _DIAG_STATS}
+    flag = {k: pv[k] < level for k in _DIAG_STATS}
+    hit = np.flatnonzero(flag["d2"])
+    return dict(df=df, pvalue=pv, flag=flag, outliers=hit[np.argsort(pv["d2"][hit], kind="stable")])
+
+
+def diagnostics_PPLS(fit, X=None, Y=None, ctx=None, subset=None, new=False, rescale=False, alpha=0.01, adjust="none",
+                     want_mu=False):
+    """Which rows does a ``PPLS_simult`` fit not explain?  Per row, on the GPU in one pass over the rows:
+    the squared Mahalanobis distance ``d2`` under the fitted covariance, its in-plane part ``sd2`` (score
+    distance) and off-plane parts ``odx2``, ``ody2`` (squared orthogonal distances in X and Y) and the
+    log-density ``loglik``, which sums to ``logl_W``; with ``want_mu`` Expect_M's ``mu_T``, ``mu_U``.  On
+    the host: ``df``, upper chi-square ``pvalue`` and ``flag`` (``p < alpha``, or ``p < alpha / n`` with
+    ``adjust="bonferroni"``) per distance, and ``outliers``, the rows with ``flag["d2"]`` sorted by p.
+
+    ``fit``: a ``PPLS_simult`` fit or a ``Theta``.  ``X, Y`` given: loaded into the context and scored;
+    ``X=None``: the rows resident in ``ctx``; ``subset``: 0-based local row indices.  ``new=True``: ``X, Y``
+    are rows scored against the fit without touching the context's data (any context of the fit's shape:
+    streamed, or without rows); with ``rescale=True`` they come in the units the data were loaded in and
+    are brought to the fit's with ``ctx.scaling()`` on the host, as ``predict_PPLS`` does -- called once
+    per chunk this is the second pass that screens a ``stream_data`` fit."""
+    global _PREDICT_CTX
+    if adjust not in ("none", "bonferroni"):
+        raise ValueError("adjust should be one of \"none\", \"bonferroni\"")
+    if isinstance(fit, Theta):
+        th = fit
+    elif isinstance(fit, dict) and "estimates" in fit:
+        e = fit["estimates"]
+        th = Theta(e["W"], e["C"], e["B"], e["sigE"], e["sigF"], e["sigH"], e["sigT"])
+    else:
+        raise ValueError("diagnostics need one joint covariance: pass a PPLS_simult fit (or a Theta); the components "
+                         "of a sequential PPLS / PPLSi fit carry their own sigmas")
+    p, q, r = th.W.shape[0], th.C.shape[0], th.r
+    if new:
+        if X is None or Y is None:
+            raise ValueError("new=True needs the rows X and Y")
+        X = np.asarray(X, dtype=np.float64)
+        Y = np.asarray(Y, dtype=np.float64)
+        if X.ndim != 2:
+            X = X.reshape(1, -1)
+        if Y.ndim != 2:
+            Y = Y.reshape(1, -1)
+        if X.shape[1] != p or Y.shape[1] != q:
+            raise ValueError("Number of columns mismatch!")
+        if ctx is None:
+            ctx = _DEFAULT_CTX if _DEFAULT_CTX is not None and (_DEFAULT_CTX.p, _DEFAULT_CTX.q) == (p, q) else None
+        if ctx is None:
+            if _PREDICT_CTX is None:
+                _PREDICT_CTX = Context(0)
+            ctx = _PREDICT_CTX
+            if (ctx.p, ctx.q) != (p, q):
+                ctx.set_data(np.zeros((0, p)), np.zeros((0, q)))   # the shape only
+        if (ctx.p, ctx.q) != (p, q):
+            raise ValueError("Number of columns mismatch!")
+        if subset is not None:
+            idx = np.ravel(np.asarray(subset, dtype=np.int64))
+            X, Y = X[idx], Y[idx]
+        if rescale:
+            sc = ctx.scaling()
+            X = (X - sc["centerX"]) / sc["scaleX"]
+            Y = (Y - sc["centerY"]) / sc["scaleY"]
+        res = ctx.row_diagnostics_new(th, X, Y, want_mu=want_mu)
+    else:
+        if X is not None and (np.ndim(X) != 2 or np.ndim(Y) != 2 or np.shape(X)[1] != p or np.shape(Y)[1] != q):
+            raise ValueError("Number of columns mismatch!")
+        ctx = _ctx_with(X, Y, ctx)
+        if (ctx.p, ctx.q) != (p, q):
+            raise ValueError("Number of columns mismatch!")
+        res = ctx.row_diagnostics(th, rows=subset, want_mu=want_mu)
+    out = dict(res)
+    out.update(diagnostics_summary(res, p, q, r, th.sigE, th.sigF, alpha=alpha, adjust=adjust))
     return out

@@ -27,6 +27,7 @@
 #include "ppls_kernels.h"
 #include "ppls_math.h"
 #include "ppls_cv.h"
+#include "ppls_rowdiag.h"
 #include "ppls_o2m.h"
 #include "ppls_permute.h"
 #include "ppls_scale.h"
@@ -5146,6 +5147,218 @@ int ppls_heldout_sse(ppls_ctx* c, const double* W, const double* C, const double
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->cv_ms[3] += ev.ms();
   c->cv_bytes[1] += (double)nrows * (c->dtype ? 4.0 : 8.0) * ((double)c->p + c->q);
+  return PPLS_OK;
+}
+
+}  // extern "C"
+
+// ============================================================================ row diagnostics
+// Per row: the squared Mahalanobis distance under the fitted covariance, split into the in-plane
+// score distance and the two orthogonal distances, the log-density and Expect_M's posterior means
+// (ppls_rowdiag.hip).  The kernel writes odx2, ody2, sd2 (and mu); d2 and the
+// log-density follow here, O(n).
+namespace {
+
+struct RowDiagFit {
+  double *W = nullptr, *C = nullptr, *coef = nullptr;   // device: padded loadings, PPLS_ROWDIAG_COEF x 16
+  double sE2 = 1.0, sF2 = 1.0, cst = 0.0;               // loglik_i = cst - d2_i / 2
+};
+
+// Everything ppls_row_diagnostics{,_new} refuse about the fit, before any device work.
+int rowdiag_check_fit(ppls_ctx* c, const ppls_theta* th, int r, double (&h)[PPLS_ROWDIAG_COEF * 16], RowDiagFit& f) {
+  int rc;
+  if ((rc = check_theta(c, th, r))) return rc;
+  if (r > std::min(c->p, c->q)) return fail(c, PPLS_E_ARG, "r=%d components for %d x %d columns", r, c->p, c->q);
+  if (!theta_finite(th, c->p, c->q, r)) return fail(c, PPLS_E_ARG, "theta has non-finite entries");
+  const PplsScalars s = scalars_of(th, r);
+  f.sE2 = th->sigE * th->sigE;
+  f.sF2 = th->sigF * th->sigF;
+  memset(h, 0, sizeof h);
+  double logdet = 0.0;
+  for (int k = 0; k < r; ++k) {
+    const double t2 = th->sigT[k] * th->sigT[k], b = th->B[k];
+    const double s11 = t2 + f.sE2, s12 = b * t2, s22 = b * b * t2 + th->sigH * th->sigH + f.sF2;
+    // det = s11 s22 - s12^2 without the cancellation: every term is non-negative
+    const double det = t2 * (th->sigH * th->sigH + f.sF2) + f.sE2 * s22;
+    if (!(det > 0.0) || !std::isfinite(det))
+      return fail(c, PPLS_E_ARG, "component %d: the 2 x 2 score covariance has determinant %g, not above 0", k + 1, det);
+    h[0 * 16 + k] = s11; h[1 * 16 + k] = s12; h[2 * 16 + k] = s22; h[3 * 16 + k] = det;
+    h[4 * 16 + k] = s.alpha[k]; h[5 * 16 + k] = s.beta[k]; h[6 * 16 + k] = s.gamma[k]; h[7 * 16 + k] = s.delta[k];
+    logdet += std::log(det);
+  }
+  if (!(f.sE2 > 0.0) || !(f.sF2 > 0.0) || !std::isfinite(f.sE2) || !std::isfinite(f.sF2))
+    return fail(c, PPLS_E_ARG, "sigE^2 = %g, sigF^2 = %g must be positive and finite", f.sE2, f.sF2);
+  f.cst = -0.5 * ((double)(c->p + c->q) * std::log(6.283185307179586) + (double)(c->p - r) * std::log(f.sE2) +
+                  (double)(c->q - r) * std::log(f.sF2) + logdet);
+  return PPLS_OK;
+}
+
+int rowdiag_upload_fit(ppls_ctx* c, CvScratch& tmp, const ppls_theta* th, int r, const double (&h)[PPLS_ROWDIAG_COEF * 16],
+                       RowDiagFit& f) {
+  int rc;
+  if ((rc = cv_upload_coef(c, tmp, th->W, c->p, r, &f.W))) return rc;
+  if ((rc = cv_upload_coef(c, tmp, th->C, c->q, r, &f.C))) return rc;
+  return cv_upload_coef(c, tmp, h, PPLS_ROWDIAG_COEF * 16, 1, &f.coef);
+}
+
+// Device results of `count` rows (odx2 | ody2 | sd2, `count` each, then mu_T | mu_U with leading
+// dimension `count`) into the caller's arrays at row offset `at` of `n`.
+int rowdiag_collect(ppls_ctx* c, const RowDiagFit& f, const double* dres, const double* dmu, int64_t count, int r,
+                    int64_t at, int64_t n, ppls_row_diag* out) {
+  if (count <= 0) return PPLS_OK;
+  std::vector<double> h((size_t)3 * count);
+  HIPCHK(c, hipMemcpy(h.data(), dres, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+  const double *ox = h.data(), *oy = ox + count, *sd = oy + count;
+  for (int64_t i = 0; i < count; ++i) {
+    const double d2 = (ox[i] / f.sE2 + oy[i] / f.sF2) + sd[i];
+    if (out->odx2) out->odx2[at + i] = ox[i];
+    if (out->ody2) out->ody2[at + i] = oy[i];
+    if (out->sd2) out->sd2[at + i] = sd[i];
+    if (out->d2) out->d2[at + i] = d2;
+    if (out->loglik) out->loglik[at + i] = f.cst - 0.5 * d2;
+  }
+  if (dmu) {
+    if (out->mu_T)
+      HIPCHK(c, hipMemcpy2D(out->mu_T + at, sizeof(double) * n, dmu, sizeof(double) * count, sizeof(double) * count, r,
+                            hipMemcpyDeviceToHost));
+    if (out->mu_U)
+      HIPCHK(c, hipMemcpy2D(out->mu_U + at, sizeof(double) * n, dmu + (size_t)count * r, sizeof(double) * count,
+                            sizeof(double) * count, r, hipMemcpyDeviceToHost));
+  }
+  return PPLS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ppls_row_diagnostics(ppls_ctx* c, const ppls_theta* th, int r, const int64_t* rows, int64_t nrows,
+                         ppls_row_diag* out) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
+  if (!out) return fail(c, PPLS_E_ARG, "NULL output");
+  double h[PPLS_ROWDIAG_COEF * 16];
+  RowDiagFit f;
+  int rc;
+  if ((rc = rowdiag_check_fit(c, th, r, h, f))) return rc;
+  if (!rows) nrows = c->n_local;   // all local rows
+  if (nrows < 0) return fail(c, PPLS_E_ARG, "row list: %lld rows", (long long)nrows);
+  for (int64_t i = 0; rows && i < nrows; ++i)   // any order, repeats allowed: the kernel only reads
+    if (rows[i] < 0 || rows[i] >= c->n_local)
+      return fail(c, PPLS_E_ARG, "row index %lld (entry %lld) outside [0, %lld)", (long long)rows[i], (long long)i,
+                  (long long)c->n_local);
+  if (nrows == 0) return PPLS_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  CvScratch tmp;
+  if ((rc = rowdiag_upload_fit(c, tmp, th, r, h, f))) return rc;
+  int64_t* d_rows = nullptr;
+  if (rows && (rc = cv_upload_rows(c, tmp, rows, nrows, &d_rows))) return rc;
+  const bool mu = out->mu_T || out->mu_U;
+  double *res = nullptr, *dmu = nullptr;
+  if ((rc = tmp.get(c, &res, (size_t)3 * nrows))) return rc;
+  if (mu && (rc = tmp.get(c, &dmu, (size_t)2 * nrows * r))) return rc;
+  HIPCHK(c, ppls_launch_rowdiag(c->X, c->ldx, c->p, c->Y, c->ldy, c->q, c->dtype, d_rows, nrows, f.W, f.C, f.coef, r, res,
+                                res + nrows, res + 2 * nrows, dmu, dmu ? dmu + (size_t)nrows * r : nullptr, nrows,
+                                ppls_rowdiag_grid(nrows, c->p, c->q, c->dtype, r, c->num_cus), c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return rowdiag_collect(c, f, res, dmu, nrows, r, 0, nrows, out);
+}
+
+int ppls_row_diagnostics_new(ppls_ctx* c, const ppls_theta* th, int r, const double* X, const double* Y, int64_t n,
+                             int layout, ppls_row_diag* out) {
+  if (!c) return PPLS_E_ARG;
+  if (c->p < 1 || c->q < 1) return fail(c, PPLS_E_STATE, "no data shape: load data (p, q) first");
+  if (!out) return fail(c, PPLS_E_ARG, "NULL output");
+  double h[PPLS_ROWDIAG_COEF * 16];
+  RowDiagFit f;
+  int rc;
+  if ((rc = rowdiag_check_fit(c, th, r, h, f))) return rc;
+  if (layout != PPLS_LAYOUT_COLMAJOR && layout != PPLS_LAYOUT_ROWMAJOR)
+    return fail(c, PPLS_E_ARG, "layout must be 0 (column-major) or 1 (row-major)");
+  if (n < 0 || (n > 0 && (!X || !Y))) return fail(c, PPLS_E_ARG, "NULL X or Y with %lld rows", (long long)n);
+  if (n == 0) return PPLS_OK;
+  const int p = c->p, q = c->q;
+  for (int blk = 0; blk < 2; ++blk) {   // the whole call is refused, as ppls_set_data refuses such data
+    const double* D = blk ? Y : X;
+    const size_t len = (size_t)n * (blk ? q : p);
+    for (size_t e = 0; e < len; ++e)
+      if (!std::isfinite(D[e])) return fail(c, PPLS_E_ARG, "%c contains NaN or Inf", blk ? 'Y' : 'X');
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  CvScratch tmp;
+  if ((rc = rowdiag_upload_fit(c, tmp, th, r, h, f))) return rc;
+  // row blocks through a staging buffer (~64 MB of rows at a time), always staged in fp64
+  const int ldx = (p + 1) & ~1, ldy = (q + 1) & ~1;
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(64 << 20) / (8LL * (ldx + ldy))));
+  const bool mu = out->mu_T || out->mu_U;
+  double *inX = nullptr, *inY = nullptr, *cm = nullptr, *res = nullptr, *dmu = nullptr;
+  if ((rc = tmp.get(c, &inX, (size_t)chunk * ldx))) return rc;
+  if ((rc = tmp.get(c, &inY, (size_t)chunk * ldy))) return rc;
+  if (layout == PPLS_LAYOUT_COLMAJOR && (rc = tmp.get(c, &cm, (size_t)chunk * std::max(p, q)))) return rc;
+  if ((rc = tmp.get(c, &res, (size_t)3 * chunk))) return rc;
+  if (mu && (rc = tmp.get(c, &dmu, (size_t)2 * chunk * r))) return rc;
+  HIPCHK(c, hipMemsetAsync(inX, 0, sizeof(double) * chunk * ldx, c->stream));
+  HIPCHK(c, hipMemsetAsync(inY, 0, sizeof(double) * chunk * ldy, c->stream));
+  for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+    const int64_t nc = std::min(chunk, n - r0);
+    for (int blk = 0; blk < 2; ++blk) {
+      const double* D = blk ? Y : X;
+      double* in = blk ? inY : inX;
+      const int cols = blk ? q : p, ld = blk ? ldy : ldx;
+      if (layout == PPLS_LAYOUT_ROWMAJOR) {
+        HIPCHK(c, hipMemcpy2DAsync(in, sizeof(double) * ld, D + r0 * cols, sizeof(double) * cols, sizeof(double) * cols, nc,
+                                   hipMemcpyHostToDevice, c->stream));
+      } else {
+        HIPCHK(c, hipMemcpy2DAsync(cm, sizeof(double) * nc, D + r0, sizeof(double) * n, sizeof(double) * nc, cols,
+                                   hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, ppls_launch_to_rowmajor(cm, nc, cols, ld, in, c->stream));
+      }
+    }
+    HIPCHK(c, ppls_launch_rowdiag(inX, ldx, p, inY, ldy, q, 0, nullptr, nc, f.W, f.C, f.coef, r, res, res + nc,
+                                  res + 2 * nc, dmu, dmu ? dmu + (size_t)nc * r : nullptr, nc,
+                                  ppls_rowdiag_grid(nc, p, q, 0, r, c->num_cus), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = rowdiag_collect(c, f, res, dmu, nc, r, r0, n, out))) return rc;
+  }
+  return PPLS_OK;
+}
+
+int ppls_rowdiag_timing(ppls_ctx* c, int r, int reps, double* ms) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
+  if (!ms || reps < 1) return fail(c, PPLS_E_ARG, "ms must be given with reps >= 1");
+  if (r < 1 || r > PPLS_RMAX || r > std::min(c->p, c->q))
+    return fail(c, PPLS_E_ARG, "r=%d outside [1, min(%d, p, q)]", r, PPLS_RMAX);
+  HIPCHK(c, hipSetDevice(c->device));
+  // unit loadings and unit scalars: the time does not depend on the values
+  std::vector<double> W((size_t)c->p * r, 0.0), C((size_t)c->q * r, 0.0), B(r, 1.0), sT(r, 1.0);
+  for (int k = 0; k < r; ++k) W[(size_t)k * c->p + k] = C[(size_t)k * c->q + k] = 1.0;
+  const ppls_theta th = {W.data(), C.data(), B.data(), sT.data(), 1.0, 1.0, 1.0};
+  double h[PPLS_ROWDIAG_COEF * 16];
+  RowDiagFit f;
+  int rc;
+  if ((rc = rowdiag_check_fit(c, &th, r, h, f))) return rc;
+  CvScratch tmp;
+  if ((rc = rowdiag_upload_fit(c, tmp, &th, r, h, f))) return rc;
+  const int64_t n = c->n_local;
+  double *res = nullptr, *dmu = nullptr;
+  if ((rc = tmp.get(c, &res, (size_t)3 * std::max<int64_t>(n, 1)))) return rc;
+  if ((rc = tmp.get(c, &dmu, (size_t)2 * std::max<int64_t>(n, 1) * r))) return rc;
+  const int grid = ppls_rowdiag_grid(n, c->p, c->q, c->dtype, r, c->num_cus);
+  for (int v = 0; v < 2; ++v) {
+    double* m = v ? dmu : nullptr;
+    CvEvents ev;
+    for (int it = 0; it <= reps; ++it) {   // one untimed launch first
+      if (it == 1) HIPCHK(c, ev.begin(c->stream));
+      HIPCHK(c, ppls_launch_rowdiag(c->X, c->ldx, c->p, c->Y, c->ldy, c->q, c->dtype, nullptr, n, f.W, f.C, f.coef, r, res,
+                                    res + n, res + 2 * n, m, m ? m + (size_t)n * r : nullptr, n, grid, c->stream));
+    }
+    HIPCHK(c, ev.end(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ms[v] = ev.ms() / reps;
+  }
   return PPLS_OK;
 }
 
