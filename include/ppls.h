@@ -654,6 +654,44 @@ int ppls_row_diagnostics(ppls_ctx* ctx, const ppls_theta* th, int r, const int64
 int ppls_row_diagnostics_new(ppls_ctx* ctx, const ppls_theta* th, int r, const double* X, const double* Y, int64_t n,
                              int layout, ppls_row_diag* out);
 
+/* ---- robust fit: the multivariate-t PPLS model by EM ------------------------------
+ * With Sigma(theta) the PPLS covariance, P = p + q and d2_i the distance above, the t model's E-step
+ * weight of a row is u_i = (nu + P) / (nu + d2_i) and its M-step is the Gaussian one on
+ * S_u = sum_i u_i d_i d_i' with divisor N.  Its log-likelihood is
+ *   l_t(theta, nu) = N [lgamma((nu + P)/2) - lgamma(nu/2) - (P/2) log(nu pi)] - (N/2) logdet
+ *                    - ((nu + P)/2) sum_i log1p(d2_i / nu),
+ *   logdet = (p-r) log sigE^2 + (q-r) log sigF^2 + sum_k log det_k.
+ * No intercept: the data are centred beforehand and the rows are reweighted as they stand.
+ *
+ * ppls_robust_weights: on the resident rows of either storage type, the distance pass of
+ * ppls_row_diagnostics and one small kernel over its 24 B per row.  nu: m values (1 <= m <= 16); the
+ * weights for nu[keep] and the distances are kept in device arrays the context owns (n_local doubles
+ * each, reused across calls; a row's d2 has the bits ppls_row_diagnostics reports).  loglik_t[j] =
+ * l_t(theta, nu[j]) over all ranks' rows (N = n_total), sum_w (nullable) = sum_i u_i; the m + 1 sums are
+ * formed in an order fixed by n_local alone (no atomics: the same bits for every launch and grid) and
+ * all-reduced through the context's communicator or reducer in the same order on every rank.
+ * PPLS_E_ARG, with the outputs and the kept weights untouched: whatever ppls_row_diagnostics refuses
+ * about the fit, m outside 1..16, a nu that is not finite or not above 0, keep outside 0..m-1.
+ * PPLS_E_STATE: a context without rows (streamed).  What replaces or rescales the rows
+ * (ppls_set_data, the generator, ppls_scale_data, a stream, being the dst of ppls_set_data_from, a
+ * change of dtype) drops the kept weights. */
+int ppls_robust_weights(ppls_ctx* ctx, const ppls_theta* th, int r, const double* nu, int m, int keep,
+                        double* loglik_t /* m */, double* sum_w /* nullable */);
+/* Host copies of the kept weights and their distances (n_local each, nullable).  PPLS_E_STATE when
+ * nothing is kept. */
+int ppls_robust_get(ppls_ctx* ctx, double* w, double* d2);
+/* ppls_xprod_resample for real case weights: dst's S becomes sum_i weight_i d_i d_i' over src's
+ * resident rows, by the real-weighted instantiation of the fp64 MFMA Gram (each term (weight_i x_a) x_b;
+ * the device holds the weights as fp64).  weight: this rank's n_local host doubles, or NULL for the
+ * weights src keeps from ppls_robust_weights, with no host round trip.  The lifecycle is
+ * ppls_xprod_resample's: the agreement across ranks, dst's reused S and partials, src left as it was,
+ * dst "streamed".  n_total is src's -- the weights are relative to N, not renormalised: the M-step of
+ * the t model divides S_u by N, not by sum u -- and ||X||^2, ||Y||^2 are the traces of S_u's diagonal
+ * blocks.  PPLS_E_ARG: a negative or non-finite weight on any rank (every rank returns it), all weights
+ * zero over all ranks, dst == src, contexts on different devices.  PPLS_E_STATE: src without data or
+ * streamed, NULL weight with nothing kept.  After such a refusal dst holds what it held before. */
+int ppls_xprod_weighted(ppls_ctx* dst, ppls_ctx* src, const double* weight /* host, src's n_local, or NULL */);
+
 /* ---- host-side algebra (no GPU; the same code the device finalize runs) ------------------------ */
 /* From the all-reduced sufficient statistics of one sweep with theta (stats = [X'mu_T p x r |
  * Y'mu_U q x r | Gram 2r x 2r], all column-major) compute Expect_M's moments, logl_W(theta) and

@@ -134,6 +134,11 @@ int ppls_gram(ppls_ctx* ctx, int xory, int nsplit, double* G, double* ms);
  * (count: n_local host counts >= 0, else PPLS_E_ARG), xory and nsplit as for ppls_gram -- the Gram of
  * the rows with row i repeated count_i times (ppls_xprod_resample). */
 int ppls_gram_weighted(ppls_ctx* ctx, int xory, int nsplit, const int32_t* count, double* G, double* ms);
+/* The real-weighted instantiation alone: G = sum_i weight_i d_i d_i' over this rank's rows, each term
+ * formed as (weight_i x_a) x_b (weight: n_local finite host doubles >= 0, held on the device as fp64,
+ * else PPLS_E_ARG), xory and nsplit as for ppls_gram (ppls_xprod_weighted).  Weights that
+ * are all 1 give ppls_gram's bits, integer weights ppls_gram_weighted's. */
+int ppls_gram_weighted_real(ppls_ctx* ctx, int xory, int nsplit, const double* weight, double* G, double* ms);
 /* The permuted cross block alone: C (p x q column-major, nullable) = sum_i x_i y_perm[i]' over this rank's
  * rows (perm: a permutation of 0 .. n_local - 1 on the host, else PPLS_E_ARG; nsplit 0 = auto, at most 64),
  * *ms = the MFMA kernel's duration (ppls_xprod_permute). */
@@ -145,9 +150,11 @@ int ppls_xperm_occupancy(int f32);
  * due), the whole call}. */
 int ppls_xperm_timing(ppls_ctx* ctx, double* ms4);
 /* Workgroups of the Gram kernel one compute unit holds at once: the unweighted instantiation for the
- * storage type (f32 0 / 1), which sizes the grid and the split plan, and the weighted one -- equal. */
+ * storage type (f32 0 / 1), which sizes the grid and the split plan, and the count-weighted and
+ * real-weighted ones -- all equal. */
 int ppls_gram_occupancy(int f32);
 int ppls_gram_occupancy_weighted(int f32);
+int ppls_gram_occupancy_real(int f32);
 /* Inverse of a batch of symmetric positive definite matrices (host A: a x p x p, column-major, stride
  * p^2) as variances.PPLS_simult inverts the observed information: method 1 the hand-written blocked
  * Cholesky + inverse (ppls_linalg.hip), 2 rocSOLVER potrf + potri.  out: the full symmetric inverses;
@@ -231,6 +238,11 @@ int ppls_o2m_pass_timing(ppls_ctx* ctx, int reps, double* ms, double* bytes, int
  * without, ms[1] with the posterior means written.  Unit loadings and scalars (the time does not
  * depend on the values); the results go to scratch of the call. */
 int ppls_rowdiag_timing(ppls_ctx* ctx, int r, int reps, double* ms /* [2] */);
+/* Benchmark (tools/bench_robust.py): the weights and t log-likelihood kernels of ppls_robust_weights alone
+ * over all local rows (24 B read, 16 B written per row), reps launches between HIP events after one
+ * untimed launch; ms[0] = the average for one nu, ms[1] for 16.  The results go to scratch of the call:
+ * kept weights are not touched. */
+int ppls_robust_timing(ppls_ctx* ctx, int reps, double* ms /* [2] */);
 
 #ifdef __cplusplus
 }

@@ -113,6 +113,8 @@ SIGNATURES = {
     "ppls_gram_weighted": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(ct.c_int32), _dp, _dp]),
     "ppls_gram_occupancy": (ct.c_int, [ct.c_int]),
     "ppls_gram_occupancy_weighted": (ct.c_int, [ct.c_int]),
+    "ppls_gram_weighted_real": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, _dp, _dp, _dp]),
+    "ppls_gram_occupancy_real": (ct.c_int, [ct.c_int]),
     "ppls_spd_inverse": (ct.c_int, [ct.c_void_p, _dp, ct.c_int, ct.c_int, ct.c_int, _dp, ct.POINTER(ct.c_int), _dp]),
     "ppls_xprod_prepare": (ct.c_int, [ct.c_void_p, _dp, _dp]),
     "ppls_xprod_release": (ct.c_int, [ct.c_void_p]),
@@ -152,6 +154,9 @@ SIGNATURES = {
     "ppls_xprod_downdate": (ct.c_int, [ct.c_void_p, ct.c_void_p, _i64p, ct.c_int64]),
     "ppls_xprod_resample": (ct.c_int, [ct.c_void_p, ct.c_void_p, ct.POINTER(ct.c_int32)]),
     "ppls_xprod_permute": (ct.c_int, [ct.c_void_p, ct.c_void_p, _i64p]),
+    "ppls_xprod_weighted": (ct.c_int, [ct.c_void_p, ct.c_void_p, _dp]),
+    "ppls_robust_weights": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsTheta), ct.c_int, _dp, ct.c_int, ct.c_int, _dp, _dp]),
+    "ppls_robust_get": (ct.c_int, [ct.c_void_p, _dp, _dp]),
     "ppls_xgram_permuted": (ct.c_int, [ct.c_void_p, ct.c_int, _i64p, _dp, _dp]),
     "ppls_xperm_occupancy": (ct.c_int, [ct.c_int]),
     "ppls_xperm_timing": (ct.c_int, [ct.c_void_p, _dp]),
@@ -162,6 +167,7 @@ SIGNATURES = {
     "ppls_row_diagnostics_new": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsTheta), ct.c_int, _dp, _dp, ct.c_int64, ct.c_int,
                                             ct.POINTER(PplsRowDiag)]),
     "ppls_rowdiag_timing": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, _dp]),
+    "ppls_robust_timing": (ct.c_int, [ct.c_void_p, ct.c_int, _dp]),
     "ppls_cv_ppls": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.POINTER(ct.c_int32), _i64p, ct.c_int,
                                 ct.c_double, ct.c_int, ct.POINTER(PplsTheta), _dp, ct.POINTER(ct.c_int)]),
     "ppls_cv_timing": (ct.c_int, [ct.c_void_p, _dp, ct.c_int]),

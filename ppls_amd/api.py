@@ -660,14 +660,21 @@ class Context:
         self._chk(self._L.ppls_varinfo_timing(self.h, int(xory), int(a), int(reps), ct.byref(new), ct.byref(old)))
         return new.value, old.value
 
-    def gram(self, xory=0, nsplit=0, want=True, count=None):
+    def gram(self, xory=0, nsplit=0, want=True, count=None, weight=None):
         """D'D (D = X, Y, or xory = 2 the joint [X Y], (p + q) x (p + q)) on the fp64 MFMA Gram kernel
         alone, this rank's rows -> (G or None, kernel ms).  ``count`` (one integer >= 0 per local row):
-        the weighted instantiation instead, sum_i count_i d_i d_i' (ppls_gram_weighted)."""
+        the weighted instantiation instead, sum_i count_i d_i d_i' (ppls_gram_weighted).  ``weight`` (one
+        finite real >= 0 per local row): the real-weighted one, sum_i weight_i d_i d_i'
+        (ppls_gram_weighted_real).  Giving both is an error."""
+        if count is not None and weight is not None:
+            raise ValueError("gram: give count or weight, not both")
         p = self.p + self.q if xory == 2 else self.q if xory else self.p
         G = np.zeros((p, p), order="F") if want else None
         ms = ct.c_double()
-        if count is None:
+        if weight is not None:
+            w = self._weights(weight, self.n_local)
+            self._chk(self._L.ppls_gram_weighted_real(self.h, int(xory), int(nsplit), dptr(w), dptr(G), ct.byref(ms)))
+        elif count is None:
             self._chk(self._L.ppls_gram(self.h, int(xory), int(nsplit), dptr(G), ct.byref(ms)))
         else:
             cnt, cp = self._counts(count, self.n_local)
@@ -676,8 +683,10 @@ class Context:
 
     def gram_occupancy(self, f32=False, weighted=False):
         """Workgroups of the MFMA Gram kernel per compute unit, for fp64 or fp32 storage: the
-        unweighted instantiation (it sizes the grid and the split plan) or the weighted one."""
-        fn = self._L.ppls_gram_occupancy_weighted if weighted else self._L.ppls_gram_occupancy
+        unweighted instantiation (it sizes the grid and the split plan), the count-weighted one
+        (``weighted=True``) or the real-weighted one (``weighted="real"``)."""
+        fn = (self._L.ppls_gram_occupancy_real if weighted == "real" else
+              self._L.ppls_gram_occupancy_weighted if weighted else self._L.ppls_gram_occupancy)
         return int(fn(int(bool(f32))))
 
     def gram_int8(self, which=2, want=True):
@@ -987,6 +996,60 @@ class Context:
         self.p, self.q, self.n_local, self.row0 = src.p, src.q, 0, 0
         self.n_total = self.stream_info()["n_total"]
         self._stream_folds = None
+
+    @staticmethod
+    def _weights(weight, n):
+        w = np.ascontiguousarray(weight, dtype=np.float64)
+        if w.ndim != 1 or w.shape[0] != n:
+            raise ValueError(f"weights: one per local row ({n}), got shape {w.shape}")
+        return w if w.size else np.zeros(1)   # (a pointer the library never reads)
+
+    def xprod_weighted(self, src: "Context", weight=None):
+        """This context's cross-products := sum_i weight_i d_i d_i' over ``src``'s resident rows
+        (ppls_xprod_weighted), by the real-weighted MFMA Gram with no copy of the rows.  ``weight``: one
+        finite real >= 0 per local row of ``src``, or None for the weights ``src`` keeps from
+        ``robust_weights`` (they never leave the device).  This context ends streamed (S, no rows) with
+        ``src``'s shape, scaling record and ``n_total``: the weights are relative to N and are not
+        renormalised.  ``src`` is left as it was.  Collective over ``src``'s ranks."""
+        w = None if weight is None else self._weights(weight, src.n_local)
+        self._chk(self._L.ppls_xprod_weighted(self.h, src.h, dptr(w)))
+        self.p, self.q, self.n_local, self.row0 = src.p, src.q, 0, 0
+        self.n_total = self.stream_info()["n_total"]
+        self._stream_folds = None
+
+    def robust_weights(self, th: Theta, nu=4.0, keep=0):
+        """E-step of the multivariate-t model on the resident rows (ppls_robust_weights): the distance
+        pass of ``row_diagnostics`` and one small kernel.  ``nu``: a value or up to 16 of them.  Returns
+        ``(loglik_t, sum_w)``: the t log-likelihood of ``th`` at every ``nu`` over all ranks' rows and
+        the sum of the weights ``(nu[keep] + p + q) / (nu[keep] + d2_i)``, which stay on the device with
+        their distances (``robust_get``, ``xprod_weighted(src, None)``).  Collective when sharded."""
+        nus = np.ascontiguousarray(np.atleast_1d(np.asarray(nu, dtype=np.float64)))
+        g = self._ROWDIAG_GUARD
+        ll = np.full(nus.shape[0] + g, np.nan)
+        sw = np.full(1 + g, np.nan)
+        self._robust_last = (ll, sw)
+        t = th.struct()
+        self._chk(self._L.ppls_robust_weights(self.h, ct.byref(t), th.r, dptr(nus), nus.shape[0], int(keep), dptr(ll),
+                                              dptr(sw)))
+        if not (np.all(np.isnan(ll[nus.shape[0]:])) and np.all(np.isnan(sw[1:]))):
+            raise PplsError(-1, "robust_weights wrote past the end of its outputs")
+        return ll[: nus.shape[0]].copy(), float(sw[0])
+
+    def robust_timing(self, reps=20):
+        """The weights and t log-likelihood kernels alone over all local rows, ms between HIP events
+        averaged over ``reps`` launches (ppls_robust_timing): dict(ms1, ms16) for one and for 16 nu."""
+        ms = np.zeros(2)
+        self._chk(self._L.ppls_robust_timing(self.h, int(reps), dptr(ms)))
+        return dict(ms1=float(ms[0]), ms16=float(ms[1]))
+
+    def robust_get(self, want_w=True, want_d2=True):
+        """Host copies ``(weights, d2)`` of what the last ``robust_weights`` kept (ppls_robust_get); None
+        for a part not wanted."""
+        n = int(self.n_local)
+        w = np.full(n, np.nan) if want_w else None
+        d2 = np.full(n, np.nan) if want_d2 else None
+        self._chk(self._L.ppls_robust_get(self.h, dptr(w) if n else None, dptr(d2) if n else None))
+        return w, d2
 
     @staticmethod
     def _perm(perm, n):
@@ -1962,6 +2025,93 @@ def PPLS_simult(X, Y, a, EMsteps=10, atol=1e-4, type=("SVD", "QR"), init=None, c
     out["class"] = "PPLS_simult"
     if timings is not None:
         timings.update(init=t1 - t0, loop=time.perf_counter() - t1, init_steps=init_steps)
+    return out
+
+
+# ---------------------------------------------------------------------------- robust fit
+def t_nu_grid(lo, hi, m=16):
+    """``m`` log-spaced points from ``lo`` to ``hi``, both included."""
+    return np.exp(np.linspace(np.log(lo), np.log(hi), int(m)))
+
+
+def t_nu_bracket(grid, k, lo=1.0, hi=1000.0):
+    """The interval the next round of the nu search covers: the neighbours of the best point ``k``."""
+    return max(lo, float(grid[max(k - 1, 0)])), min(hi, float(grid[min(k + 1, len(grid) - 1)]))
+
+
+def robust_PPLS_simult(X, Y, a, nu=4.0, outer=50, inner=5, atol=1e-4, type="SVD", init=None, ctx=None, work=None):
+    """PPLS_simult under the multivariate-t model with ``nu`` degrees of freedom, fitted by EM: rows the
+    Gaussian fit does not explain are weighted down instead of deciding the answer.
+
+    From theta (``init``: a dict as for PPLS_simult, default the estimates of ``PPLS_simult(X, Y, a)``
+    on the same context) the loop repeats: (1) ``ctx.robust_weights`` -- the distances d2_i, the weights
+    u_i = (nu + p + q) / (nu + d2_i) and the t log-likelihood at theta; (2) ``work.xprod_weighted(ctx)``
+    -- S_u = sum u_i d_i d_i' with ``n_total = N``, not sum u; (3) ``inner`` EM steps of PPLS_simult on
+    ``work``, warm-started at theta.  It stops when the t log-likelihood rises by less than ``atol``
+    (never tested on the first step) or after ``outer`` iterations.  ``nu="estimate"``: nu is re-chosen
+    in step (1) to maximise the t log-likelihood of theta over [1, 1000], by four rounds of a 16-point
+    log-spaced grid, each bracketing the previous best point (the ECME step).
+
+    ``X``, ``Y``: the data, centred beforehand (no intercept is fitted), or ``None, None`` with ``ctx``
+    holding the rows, ``scale_data`` output included.  ``work``: the context that holds S_u (default: a
+    new one on ``ctx``'s device, closed at the end).  Sharded, every rank calls this with its own rows
+    and a shared ``init``.
+
+    Returns ``dict(estimates, loglik, nu, weights, d2, steps, converged, gaussian)``: ``estimates``
+    canonicalised as PPLS_simult's; ``loglik`` the t log-likelihood at the start and after every outer
+    iteration (``steps + 1`` values); ``weights`` and ``d2`` this rank's rows' at the returned estimates;
+    ``gaussian`` the starting PPLS_simult fit (None when ``init`` was given)."""
+    estimate = isinstance(nu, str)
+    if estimate and nu != "estimate":
+        raise ValueError("nu must be a positive number or 'estimate'")
+    if not estimate and not (np.isfinite(nu) and nu > 0):
+        raise ValueError(f"nu = {nu} must be positive and finite")
+    if outer < 1 or inner < 1:
+        raise ValueError(f"outer = {outer}, inner = {inner} must be at least 1")
+    ctx = _ctx_with(X, Y, ctx)
+    t = _orth_type(type)
+    gauss = None
+    if init is None:
+        gauss = PPLS_simult(None, None, a, type=type, ctx=ctx)
+        init = gauss["estimates"]
+    th = Theta(init["W"], init["C"], init["B"], init["sigE"], init["sigF"], init["sigH"], init["sigT"])
+    if th.r != a:
+        raise ValueError(f"init has {th.r} components, a = {a}")
+
+    def estep(th):
+        if not estimate:
+            return float(nu), float(ctx.robust_weights(th, nu)[0][0])
+        lo, hi = 1.0, 1000.0
+        for _ in range(4):
+            grid = t_nu_grid(lo, hi)
+            k = int(np.argmax(ctx.robust_weights(th, grid)[0]))
+            lo, hi = t_nu_bracket(grid, k)
+        return float(grid[k]), float(ctx.robust_weights(th, grid[k])[0][0])   # keeps the weights of the chosen nu
+
+    own = work is None
+    work = Context(ctx.device) if own else work
+    ll, steps, converged = [], 0, False
+    try:
+        while True:
+            nu_k, l = estep(th)
+            ll.append(l)
+            if len(ll) > 1 and ll[-1] - ll[-2] < atol:
+                converged = True
+                break
+            if steps >= outer:
+                break
+            work.xprod_weighted(ctx)
+            th = work.em_run(th, int(inner), -np.inf, t, want_eout=False, want_mu=False)[0]
+            steps += 1
+    finally:
+        if own:
+            work.close()
+    w, d2 = ctx.robust_get()
+    d = th.as_dict()
+    estimates = dict(W=d["W"], C=d["C"], B=d["B"], sigE=d["sigE"], sigF=d["sigF"], sigH=d["sigH"], sigT=d["sigT"])
+    out = dict(estimates=estimates, loglik=np.array(ll), nu=nu_k, weights=w, d2=d2, steps=steps, converged=converged,
+               gaussian=gauss)
+    out["class"] = "robust_PPLS_simult"
     return out
 
 

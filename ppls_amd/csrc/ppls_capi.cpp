@@ -27,6 +27,7 @@
 #include "ppls_kernels.h"
 #include "ppls_math.h"
 #include "ppls_cv.h"
+#include "ppls_robust.h"
 #include "ppls_rowdiag.h"
 #include "ppls_o2m.h"
 #include "ppls_permute.h"
@@ -240,6 +241,16 @@ struct ppls_ctx {
   int64_t rs_cnt_len = 0;
   double* rs_part = nullptr;
   int64_t rs_part_len = 0;
+  // ppls_xprod_weighted with this context as dst and host weights: their device copy, kept likewise
+  double* rs_wt = nullptr;
+  int64_t rs_wt_len = 0;
+  // ppls_robust_weights on this context: the weights of the resident rows for the nu last
+  // kept and their distances, n_local each, reused across calls; rb_kept while they belong to the rows
+  // as they stand.  Option "robust_grid": the row pass's workgroups (0 auto; any value, the same bits).
+  double *rb_w = nullptr, *rb_d2 = nullptr;
+  int64_t rb_len = 0;
+  bool rb_kept = false;
+  int rb_grid = 0;
   // ppls_xprod_permute with this context as dst: the device array [row indices | padding |
   // split bounds] with its host staging, the ldx x ldy block the ranks all-reduce, and the host byte map
   // of the permutation check, kept from call to call (the split partials are rs_part).  xp_serial numbers
@@ -875,9 +886,10 @@ int gram_queue(ppls_ctx* c, const GramShape& g, int64_t n, int req, int** q, int
 // partials, then the finish (sum over splits, mirrored).  ms: the MFMA kernel's duration (HIP
 // events), if not null.  The partials are allocated here and freed, unless the caller passes them
 // (part_in, ppls_gram_part_doubles(g.p, nsplit) doubles; the caller frees them).  cnt: NULL, or n device
-// counts, one per row: the weighted Gram sum_i cnt[i] d_i d_i' (DESIGN §19).
+// counts, one per row: the weighted Gram sum_i cnt[i] d_i d_i' (DESIGN §19).  wt: NULL, or n device
+// weights likewise; not both.
 int gram_run(ppls_ctx* c, const GramShape& g, int64_t n, int req, double* G, float* ms, double* part_in = nullptr,
-             const int32_t* cnt = nullptr) {
+             const int32_t* cnt = nullptr, const double* wt = nullptr) {
   int rc;
   const int nsplit = gram_nsplit(c, g, n, req);
   double* part = part_in;
@@ -893,7 +905,7 @@ int gram_run(ppls_ctx* c, const GramShape& g, int64_t n, int req, double* G, flo
   }
   if (e == hipSuccess)
     e = ppls_launch_gram_joint(g.X, g.ldx, g.xcols, g.xreal, g.Y, g.ldy, g.ycols, g.yreal, c->dtype, n, g.p, nsplit, part,
-                               q, cnt, c->stream);
+                               q, cnt, wt, c->stream);
   if (e == hipSuccess && ms) e = hipEventRecord(e1, c->stream);
   if (e == hipSuccess) e = ppls_launch_gram_finish(part, nsplit, g.p, g.xreal, g.xcols, g.yreal, G, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1364,6 +1376,7 @@ int alloc_data(ppls_ctx* c, int64_t n_local, int p, int q, int64_t n_total) {
   c->have_data = false;
   c->sc_center.clear();   // new data carry no transform (ppls_get_scaling: center 0, scale 1)
   c->sc_scale.clear();
+  c->rb_kept = false;     // kept robust weights belonged to the rows that were here
   return PPLS_OK;
 }
 
@@ -1516,6 +1529,9 @@ void ppls_ctx_destroy(ppls_ctx* c) {
   dfree(c->gram_q);
   dfree(c->rs_cnt);
   dfree(c->rs_part);
+  dfree(c->rs_wt);
+  dfree(c->rb_w);
+  dfree(c->rb_d2);
   dfree(c->pm_idx);
   dfree(c->pm_blk);
   dfree(c->o2m_buf);
@@ -1539,6 +1555,9 @@ int ppls_set_option(ppls_ctx* c, const char* key, int64_t value) {
     c->grid_opt = (int)value;
     c->part_groups = 0;
     dfree(c->part);
+  } else if (!strcmp(key, "robust_grid")) {
+    if (value < 0 || value > 65535) return fail(c, PPLS_E_ARG, "robust_grid out of range");
+    c->rb_grid = (int)value;
   } else if (!strcmp(key, "rows_per_step")) {
     if (value < 0 || value > 2) return fail(c, PPLS_E_ARG, "rows_per_step must be 0 (auto), 1 or 2");
     c->rp_opt = (int)value;
@@ -1593,6 +1612,7 @@ int ppls_set_option(ppls_ctx* c, const char* key, int64_t value) {
       if (c->st_state == 1) return fail(c, PPLS_E_STATE, "a stream is open: dtype cannot change before ppls_stream_end");
       c->dtype = (int)value;
       c->have_data = false;   // the data must be (re)loaded in the new storage type
+      c->rb_kept = false;
     }
   } else if (!strcmp(key, "nt")) {
     if (value < -1 || value > 1) return fail(c, PPLS_E_ARG, "nt must be -1 (auto), 0 or 1");
@@ -4207,8 +4227,9 @@ int ppls_spd_inverse(ppls_ctx* c, const double* A, int p, int a, int method, dou
 
 namespace {
 
-// ppls_gram (count NULL, weighted false) and ppls_gram_weighted.
-int gram_debug(ppls_ctx* c, int xory, int nsplit, bool weighted, const int32_t* count, double* G, double* ms) {
+// ppls_gram (count NULL, weighted false), ppls_gram_weighted and ppls_gram_weighted_real (weight given).
+int gram_debug(ppls_ctx* c, int xory, int nsplit, bool weighted, const int32_t* count, double* G, double* ms,
+               const double* weight = nullptr, bool real = false) {
   if (!c) return PPLS_E_ARG;
   if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
   NEED_ROWS(c);
@@ -4220,9 +4241,17 @@ int gram_debug(ppls_ctx* c, int xory, int nsplit, bool weighted, const int32_t* 
   int rc;
   struct Counts {
     int32_t* d = nullptr;
-    ~Counts() { dfree(d); }
+    double* w = nullptr;
+    ~Counts() { dfree(d); dfree(w); }
   } cnt;
-  if (weighted) {
+  if (real) {
+    if (!weight) return fail(c, PPLS_E_ARG, "NULL weights for %lld rows", (long long)c->n_local);
+    for (int64_t i = 0; i < c->n_local; ++i)
+      if (!(weight[i] >= 0.0) || !std::isfinite(weight[i]))
+        return fail(c, PPLS_E_ARG, "weight %g of row %lld is negative or not finite", weight[i], (long long)i);
+    if ((rc = dalloc(c, &cnt.w, (size_t)c->n_local))) return rc;
+    HIPCHK(c, hipMemcpy(cnt.w, weight, sizeof(double) * c->n_local, hipMemcpyHostToDevice));
+  } else if (weighted) {
     if (!count) return fail(c, PPLS_E_ARG, "NULL counts for %lld rows", (long long)c->n_local);
     for (int64_t i = 0; i < c->n_local; ++i)
       if (count[i] < 0) return fail(c, PPLS_E_ARG, "count %d of row %lld is negative", (int)count[i], (long long)i);
@@ -4232,7 +4261,7 @@ int gram_debug(ppls_ctx* c, int xory, int nsplit, bool weighted, const int32_t* 
   double* dG = nullptr;
   if ((rc = dalloc(c, &dG, pp))) return rc;
   float t = 0.f;
-  rc = gram_run(c, g, c->n_local, nsplit > 0 ? nsplit : 0, dG, &t, nullptr, cnt.d);
+  rc = gram_run(c, g, c->n_local, nsplit > 0 ? nsplit : 0, dG, &t, nullptr, cnt.d, cnt.w);
   if (!rc && G) {
     if (xory < 2) {
       if (hipMemcpy(G, dG, sizeof(double) * pp, hipMemcpyDeviceToHost) != hipSuccess)
@@ -4264,6 +4293,10 @@ int ppls_gram(ppls_ctx* c, int xory, int nsplit, double* G, double* ms) {
 
 int ppls_gram_weighted(ppls_ctx* c, int xory, int nsplit, const int32_t* count, double* G, double* ms) {
   return gram_debug(c, xory, nsplit, true, count, G, ms);
+}
+
+int ppls_gram_weighted_real(ppls_ctx* c, int xory, int nsplit, const double* weight, double* G, double* ms) {
+  return gram_debug(c, xory, nsplit, false, nullptr, G, ms, weight, true);
 }
 
 // scores.PPLS (EM_W_multi.R:411-420): T = X W, U = Y C (local rows, column-major n_local x k) in
@@ -5162,6 +5195,7 @@ namespace {
 struct RowDiagFit {
   double *W = nullptr, *C = nullptr, *coef = nullptr;   // device: padded loadings, PPLS_ROWDIAG_COEF x 16
   double sE2 = 1.0, sF2 = 1.0, cst = 0.0;               // loglik_i = cst - d2_i / 2
+  double logdet = 0.0;   // (p - r) log sigE^2 + (q - r) log sigF^2 + sum_k log det_k
 };
 
 // Everything ppls_row_diagnostics{,_new} refuse about the fit, before any device work.
@@ -5190,6 +5224,7 @@ int rowdiag_check_fit(ppls_ctx* c, const ppls_theta* th, int r, double (&h)[PPLS
     return fail(c, PPLS_E_ARG, "sigE^2 = %g, sigF^2 = %g must be positive and finite", f.sE2, f.sF2);
   f.cst = -0.5 * ((double)(c->p + c->q) * std::log(6.283185307179586) + (double)(c->p - r) * std::log(f.sE2) +
                   (double)(c->q - r) * std::log(f.sF2) + logdet);
+  f.logdet = ((double)(c->p - r) * std::log(f.sE2) + (double)(c->q - r) * std::log(f.sF2)) + logdet;
   return PPLS_OK;
 }
 
@@ -5228,6 +5263,24 @@ int rowdiag_collect(ppls_ctx* c, const RowDiagFit& f, const double* dres, const 
   return PPLS_OK;
 }
 
+// The device stage of ppls_row_diagnostics on the resident rows, queued on the context stream with no
+// copy-out: the fit uploaded, then the kernel.  res = [odx2 | ody2 | sd2] (nrows each) and, with mu, dmu
+// = [mu_T | mu_U]; both live in tmp.  d_rows: device indices or nullptr (rows 0 .. nrows - 1).
+int rowdiag_device(ppls_ctx* c, CvScratch& tmp, const ppls_theta* th, int r, const double (&h)[PPLS_ROWDIAG_COEF * 16],
+                   RowDiagFit& f, const int64_t* d_rows, int64_t nrows, bool mu, double** res_out, double** dmu_out) {
+  int rc;
+  if ((rc = rowdiag_upload_fit(c, tmp, th, r, h, f))) return rc;
+  double *res = nullptr, *dmu = nullptr;
+  if ((rc = tmp.get(c, &res, (size_t)3 * nrows))) return rc;
+  if (mu && (rc = tmp.get(c, &dmu, (size_t)2 * nrows * r))) return rc;
+  HIPCHK(c, ppls_launch_rowdiag(c->X, c->ldx, c->p, c->Y, c->ldy, c->q, c->dtype, d_rows, nrows, f.W, f.C, f.coef, r, res,
+                                res + nrows, res + 2 * nrows, dmu, dmu ? dmu + (size_t)nrows * r : nullptr, nrows,
+                                ppls_rowdiag_grid(nrows, c->p, c->q, c->dtype, r, c->num_cus), c->stream));
+  *res_out = res;
+  *dmu_out = dmu;
+  return PPLS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -5251,18 +5304,76 @@ int ppls_row_diagnostics(ppls_ctx* c, const ppls_theta* th, int r, const int64_t
   if (nrows == 0) return PPLS_OK;
   HIPCHK(c, hipSetDevice(c->device));
   CvScratch tmp;
-  if ((rc = rowdiag_upload_fit(c, tmp, th, r, h, f))) return rc;
   int64_t* d_rows = nullptr;
   if (rows && (rc = cv_upload_rows(c, tmp, rows, nrows, &d_rows))) return rc;
-  const bool mu = out->mu_T || out->mu_U;
   double *res = nullptr, *dmu = nullptr;
-  if ((rc = tmp.get(c, &res, (size_t)3 * nrows))) return rc;
-  if (mu && (rc = tmp.get(c, &dmu, (size_t)2 * nrows * r))) return rc;
-  HIPCHK(c, ppls_launch_rowdiag(c->X, c->ldx, c->p, c->Y, c->ldy, c->q, c->dtype, d_rows, nrows, f.W, f.C, f.coef, r, res,
-                                res + nrows, res + 2 * nrows, dmu, dmu ? dmu + (size_t)nrows * r : nullptr, nrows,
-                                ppls_rowdiag_grid(nrows, c->p, c->q, c->dtype, r, c->num_cus), c->stream));
+  if ((rc = rowdiag_device(c, tmp, th, r, h, f, d_rows, nrows, out->mu_T || out->mu_U, &res, &dmu))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return rowdiag_collect(c, f, res, dmu, nrows, r, 0, nrows, out);
+}
+
+// ---------------------------------------------------------------------------- robust weights
+int ppls_robust_weights(ppls_ctx* c, const ppls_theta* th, int r, const double* nu, int m, int keep, double* loglik_t,
+                        double* sum_w) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
+  if (!nu || !loglik_t) return fail(c, PPLS_E_ARG, "NULL argument");
+  double h[PPLS_ROWDIAG_COEF * 16];
+  RowDiagFit f;
+  int rc;
+  if ((rc = rowdiag_check_fit(c, th, r, h, f))) return rc;
+  if (m < 1 || m > PPLS_ROBUST_MAXNU) return fail(c, PPLS_E_ARG, "m=%d values of nu outside [1, %d]", m, PPLS_ROBUST_MAXNU);
+  if (keep < 0 || keep >= m) return fail(c, PPLS_E_ARG, "keep=%d outside [0, %d)", keep, m);
+  PplsRobustNu nus;
+  memset(&nus, 0, sizeof nus);
+  for (int j = 0; j < m; ++j) {
+    if (!(nu[j] > 0.0) || !std::isfinite(nu[j])) return fail(c, PPLS_E_ARG, "nu[%d] = %g must be positive and finite", j, nu[j]);
+    nus.nu[j] = nu[j];
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const int64_t n = c->n_local;
+  // every allocation before the kept weights are touched
+  CvScratch tmp;
+  double *part = nullptr, *sums = nullptr, *res = nullptr, *dmu = nullptr;
+  if ((rc = tmp.get(c, &part, (size_t)ppls_robust_blocks(n) * PPLS_ROBUST_SUMS))) return rc;
+  if ((rc = tmp.get(c, &sums, (size_t)PPLS_ROBUST_SUMS))) return rc;
+  if (c->rb_len < n || !c->rb_w || !c->rb_d2) {
+    c->rb_kept = false;
+    c->rb_len = 0;
+    if ((rc = dalloc(c, &c->rb_w, (size_t)std::max<int64_t>(n, 1)))) return rc;
+    if ((rc = dalloc(c, &c->rb_d2, (size_t)std::max<int64_t>(n, 1)))) return rc;
+    c->rb_len = std::max<int64_t>(n, 1);
+  }
+  if (n > 0 && (rc = rowdiag_device(c, tmp, th, r, h, f, nullptr, n, false, &res, &dmu))) return rc;
+  c->rb_kept = false;   // from here the kept arrays are overwritten
+  const double P = (double)(c->p + c->q);
+  const int grid = c->rb_grid > 0 ? c->rb_grid : ppls_robust_grid(n, c->num_cus);
+  HIPCHK(c, ppls_launch_robust_weights(res, res ? res + n : nullptr, res ? res + 2 * n : nullptr, n, f.sE2, f.sF2, &nus, m, keep,
+                                       P, c->rb_w, c->rb_d2, part, sums, grid, c->stream));
+  if ((rc = allreduce(c, sums, (size_t)PPLS_ROBUST_SUMS))) return rc;
+  double hs[PPLS_ROBUST_SUMS];
+  HIPCHK(c, hipMemcpyAsync(hs, sums, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const double N = (double)c->n_total;
+  for (int j = 0; j < m; ++j) {
+    const double v = nu[j];
+    const double cst = std::lgamma(0.5 * (v + P)) - std::lgamma(0.5 * v) - 0.5 * P * std::log(v * 3.141592653589793);
+    loglik_t[j] = (N * cst - 0.5 * N * f.logdet) - 0.5 * (v + P) * hs[j];
+  }
+  if (sum_w) *sum_w = hs[PPLS_ROBUST_MAXNU];
+  c->rb_kept = true;
+  return PPLS_OK;
+}
+
+int ppls_robust_get(ppls_ctx* c, double* w, double* d2) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->rb_kept) return fail(c, PPLS_E_STATE, "no robust weights are kept: call ppls_robust_weights first");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->n_local > 0 && w) HIPCHK(c, hipMemcpy(w, c->rb_w, sizeof(double) * c->n_local, hipMemcpyDeviceToHost));
+  if (c->n_local > 0 && d2) HIPCHK(c, hipMemcpy(d2, c->rb_d2, sizeof(double) * c->n_local, hipMemcpyDeviceToHost));
+  return PPLS_OK;
 }
 
 int ppls_row_diagnostics_new(ppls_ctx* c, const ppls_theta* th, int r, const double* X, const double* Y, int64_t n,
@@ -5354,6 +5465,47 @@ int ppls_rowdiag_timing(ppls_ctx* c, int r, int reps, double* ms) {
       if (it == 1) HIPCHK(c, ev.begin(c->stream));
       HIPCHK(c, ppls_launch_rowdiag(c->X, c->ldx, c->p, c->Y, c->ldy, c->q, c->dtype, nullptr, n, f.W, f.C, f.coef, r, res,
                                     res + n, res + 2 * n, m, m ? m + (size_t)n * r : nullptr, n, grid, c->stream));
+    }
+    HIPCHK(c, ev.end(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ms[v] = ev.ms() / reps;
+  }
+  return PPLS_OK;
+}
+
+int ppls_robust_timing(ppls_ctx* c, int reps, double* ms) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
+  if (!ms || reps < 1) return fail(c, PPLS_E_ARG, "ms must be given with reps >= 1");
+  HIPCHK(c, hipSetDevice(c->device));
+  // distances of one component at unit loadings and scalars: real inputs, whatever the data
+  std::vector<double> W((size_t)c->p, 0.0), C((size_t)c->q, 0.0);
+  W[0] = C[0] = 1.0;
+  double one = 1.0;
+  const ppls_theta th = {W.data(), C.data(), &one, &one, 1.0, 1.0, 1.0};
+  double h[PPLS_ROWDIAG_COEF * 16];
+  RowDiagFit f;
+  int rc;
+  if ((rc = rowdiag_check_fit(c, &th, 1, h, f))) return rc;
+  CvScratch tmp;
+  const int64_t n = c->n_local;
+  double *res = nullptr, *dmu = nullptr, *w = nullptr, *d2 = nullptr, *part = nullptr, *sums = nullptr;
+  if (n < 1) return fail(c, PPLS_E_STATE, "no rows on this rank");
+  if ((rc = rowdiag_device(c, tmp, &th, 1, h, f, nullptr, n, false, &res, &dmu))) return rc;
+  if ((rc = tmp.get(c, &w, (size_t)n)) || (rc = tmp.get(c, &d2, (size_t)n))) return rc;
+  if ((rc = tmp.get(c, &part, (size_t)ppls_robust_blocks(n) * PPLS_ROBUST_SUMS))) return rc;
+  if ((rc = tmp.get(c, &sums, (size_t)PPLS_ROBUST_SUMS))) return rc;
+  PplsRobustNu nus;
+  for (int j = 0; j < PPLS_ROBUST_MAXNU; ++j) nus.nu[j] = 1.0 + j;
+  const int grid = c->rb_grid > 0 ? c->rb_grid : ppls_robust_grid(n, c->num_cus);
+  for (int v = 0; v < 2; ++v) {
+    const int m = v ? PPLS_ROBUST_MAXNU : 1;
+    CvEvents ev;
+    for (int it = 0; it <= reps; ++it) {   // one untimed launch first
+      if (it == 1) HIPCHK(c, ev.begin(c->stream));
+      HIPCHK(c, ppls_launch_robust_weights(res, res + n, res + 2 * n, n, f.sE2, f.sF2, &nus, m, 0, (double)(c->p + c->q), w, d2,
+                                           part, sums, grid, c->stream));
     }
     HIPCHK(c, ev.end(c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -5530,6 +5682,7 @@ int ppls_scale_data(ppls_ctx* c, int center, int scale) {
     return fail(c, PPLS_E_ARG, "scale = TRUE needs at least 2 rows (over all ranks: %lld): the standard deviation "
                                "divides by n - 1", (long long)c->n_total);
   HIPCHK(c, hipSetDevice(c->device));
+  c->rb_kept = false;   // the rows change under kept robust weights
   int rc;
   const int p = c->p, q = c->q, P = p + q;
   ScaleSide sd[2] = {{c->X, c->ldx, p, 0, ppls_scale_plan(c->n_local, p, c->dtype, c->num_cus)},
@@ -5721,7 +5874,7 @@ int stream_merge_rows(ppls_ctx* c, double* Xs, double* Ys, int64_t n, double* S,
   } else if ((rc = gram_queue(c, g, n, 0, &q, 0, s))) {
     return stream_fail(c, rc);
   }
-  STREAMCHK(c, ppls_launch_gram_joint(Xs, c->ldx, c->ldx, c->p, Ys, c->ldy, c->ldy, c->q, 0, n, P, nsplit, c->st_part, q, nullptr, s));
+  STREAMCHK(c, ppls_launch_gram_joint(Xs, c->ldx, c->ldx, c->p, Ys, c->ldy, c->ldy, c->q, 0, n, P, nsplit, c->st_part, q, nullptr, nullptr, s));
   STREAMCHK(c, ppls_launch_stream_merge(S, c->p, c->ldx, c->q, c->ldy, c->st_part, nsplit,
                                         c->st_center ? delta : nullptr, N * nc / (N + nc), s));
   return PPLS_OK;
@@ -6293,17 +6446,18 @@ int resample_adopt(ppls_ctx* dst, const ppls_ctx* src, double* S) {
   return PPLS_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ppls_xprod_resample(ppls_ctx* dst, ppls_ctx* src, const int32_t* count) {
+// ppls_xprod_resample (count; weight NULL, real false) and ppls_xprod_weighted (real: weight, or NULL for
+// src's kept device weights).  One lifecycle: the agreement across ranks, dst's reused S and partials.
+int reweight_impl(ppls_ctx* dst, ppls_ctx* src, const int32_t* count, const double* weight, bool real) {
   if (!dst || !src) return dst ? fail(dst, PPLS_E_ARG, "NULL source context") : PPLS_E_ARG;
   if (dst == src) return fail(dst, PPLS_E_ARG, "source and destination are the same context");
   if (!src->have_data) return fail(dst, PPLS_E_STATE, "the source context has no data");
   if (src->st_state == 2) return fail(dst, PPLS_E_STATE, PPLS_STREAMED_MSG);
   if (dst->device != src->device)
     return fail(dst, PPLS_E_ARG, "contexts on different devices (%d, %d)", dst->device, src->device);
+  const bool kept = real && !weight;   // src's device weights, no host round trip
+  if (kept && !src->rb_kept)
+    return fail(dst, PPLS_E_STATE, "NULL weights and the source keeps none: call ppls_robust_weights on it first");
   HIPCHK(dst, hipSetDevice(src->device));
   int rc;
   const bool coll = collective(src);
@@ -6313,7 +6467,17 @@ int ppls_xprod_resample(ppls_ctx* dst, ppls_ctx* src, const int32_t* count) {
   // this rank's verdict on its counts joins the agreement below (with sum count), so ranks return together
   int bad = PPLS_OK;
   double sum = 0.0;
-  if (n > 0 && !count) {
+  if (kept) {
+    sum = 1.0;   // kept weights are (nu + P) / (nu + d2) > 0 by construction
+  } else if (real) {
+    for (int64_t i = 0; i < n; ++i) {
+      if (!(weight[i] >= 0.0) || !std::isfinite(weight[i])) {
+        bad = fail(dst, PPLS_E_ARG, "weight %g of local row %lld is negative or not finite", weight[i], (long long)i);
+        break;
+      }
+      sum += weight[i];
+    }
+  } else if (n > 0 && !count) {
     bad = fail(dst, PPLS_E_ARG, "NULL counts for %lld local rows", (long long)n);
   } else {
     for (int64_t i = 0; i < n; ++i) {
@@ -6341,7 +6505,11 @@ int ppls_xprod_resample(ppls_ctx* dst, ppls_ctx* src, const int32_t* count) {
       dst->rs_part_len = 0;
       if (!(rc_alloc = dalloc(dst, &dst->rs_part, (size_t)need))) dst->rs_part_len = need;
     }
-    if (!rc_alloc && dst->rs_cnt_len < nrun) {
+    if (!rc_alloc && real && !kept && dst->rs_wt_len < nrun) {
+      dst->rs_wt_len = 0;
+      if (!(rc_alloc = dalloc(dst, &dst->rs_wt, (size_t)nrun))) dst->rs_wt_len = nrun;
+    }
+    if (!rc_alloc && !real && dst->rs_cnt_len < nrun) {
       dst->rs_cnt_len = 0;
       if (!(rc_alloc = dalloc(dst, &dst->rs_cnt, (size_t)nrun))) dst->rs_cnt_len = nrun;
     }
@@ -6364,11 +6532,11 @@ int ppls_xprod_resample(ppls_ctx* dst, ppls_ctx* src, const int32_t* count) {
   if (f[1] > 0.0) {
     dfree(Snew);
     if (bad) dst->err = bad_err;
-    return bad ? bad : fail(dst, PPLS_E_ARG, "resampled S: %d other rank(s) passed bad counts", (int)f[1]);
+    return bad ? bad : fail(dst, PPLS_E_ARG, "resampled S: %d other rank(s) passed bad %s", (int)f[1], real ? "weights" : "counts");
   }
-  if (!(f[2] >= 1.0)) {
+  if (real ? !(f[2] > 0.0) : !(f[2] >= 1.0)) {
     dfree(Snew);
-    return fail(dst, PPLS_E_ARG, "the counts sum to 0 over all ranks: a replicate needs rows");
+    return fail(dst, PPLS_E_ARG, real ? "the weights are all zero over all ranks" : "the counts sum to 0 over all ranks: a replicate needs rows");
   }
   // From here dst ends streamed on S_c, or without data.  Its own pending work first (an EM session may
   // still read the S that is about to be overwritten); the Gram then runs on src's stream, behind
@@ -6388,11 +6556,16 @@ int ppls_xprod_resample(ppls_ctx* dst, ppls_ctx* src, const int32_t* count) {
   dst->xp_active = false;
   dst->xp_pending_gram = false;
   if (!local && n > 0) {
-    hipError_t e = hipMemcpyAsync(dst->rs_cnt, count, sizeof(int32_t) * n, hipMemcpyHostToDevice, src->stream);
+    hipError_t e = hipSuccess;
+    // (kept: src->rb_w as it stands)
+    if (real && !kept) e = hipMemcpyAsync(dst->rs_wt, weight, sizeof(double) * n, hipMemcpyHostToDevice, src->stream);
+    else if (!real) e = hipMemcpyAsync(dst->rs_cnt, count, sizeof(int32_t) * n, hipMemcpyHostToDevice, src->stream);
     if (e != hipSuccess) local = fail(dst, PPLS_E_HIP, "resample: upload of the counts: %s", hipGetErrorString(e));
     // always the fp64 MFMA Gram (the int8 form does not take weights); src's record of how its own S was
     // formed (oz_used) is not touched
-    if (!local && (local = gram_run(src, g, n, 0, dst->xp_S, nullptr, dst->rs_part, dst->rs_cnt))) dst->err = src->err;
+    if (!local && (local = gram_run(src, g, n, 0, dst->xp_S, nullptr, dst->rs_part, real ? nullptr : dst->rs_cnt,
+                                    kept ? src->rb_w : real ? dst->rs_wt : nullptr)))
+      dst->err = src->err;
   } else if (!local) {
     if (hipMemsetAsync(dst->xp_S, 0, sizeof(double) * PP, src->stream) != hipSuccess)
       local = fail(dst, PPLS_E_HIP, "resample: zeroing S failed");
@@ -6422,7 +6595,7 @@ int ppls_xprod_resample(ppls_ctx* dst, ppls_ctx* src, const int32_t* count) {
   if (e != hipSuccess) return resample_drop(dst, fail(dst, PPLS_E_HIP, "resample: traces of S: %s", hipGetErrorString(e)));
   dst->ssq_host[0] = s2[0];
   dst->ssq_host[1] = s2[1];
-  dst->n_total = (int64_t)f[2];
+  dst->n_total = real ? src->n_total : (int64_t)f[2];   // real weights are relative to N
   dst->sc_center = src->sc_center;   // the rows keep the transform they carry in src
   dst->sc_scale = src->sc_scale;
   dst->mem_free_min = src->mem_free_min;
@@ -6431,6 +6604,18 @@ int ppls_xprod_resample(ppls_ctx* dst, ppls_ctx* src, const int32_t* count) {
   dst->xp_explicit = true;
   dst->have_data = true;
   return PPLS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ppls_xprod_resample(ppls_ctx* dst, ppls_ctx* src, const int32_t* count) {
+  return reweight_impl(dst, src, count, nullptr, false);
+}
+
+int ppls_xprod_weighted(ppls_ctx* dst, ppls_ctx* src, const double* weight) {
+  return reweight_impl(dst, src, nullptr, weight, true);
 }
 
 }  // extern "C"

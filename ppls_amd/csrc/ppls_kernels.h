@@ -195,6 +195,7 @@ hipError_t ppls_launch_to_rowmajor(const double* src, int64_t n, int p, int ld, 
 int ppls_gram_tiles(int p);
 int ppls_gram_occupancy(int f32);
 int ppls_gram_occupancy_weighted(int f32);   // the weighted instantiations' (equal: they share the grid and the plan)
+int ppls_gram_occupancy_real(int f32);       // the real-weighted instantiations' (equal too)
 // row splits for n rows (nsplit_req > 0: equal splits; 0: halving) and their bounds (nsplit + 1, nullable)
 int ppls_gram_plan(int p, int xreal, int xcols, int yreal, int64_t n, int wave_slots, int nsplit_req, int64_t* bounds);
 int64_t ppls_gram_part_doubles(int p, int nsplit);   // the per-item partials a launch writes

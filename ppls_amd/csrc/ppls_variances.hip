@@ -135,6 +135,20 @@ struct PplsGramOps<float> {
   __host__ __device__ static int col(int m, int i) { return 4 * i + m; }
 };
 
+// What weights a row's term: void (none), int32_t (a count) or PPLS_GRAM_WREAL (a real case
+// weight).  elem is what the device array and the ring hold; an unweighted kernel never reads it.
+#define PPLS_GRAM_WREAL double
+template <typename WT>
+struct PplsGramW {
+  typedef WT elem;
+  static constexpr bool weighted = true;
+};
+template <>
+struct PplsGramW<void> {
+  typedef int32_t elem;
+  static constexpr bool weighted = false;
+};
+
 // One work item = split s x lower tile t = (I, J) x quadrant, on ONE wave: its 64 x 64 output as 4 x 4
 // v_mfma_f64_16x16x4_f64 blocks (64 fp64 accumulators per lane), every MFMA operand loaded by the
 // lane that feeds it straight from global memory into a ring PPLS_GRING k-steps deep -- no LDS, no
@@ -147,14 +161,18 @@ struct PplsGramOps<float> {
 // WEIGHTED: sum_i cnt[i] d_i d_i' -- the lane that feeds row r0 + kr + 4 step loads that
 // row's count with the step's operands, into the same ring, and multiplies its four A operands by it
 // (B stays as loaded: each term is (c x_a) x_b); everything else, the item's sum order included, is
-// the unweighted form's.
-template <typename T, bool WEIGHTED>
+// the unweighted form's.  A real weight differs only in what the ring holds: a[m] = A.op(m) * w, one
+// rounding per A operand, where the count form's product is exact while |c x| needs no more than 53 bits.
+template <typename T, typename WT>
 __device__ __forceinline__ void ppls_gram_wave_item(const T* __restrict__ X, int ldx, int xcols, const T* __restrict__ Y,
                                                     int ldy, int ycols, int p, int ntiles, int it,
-                                                    const int64_t* __restrict__ bounds, const int32_t* __restrict__ cnt,
+                                                    const int64_t* __restrict__ bounds,
+                                                    const typename PplsGramW<WT>::elem* __restrict__ cnt,
                                                     double* __restrict__ part) {
   typedef double d4 __attribute__((ext_vector_type(4)));
   typedef PplsGramOps<T> Op;
+  typedef typename PplsGramW<WT>::elem WE;
+  constexpr bool WEIGHTED = PplsGramW<WT>::weighted;
   constexpr int D = PPLS_GRING;
   const int quad = it & 3, st = it >> 2;
   const int s = st / ntiles, t = st - s * ntiles;
@@ -180,10 +198,10 @@ __device__ __forceinline__ void ppls_gram_wave_item(const T* __restrict__ X, int
     base(J * PPLS_GT + (quad & 1) * PPLS_GQ + Op::lcol(l, li), &pb[l], &sb[l]);
   }
   Op ra[D], rb[D];
-  int32_t rw[D];   // WEIGHTED: the lane's row count of each k-step in flight (kept as loaded, converted at use)
+  WE rw[D];   // WEIGHTED: the lane's row count or weight of each k-step in flight (kept as loaded, converted at use)
   // (a wave-uniform base that advances with the steps plus the lane's constant row kr: the address costs
   // the ring no 64-bit per-lane pointer -- the fp64 form sits at the 256-VGPR limit of 2 waves per SIMD)
-  const int32_t* pw = nullptr;
+  const WE* pw = nullptr;
   if constexpr (WEIGHTED) pw = cnt + r0;
   auto ld_step = [&](int d) {
     ra[d].load(pa);
@@ -203,7 +221,7 @@ __device__ __forceinline__ void ppls_gram_wave_item(const T* __restrict__ X, int
   for (int m = 0; m < 4; ++m)
 #pragma unroll
     for (int q = 0; q < 4; ++q) acc[m][q] = d4{0.0, 0.0, 0.0, 0.0};
-  auto mma = [&](const Op& A, const Op& B, int32_t c) {
+  auto mma = [&](const Op& A, const Op& B, WE c) {
     double a[4], b[4];
     if constexpr (WEIGHTED) {
       const double w = (double)c;
@@ -253,7 +271,7 @@ __device__ __forceinline__ void ppls_gram_wave_item(const T* __restrict__ X, int
       A.v[l] = {};
       B.v[l] = {};
     }
-    int32_t c = 0;
+    WE c = 0;
     if (r0 + 4 * nfull + kr < r1) {   // (also the only rows whose count is read: none past r1)
       A.load(pa);
       B.load(pb);
@@ -276,12 +294,12 @@ __device__ __forceinline__ void ppls_gram_wave_item(const T* __restrict__ X, int
 // Persistent: one workgroup per resident slot (4 independent waves); every wave takes work items
 // from the queues (ppls_gram_next) until they are empty.  Each item's sums depend only on the item,
 // so the result is the same bit for bit whichever wave runs it.  rowcnt: one count per local row
-// (WEIGHTED; unread otherwise).
-template <typename T, bool WEIGHTED>
+// or one real weight (the weighted forms; unread otherwise).
+template <typename T, typename WT>
 __global__ __launch_bounds__(256, 2) void ppls_gram_mfma_kernel(const T* __restrict__ X, int ldx, int xcols,
                                                                  const T* __restrict__ Y, int ldy, int ycols, int p,
                                                                  int ntiles, int nsplit, int* __restrict__ queue,
-                                                                 const int32_t* __restrict__ rowcnt,
+                                                                 const typename PplsGramW<WT>::elem* __restrict__ rowcnt,
                                                                  double* __restrict__ part) {
   // queue = [qoff (9) | counters (8, zeroed before the launch) | pad | row bounds (nsplit + 1 int64) | items]
   const int* qoff = queue;
@@ -294,7 +312,7 @@ __global__ __launch_bounds__(256, 2) void ppls_gram_mfma_kernel(const T* __restr
     if (lane == 0) it = ppls_gram_next(cnt, qoff, items, g);
     it = __builtin_amdgcn_readfirstlane(it);
     if (it < 0) return;
-    ppls_gram_wave_item<T, WEIGHTED>(X, ldx, xcols, Y, ldy, ycols, p, ntiles, it, bounds, rowcnt, part);
+    ppls_gram_wave_item<T, WT>(X, ldx, xcols, Y, ldy, ycols, p, ntiles, it, bounds, rowcnt, part);
   }
 }
 
@@ -433,15 +451,23 @@ int ppls_gram_tiles(int p) {
 
 int ppls_gram_occupancy(int f32) {
   int occ = 0;
-  hipError_t e = f32 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ppls_gram_mfma_kernel<float, false>, 256, 0)
-                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ppls_gram_mfma_kernel<double, false>, 256, 0);
+  hipError_t e = f32 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ppls_gram_mfma_kernel<float, void>, 256, 0)
+                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ppls_gram_mfma_kernel<double, void>, 256, 0);
   return e == hipSuccess && occ > 0 ? occ : 1;
 }
 
 int ppls_gram_occupancy_weighted(int f32) {
   int occ = 0;
-  hipError_t e = f32 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ppls_gram_mfma_kernel<float, true>, 256, 0)
-                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ppls_gram_mfma_kernel<double, true>, 256, 0);
+  hipError_t e = f32 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ppls_gram_mfma_kernel<float, int32_t>, 256, 0)
+                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ppls_gram_mfma_kernel<double, int32_t>, 256, 0);
+  return e == hipSuccess && occ > 0 ? occ : 1;
+}
+
+int ppls_gram_occupancy_real(int f32) {
+  int occ = 0;
+  hipError_t e =
+      f32 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ppls_gram_mfma_kernel<float, PPLS_GRAM_WREAL>, 256, 0)
+          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ppls_gram_mfma_kernel<double, PPLS_GRAM_WREAL>, 256, 0);
   return e == hipSuccess && occ > 0 ? occ : 1;
 }
 
@@ -531,8 +557,8 @@ hipError_t ppls_gram_queue_prepare(int* queue, int p, int xreal, int xcols, int 
 
 hipError_t ppls_launch_gram_joint(const void* X, int ldx, int xcols, int xreal, const void* Y, int ldy, int ycols,
                                   int yreal, int f32, int64_t n, int p, int nsplit, double* part, int* queue,
-                                  const int32_t* cnt, hipStream_t st) {
-  if (n <= 0 || p <= 0 || nsplit < 1 || !queue || xcols + ycols < 1 || xreal > xcols || yreal > ycols)
+                                  const int32_t* cnt, const double* wt, hipStream_t st) {
+  if (n <= 0 || p <= 0 || nsplit < 1 || !queue || xcols + ycols < 1 || xreal > xcols || yreal > ycols || (cnt && wt))
     return hipErrorInvalidValue;
   const int ev = f32 ? 4 : 2;
   if (xcols % ev || ycols % ev) return hipErrorInvalidValue;
@@ -543,27 +569,34 @@ hipError_t ppls_launch_gram_joint(const void* X, int ldx, int xcols, int xreal, 
   const int grid = (cus * ppls_gram_occupancy(f32) + 7) / 8 * 8;
   hipError_t e = hipMemsetAsync(queue + 9, 0, 8 * sizeof(int), st);   // the queue counters
   if (e != hipSuccess) return e;
-  // cnt (n device counts, one per row): the weighted instantiation; the grid is the unweighted one's
-  // (the occupancies are equal, tests/test_gpu_resample.py), so are the queues and the split plan
+  // cnt (n device counts, one per row) or wt (n device weights): a weighted instantiation; the grid is
+  // the unweighted one's (the occupancies are equal, tests/test_gpu_resample.py, test_gpu_robust.py), so
+  // are the queues and the split plan
   const dim3 gd((unsigned)grid), bd(256);
-  if (f32 && cnt)
-    hipLaunchKernelGGL((ppls_gram_mfma_kernel<float, true>), gd, bd, 0, st, (const float*)X, ldx, xcols, (const float*)Y,
+  if (f32 && wt)
+    hipLaunchKernelGGL((ppls_gram_mfma_kernel<float, PPLS_GRAM_WREAL>), gd, bd, 0, st, (const float*)X, ldx, xcols,
+                       (const float*)Y, ldy, ycols, p, ntiles, nsplit, queue, wt, part);
+  else if (wt)
+    hipLaunchKernelGGL((ppls_gram_mfma_kernel<double, PPLS_GRAM_WREAL>), gd, bd, 0, st, (const double*)X, ldx, xcols,
+                       (const double*)Y, ldy, ycols, p, ntiles, nsplit, queue, wt, part);
+  else if (f32 && cnt)
+    hipLaunchKernelGGL((ppls_gram_mfma_kernel<float, int32_t>), gd, bd, 0, st, (const float*)X, ldx, xcols, (const float*)Y,
                        ldy, ycols, p, ntiles, nsplit, queue, cnt, part);
   else if (f32)
-    hipLaunchKernelGGL((ppls_gram_mfma_kernel<float, false>), gd, bd, 0, st, (const float*)X, ldx, xcols, (const float*)Y,
+    hipLaunchKernelGGL((ppls_gram_mfma_kernel<float, void>), gd, bd, 0, st, (const float*)X, ldx, xcols, (const float*)Y,
                        ldy, ycols, p, ntiles, nsplit, queue, cnt, part);
   else if (cnt)
-    hipLaunchKernelGGL((ppls_gram_mfma_kernel<double, true>), gd, bd, 0, st, (const double*)X, ldx, xcols,
+    hipLaunchKernelGGL((ppls_gram_mfma_kernel<double, int32_t>), gd, bd, 0, st, (const double*)X, ldx, xcols,
                        (const double*)Y, ldy, ycols, p, ntiles, nsplit, queue, cnt, part);
   else
-    hipLaunchKernelGGL((ppls_gram_mfma_kernel<double, false>), gd, bd, 0, st, (const double*)X, ldx, xcols,
+    hipLaunchKernelGGL((ppls_gram_mfma_kernel<double, void>), gd, bd, 0, st, (const double*)X, ldx, xcols,
                        (const double*)Y, ldy, ycols, p, ntiles, nsplit, queue, cnt, part);
   return hipGetLastError();
 }
 
 hipError_t ppls_launch_gram(const void* X, int f32, int64_t n, int ld, int p, int nsplit, double* part, int* queue,
                             hipStream_t st) {
-  return ppls_launch_gram_joint(X, ld, ld, p, nullptr, 0, 0, 0, f32, n, p, nsplit, part, queue, nullptr, st);
+  return ppls_launch_gram_joint(X, ld, ld, p, nullptr, 0, 0, 0, f32, n, p, nsplit, part, queue, nullptr, nullptr, st);
 }
 
 hipError_t ppls_launch_gram_finish(const double* part, int nsplit, int p, int xreal, int xcols, int yreal, double* G,

@@ -21,10 +21,12 @@ extern "C" {
 // (ppls_gram_part_doubles), by persistent waves taking items from `queue` (ppls_gram_queue_ints(p,
 // nsplit) device ints, filled once by ppls_gram_queue_prepare); ppls_launch_gram_finish sums and
 // mirrors them.  cnt: NULL, or n device counts >= 0, one per row: sum_i cnt[i] d_i d_i', the Gram of
-// the rows with row i repeated cnt[i] times (the weighted instantiation).
+// the rows with row i repeated cnt[i] times (the weighted instantiation).  wt: NULL, or n
+// device weights >= 0, one per row: sum_i wt[i] d_i d_i' with each term formed as (wt[i] x_a) x_b (the
+// real-weighted instantiation).  At most one of cnt, wt.
 hipError_t ppls_launch_gram_joint(const void* X, int ldx, int xcols, int xreal, const void* Y, int ldy, int ycols,
                                   int yreal, int f32, int64_t n, int p, int nsplit, double* part, int* queue,
-                                  const int32_t* cnt, hipStream_t st);
+                                  const int32_t* cnt, const double* wt, hipStream_t st);
 
 // Rows of S per wave of the tile kernel (rw_opt 1, 2, 4 or 8 (r <= 8) forces it; 0 = auto).
 int ppls_xprod_tile_rows(int P, int r, int rw_opt, int num_cus);

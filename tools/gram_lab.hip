@@ -364,7 +364,7 @@ int main(int argc, char** argv) {
   for (int req : {nsplit, 0}) {
     (void)ppls_gram_queue_prepare(queue, P, P, P, 0, n, wave_slots, req, 0);
     const int ns = ppls_gram_plan(P, P, P, 0, n, wave_slots, req, nullptr);
-    ms = timeit([&] { (void)ppls_launch_gram_joint(X, P, P, P, nullptr, 0, 0, 0, 0, n, P, ns, part, queue, nullptr, 0); }, reps);
+    ms = timeit([&] { (void)ppls_launch_gram_joint(X, P, P, P, nullptr, 0, 0, 0, 0, n, P, ns, part, queue, nullptr, nullptr, 0); }, reps);
     (void)ppls_launch_gram_finish(part, ns, P, P, P, 0, G, 0);
     (void)hipDeviceSynchronize();
     char name[96];
