@@ -194,6 +194,51 @@ int ppls_scale_data(ppls_ctx* ctx, int center, int scale);
  * ppls_set_data_from copies the source's. */
 int ppls_get_scaling(ppls_ctx* ctx, double* center, double* scale);
 
+/* Covariate adjustment of the resident data, in place: X and Y <- their least-squares residuals on the
+ * design [1 Z] (intercept = 1) or Z (intercept = 0) over ALL ranks' rows -- R's
+ * resid(lm(cbind(X, Y) ~ Z)); centring is the case Z = 1.  Z: this rank's n_local x k host rows in
+ * `layout`; k1 = k + intercept design columns, 1 <= k1 <= 16.  The host centres (intercept = 1) and
+ * unit-scales Z's columns and orthonormalises them, together with the constant column, by two rounds of
+ * Cholesky-QR (fixed-order sums, one all-reduce of the k1 x k1 Gram per round, and one of k + 1 doubles
+ * for the means before them); the
+ * device forms G = Q'[X Y] in one read of the rows (fixed-order sums, bitwise repeatable; sharded: one
+ * all-reduce of G) and subtracts Q G in place: one fma chain per element in fp64 (fp32 storage: one
+ * rounding, at the store).  N stays n_total: no degrees-of-freedom correction, as in the reference.
+ * Aliased covariates are refused, not dropped: a column whose centred norm is at most 1e-7 of its raw
+ * norm (constant beside the intercept), or whose Cholesky pivot given the columns before it is at most
+ * 1e-7 (lm.fit's tol), is PPLS_E_ARG, and the message names the column, 1-based.  PPLS_E_ARG also: Z
+ * NULL on a rank with rows or a NaN / Inf in Z on any rank, k < 1 or k1 > 16, n_total <= k1.
+ * PPLS_E_STATE: no data, a streamed context or an open stream, data that ppls_scale_data has changed
+ * (adjust before scaling: R's resid(), then scale()), data that are adjusted already.  Every refusal
+ * is taken on all ranks alike and leaves the rows and the records untouched.  Afterwards the context
+ * is as if the residuals had been loaded with ppls_set_data, exactly as after ppls_scale_data (||X||^2,
+ * ||Y||^2 recomputed, S, the meta_xprod matrices and kept robust weights dropped, an ppls_em_begin
+ * session ended); ppls_scale_data after it composes.  A rank with n_local = 0 still joins. */
+int ppls_adjust_data(ppls_ctx* ctx, const double* Z, int k, int layout, int intercept);
+/* The covariate part of the transform the data carry:
+ *   loaded = resident * scale + center + (z - zcenter) Gamma
+ * with scale, center of ppls_get_scaling (center: the column means with an intercept, else 0), zcenter
+ * (k) Z's column means (0 without an intercept) and Gamma k x (p + q) row-major (X's columns, then
+ * Y's), in the loaded units.  Each output nullable; *k = 0 when the data are not adjusted (nothing else
+ * is written then).  ppls_set_data_from and the derived cross-product contexts copy it; ppls_set_data,
+ * the generator and ppls_stream_begin clear it. */
+int ppls_get_adjustment(ppls_ctx* ctx, int* k, double* zcenter, double* Gamma);
+/* The same adjustment for contexts that hold only S.  src's LAST k columns of Y are the covariates
+ * (its shape is p, q + k; 1 <= k <= 16, k < q_src); dst receives the cross-products of [X | Y_1..q] with
+ * those columns partialled out, the Schur complement S_dd - S_dz S_zz^-1 S_zd = S_dd - F F', F = S_dz
+ * L^-T, as a context that holds S and no rows (the lifecycle of ppls_xprod_resample's dst).  There is
+ * no intercept here: a src that was streamed or scaled with center = 1 has removed it.  src: streamed
+ * without folds, a resample / permute / weighted destination, or resident (S is then formed and kept,
+ * as ppls_xprod_downdate does).  S is the same on every rank, so nothing below is collective.  scale =
+ * 1: then d_j = sqrt(S_jj / (n_total - 1)) and S_ij /= d_i d_j.  dst afterwards: n_total src's, ||X||^2,
+ * ||Y||^2 the traces, the scaling record src's for the kept columns composed with d, the adjustment
+ * record zcenter = src's centres of the k columns and Gamma = S_zz^-1 S_zd in src's units; a repeated
+ * call of unchanged shape reuses dst's S.  PPLS_E_ARG, with dst as it was: k out of range, dst == src,
+ * contexts on different devices, S_zz singular (a zero diagonal entry, or a pivot of its unit-diagonal
+ * form at most 1e-7; the message names the column), scale = 1 with a d_j that is not > 0 or not finite.
+ * PPLS_E_STATE: src without data, with an open stream, or streamed with folds. */
+int ppls_xprod_adjust(ppls_ctx* dst, ppls_ctx* src, int k, int scale);
+
 /* ---- the hot path ------------------------------------------------------------------------ */
 int ppls_estep(ppls_ctx* ctx, const ppls_theta* th, int r, ppls_expect* out);
 int ppls_mstep(ppls_ctx* ctx, const ppls_expect* fit, int r, int type, ppls_theta* out);

@@ -244,6 +244,28 @@ int ppls_rowdiag_timing(ppls_ctx* ctx, int r, int reps, double* ms /* [2] */);
  * kept weights are not touched. */
 int ppls_robust_timing(ppls_ctx* ctx, int reps, double* ms /* [2] */);
 
+/* ppls_adjust_data's coefficient pass and its reduce alone on the resident rows with a caller-supplied
+ * Q (this rank's n_local x k1 rows, row-major; 1 <= k1 <= 16): G (k1 x (p + q), row-major) = Q'[X Y]
+ * over all ranks' rows.  The data are not modified.  Collective when the rows are sharded. */
+int ppls_adjust_coef(ppls_ctx* ctx, const double* Q, int k1, double* G);
+/* What those passes run for k1 design columns on the resident rows: *kt the tile (4, 8 or 16) and
+ * plans[10] = {tx, ty, grid_x, grid_y, nblocks} of X's launch, then of Y's (ppls_scale_plan). */
+int ppls_adjust_info(ppls_ctx* ctx, int k1, int* kt, int64_t* plans);
+/* sum_a G_aj^2 per column (p + q values) of the last ppls_adjust_data on these data: the sum of
+ * squares the design explained (with an intercept: the mean's share included). */
+int ppls_adjust_explained(ppls_ctx* ctx, double* ss);
+/* ppls_xprod_adjust's Schur kernel alone on a host matrix, uploaded and downloaded around one launch
+ * (and, with scale = 1, the stream's standardise pass with d_j = sqrt(S_jj): a unit diagonal): S_src
+ * is row-major (ldx + ldy_src)^2 in the joint layout of p and q_src columns, its last k real Y columns
+ * the covariates; S_dst receives the (ldx + ldy_dst)^2 matrix of p and q_src - k columns (ldx, ldy_src,
+ * ldy_dst even, ldy_dst <= ldy_src).  The output is written between NaN guards, which are checked. */
+int ppls_xadjust_matrix(ppls_ctx* ctx, const double* S_src, int p, int ldx, int q_src, int ldy_src, int k, int ldy_dst,
+                        int scale, double* S_dst);
+/* HIP-event times (ms) of the last coefficient pass (partials + reduce, X and Y), apply pass, Schur pass
+ * and, behind a Schur pass with scale = 1, the stream's standardise pass on the same matrix (else 0) on
+ * this context (ppls_xprod_adjust records on dst). */
+int ppls_adjust_timing(ppls_ctx* ctx, double* ms4);
+
 #ifdef __cplusplus
 }
 #endif

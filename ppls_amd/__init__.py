@@ -7,13 +7,13 @@ from ._lib import PPLS_ORTH_QR, PPLS_ORTH_SVD, Expect, PplsError, Theta  # noqa:
 from .api import (PPLS, Context, Expect_M, Maximiz_M, PPLS_simult, PPLS_simult_to_o2m, PPLS_to_o2m, PPLSi,  # noqa: F401
                   default_context, fconstraint, initial_guess, logl_W, loglC_fast, meta_EMstep, meta_PPLSi,
                   print_PPLS, random_theta0, scores_PPLS, variances_PPLS_simult, cv_blocks, predict_PPLS, cv_PPLS,
-                  crossval_PPLS, scale_data, stream_data, fold_labels, population_labels, bootstrap_counts,
+                  crossval_PPLS, scale_data, adjust_data, adjust_new, stream_data, fold_labels, population_labels, bootstrap_counts,
                   align_signs, bootstrap_summary, bootstrap_PPLS_simult, permutation_indices, permutation_pvalues,
                   permutation_PPLS, diagnostics_PPLS, robust_PPLS_simult)
 
 __all__ = ["Context", "fconstraint", "Expect_M", "Maximiz_M", "PPLS_simult", "PPLS", "PPLSi", "initial_guess", "print_PPLS", "scores_PPLS",
            "PPLS_simult_to_o2m", "PPLS_to_o2m", "meta_EMstep", "meta_PPLSi", "variances_PPLS_simult", "logl_W", "loglC_fast", "Theta",
            "Expect", "PplsError", "random_theta0", "default_context", "PPLS_ORTH_SVD", "PPLS_ORTH_QR",
-           "cv_blocks", "predict_PPLS", "cv_PPLS", "crossval_PPLS", "scale_data", "stream_data", "fold_labels", "population_labels",
+           "cv_blocks", "predict_PPLS", "cv_PPLS", "crossval_PPLS", "scale_data", "adjust_data", "adjust_new", "stream_data", "fold_labels", "population_labels",
            "bootstrap_counts", "align_signs", "bootstrap_summary", "bootstrap_PPLS_simult", "permutation_indices",
            "permutation_pvalues", "permutation_PPLS", "diagnostics_PPLS", "robust_PPLS_simult"]

@@ -209,6 +209,15 @@ SIGNATURES = {
     "ppls_o2m_info": (ct.c_int, [ct.c_void_p, ct.POINTER(ct.c_int), ct.POINTER(ct.c_int), ct.POINTER(ct.c_int), _dp, _dp,
                                  ct.POINTER(ct.c_int)]),
     "ppls_o2m_pass_timing": (ct.c_int, [ct.c_void_p, ct.c_int, _dp, _dp, ct.POINTER(ct.c_int)]),
+    "ppls_adjust_data": (ct.c_int, [ct.c_void_p, _dp, ct.c_int, ct.c_int, ct.c_int]),
+    "ppls_get_adjustment": (ct.c_int, [ct.c_void_p, ct.POINTER(ct.c_int), _dp, _dp]),
+    "ppls_xprod_adjust": (ct.c_int, [ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_int]),
+    "ppls_adjust_coef": (ct.c_int, [ct.c_void_p, _dp, ct.c_int, _dp]),
+    "ppls_adjust_info": (ct.c_int, [ct.c_void_p, ct.c_int, ct.POINTER(ct.c_int), _i64p]),
+    "ppls_adjust_explained": (ct.c_int, [ct.c_void_p, _dp]),
+    "ppls_xadjust_matrix": (ct.c_int, [ct.c_void_p, _dp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int,
+                                       ct.c_int, _dp]),
+    "ppls_adjust_timing": (ct.c_int, [ct.c_void_p, _dp]),
 }
 
 

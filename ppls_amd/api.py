@@ -58,6 +58,7 @@ class Context:
         self.n_local = self.n_total = None
         self.row0 = 0
         self._stream_folds = None     # K while the context is (being) streamed with folds
+        self._reducer_fn = None       # the host reducer in place of RCCL (set_reducer)
 
     # -- plumbing
     def _chk(self, rc):
@@ -109,6 +110,7 @@ class Context:
         numpy view of the buffer and must overwrite it in place with its sum over all ranks (e.g.
         ``torch.distributed.all_reduce`` on gloo).  ``None`` restores RCCL.  Collective when data
         is resident."""
+        self._reducer_fn = fn
         if fn is None:
             self._reducer_cb = None
             self._chk(self._L.ppls_set_reducer(self.h, None, None))
@@ -205,6 +207,92 @@ class Context:
         ms, by = np.zeros(3), np.zeros(3)
         self._chk(self._L.ppls_scale_timing(self.h, dptr(ms), dptr(by)))
         return dict(ms=ms, bytes=by)
+
+    # -- covariate adjustment
+    @staticmethod
+    def _design(Z, n):
+        Z = np.asarray(Z, dtype=np.float64)
+        if Z.ndim == 1:
+            Z = Z.reshape(-1, 1)
+        if Z.ndim != 2 or Z.shape[0] != n:
+            raise ValueError(f"Z must be a matrix with one row per local row ({n}), got shape {Z.shape}")
+        return np.ascontiguousarray(Z)
+
+    def adjust_data(self, Z, intercept=True):
+        """R's ``resid(lm(cbind(X, Y) ~ Z))`` on the resident data, in place on the device
+        (ppls_adjust_data): X and Y become their least-squares residuals on ``[1 Z]`` (or ``Z``) over all
+        ranks' rows.  ``Z``: this rank's n_local x k covariate rows.  Collective when the rows are
+        sharded.  An aliased or constant covariate is an argument error and leaves the data untouched;
+        adjust before ``scale_data``."""
+        Z = self._design(Z, self.n_local)
+        self._chk(self._L.ppls_adjust_data(self.h, dptr(Z) if Z.size else None, Z.shape[1], _lib.PPLS_LAYOUT_ROWMAJOR,
+                                           int(bool(intercept))))
+
+    def adjustment(self):
+        """The covariate part of the transform the data carry (ppls_get_adjustment):
+        ``loaded = resident * scale + center + (z - zcenter) @ Gamma`` with ``scaling()``'s centre and
+        scale, as ``dict(k, zcenter, coefX, coefY)`` (k x p and k x q, in the loaded units); k = 0 and
+        empty arrays when the data are not adjusted."""
+        k = ct.c_int()
+        self._chk(self._L.ppls_get_adjustment(self.h, ct.byref(k), None, None))
+        zc = np.zeros(k.value)
+        G = np.zeros((k.value, self.p + self.q))
+        if k.value:
+            self._chk(self._L.ppls_get_adjustment(self.h, ct.byref(k), dptr(zc), dptr(G)))
+        return dict(k=k.value, zcenter=zc, coefX=G[:, : self.p].copy(), coefY=G[:, self.p:].copy())
+
+    def adjust_explained(self):
+        """Per column of X, then of Y: the sum of squares the design explained in the last
+        ``adjust_data`` (ppls_adjust_explained), sum_a G_aj^2."""
+        ss = np.zeros(self.p + self.q)
+        self._chk(self._L.ppls_adjust_explained(self.h, dptr(ss)))
+        return ss
+
+    def xprod_adjust(self, src: "Context", k, scale=False):
+        """This context's cross-products := ``src``'s with its last ``k`` Y columns partialled out of
+        the others (ppls_xprod_adjust): the Schur complement, for a ``src`` that holds S (streamed
+        without folds, a resample / permute / weighted destination) or resident rows.  This context ends
+        streamed (S, no rows) with shape p, q_src - k; ``scale=True`` standardises the result."""
+        self._chk(self._L.ppls_xprod_adjust(self.h, src.h, int(k), int(bool(scale))))
+        self.p, self.q, self.n_local, self.row0 = src.p, src.q - int(k), 0, 0
+        self.n_total = self.stream_info()["n_total"]
+        self._stream_folds = None
+
+    def adjust_coef(self, Q):
+        """Q'[X Y] over the resident rows by adjust_data's coefficient pass and its reduce alone
+        (ppls_adjust_coef): ``Q`` is this rank's n_local x k1 rows; returns k1 x (p + q).  The data
+        are not modified."""
+        Q = self._design(Q, self.n_local)
+        G = np.zeros((Q.shape[1], self.p + self.q))
+        self._chk(self._L.ppls_adjust_coef(self.h, dptr(Q) if Q.size else None, Q.shape[1], dptr(G)))
+        return G
+
+    def adjust_info(self, k1):
+        """The tile and launch shapes of the adjustment's row passes for ``k1`` design columns
+        (ppls_adjust_info): ``dict(kt, X=dict(tx, ty, grid_x, grid_y, nblocks), Y=...)``."""
+        kt = ct.c_int()
+        pl = np.zeros(10, dtype=np.int64)
+        self._chk(self._L.ppls_adjust_info(self.h, int(k1), ct.byref(kt), pl.ctypes.data_as(_lib._i64p)))
+        names = ("tx", "ty", "grid_x", "grid_y", "nblocks")
+        return dict(kt=kt.value, X=dict(zip(names, map(int, pl[:5]))), Y=dict(zip(names, map(int, pl[5:]))))
+
+    def xadjust_matrix(self, S_src, p, ldx, q_src, ldy_src, k, ldy_dst, scale=False):
+        """The Schur kernel of ``xprod_adjust`` alone on a host matrix in the joint padded layout
+        (ppls_xadjust_matrix): returns the (ldx + ldy_dst)^2 result, padding included."""
+        S = np.ascontiguousarray(S_src, dtype=np.float64)
+        if S.shape != (ldx + ldy_src, ldx + ldy_src):
+            raise ValueError("S_src must be (ldx + ldy_src) x (ldx + ldy_src)")
+        out = np.full((ldx + ldy_dst, ldx + ldy_dst), np.nan)
+        self._chk(self._L.ppls_xadjust_matrix(self.h, dptr(S), int(p), int(ldx), int(q_src), int(ldy_src), int(k),
+                                              int(ldy_dst), int(bool(scale)), dptr(out)))
+        return out
+
+    def adjust_timing(self):
+        """HIP-event ms of the last coefficient pass, apply pass, Schur pass and the standardise pass
+        behind a scaled Schur pass (ppls_adjust_timing)."""
+        ms = np.zeros(4)
+        self._chk(self._L.ppls_adjust_timing(self.h, dptr(ms)))
+        return dict(coef=ms[0], apply=ms[1], schur=ms[2], standardise=ms[3])
 
     # -- streamed data: S from row chunks, no rows resident
     def stream_begin(self, p, q, center=False, scale=False, nr_folds=None):
@@ -2382,6 +2470,62 @@ def scale_data(X=None, Y=None, center=True, scale=True, ctx=None):
     return ctx.scaling()
 
 
+# ---------------------------------------------------------------------------- covariate adjustment
+def _adjust_record(ctx):
+    """adjust_data's result from the context's two records."""
+    sc, ad = ctx.scaling(), ctx.adjustment()
+    return dict(coefX=ad["coefX"], coefY=ad["coefY"], zcenter=ad["zcenter"], centerX=sc["centerX"], centerY=sc["centerY"])
+
+
+def adjust_data(X=None, Y=None, Z=None, intercept=True, ctx=None):
+    """R's ``X <- resid(lm(X ~ Z)); Y <- resid(lm(Y ~ Z))`` on the device, in place: age, sex, batch or
+    ancestry components regressed out of both blocks before a fit, without a host round trip.  ``X``,
+    ``Y``: loaded first if given, else the context's resident data are adjusted; ``Z``: the n x k
+    covariates (this rank's rows).  Returns ``dict(coefX, coefY, zcenter, centerX, centerY,
+    ss_explainedX, ss_explainedY)``: ``lm``'s slopes (k x p, k x q), the covariate and column means
+    (0 without an intercept) and, per column, the sum of squares the design explained.  The residuals
+    stay resident: ``adjust_data(X, Y, Z, ctx=ctx); scale_data(ctx=ctx); PPLS(None, None, 3, ctx=ctx)``."""
+    if Z is None:
+        raise ValueError("adjust_data needs the covariates Z")
+    ctx = _ctx_with(X, Y, ctx)
+    ctx.adjust_data(Z, intercept)
+    out = _adjust_record(ctx)
+    ss = ctx.adjust_explained()
+    out["ss_explainedX"], out["ss_explainedY"] = ss[: ctx.p].copy(), ss[ctx.p:].copy()
+    return out
+
+
+def adjust_new(ctx, Xnew=None, Ynew=None, Znew=None):
+    """Raw rows in the context's resident units, on the host, from its two records:
+    ``(new - center - (Znew - zcenter) @ coef) / scale``.  Either of ``Xnew``, ``Ynew`` may be None;
+    returns the pair.  On an adjusted context ``Znew`` is required -- the adjustment is never skipped
+    silently; on any other it must be None or is ignored, and only centre and scale apply."""
+    sc, ad = ctx.scaling(), ctx.adjustment()
+    Zc = None
+    if ad["k"]:
+        if Znew is None:
+            raise ValueError("the context's data were adjusted for covariates: new rows need their Z")
+        Zc = np.asarray(Znew, dtype=np.float64)
+        if Zc.ndim != 2:
+            Zc = Zc.reshape(-1, ad["k"])      # one row of k values, or a column for k = 1
+        if Zc.shape[1] != ad["k"]:
+            raise ValueError(f"Znew has {Zc.shape[1]} columns, the adjustment {ad['k']}")
+        Zc = Zc - ad["zcenter"]
+    out = []
+    for new, b in ((Xnew, "X"), (Ynew, "Y")):
+        if new is None:
+            out.append(None)
+            continue
+        new = np.asarray(new, dtype=np.float64)
+        if new.ndim != 2:
+            new = new.reshape(1, -1)
+        if Zc is not None and Zc.shape[0] != new.shape[0]:
+            raise ValueError("Znew needs one row per new row")
+        fit = Zc @ ad["coef" + b] if Zc is not None else 0.0
+        out.append((new - sc["center" + b] - fit) / sc["scale" + b])
+    return tuple(out)
+
+
 def _chunk_arrays(X, Y, p=None, q=None):
     """One chunk as float64 matrices in one memory order, and that order's layout code: F-contiguous
     pairs go as they are (column-major), everything else C-contiguous (copied only if it is not)."""
@@ -2410,7 +2554,50 @@ def _fold_array(fold, n, K=None):
     return np.ascontiguousarray(f, dtype=np.int32)
 
 
-def stream_data(chunks, center=True, scale=True, ctx=None, nr_folds=None):
+def _stream_covariates(chunks, scale, ctx):
+    """stream_data(covariates=True): [Y Z] streamed centred into a private source, then partialled out."""
+    if isinstance(chunks, np.ndarray) or not hasattr(chunks, "__iter__"):
+        raise TypeError("chunks must be an iterable of (X, Y, Z) triples")
+    ctx = ctx or default_context()
+    src = None
+    try:
+        p = q = k = None
+        for tri in chunks:
+            if not isinstance(tri, (tuple, list)) or len(tri) != 3:
+                raise TypeError("every chunk must be an (X, Y, Z) triple")
+            X = np.asarray(tri[0], dtype=np.float64)
+            Z = Context._design(tri[2], X.shape[0] if X.ndim == 2 else -1)
+            Y = np.asarray(tri[1], dtype=np.float64)
+            if Y.ndim != 2 or Y.shape[0] != Z.shape[0]:
+                raise ValueError("a chunk is a triple of matrices X, Y, Z with the same number of rows")
+            if k is not None and Z.shape[1] != k:
+                raise ValueError(f"chunk with {Z.shape[1]} covariates in a stream of {k}")
+            YZ = np.ascontiguousarray(np.hstack([Y, Z]))
+            X, YZ, _ = _chunk_arrays(X, YZ, p, None if q is None else q + k)
+            if src is None:
+                p, q, k = X.shape[1], Y.shape[1], Z.shape[1]
+                if k < 1:
+                    raise ValueError("covariates=True needs at least one column of Z")
+                src = Context(ctx.device)
+                if getattr(ctx, "_reducer_fn", None) is not None:
+                    src.set_reducer(ctx._reducer_fn)     # the same ranks take part
+                src.stream_begin(p, q + k, True, False)
+            src.stream_rows(X, YZ)
+        if src is None:
+            raise ValueError("chunks is empty: no rows to stream")
+        src.stream_end()
+        ctx.xprod_adjust(src, k, scale)
+    finally:
+        if src is not None:
+            src.close()
+    out = dict(n=ctx.n_total)
+    out.update(ctx.scaling())
+    ad = ctx.adjustment()
+    out.update(coefX=ad["coefX"], coefY=ad["coefY"], zcenter=ad["zcenter"])
+    return out
+
+
+def stream_data(chunks, center=True, scale=True, ctx=None, nr_folds=None, covariates=False):
     """Load data too large to hold at once: ``chunks`` is an iterable of ``(X, Y)`` row blocks (numpy
     matrices, e.g. slices of a memory-mapped file).  Their cross-products -- of the rows centred and
     scaled as R's ``scale()`` would the whole matrix -- are accumulated on the device; no rows stay
@@ -2418,7 +2605,19 @@ def stream_data(chunks, center=True, scale=True, ctx=None, nr_folds=None):
     ``PPLS(None, None, a, ctx=ctx)`` and ``PPLS_simult(None, None, a, ctx=ctx)`` fit from them.
     ``nr_folds=K``: every chunk is an ``(X, Y, fold)`` triple with the fold (0 .. K-1) of each row
     (``fold_labels`` gives cv_PPLS's); one cross-product matrix per fold is kept, the result gains
-    ``fold_total``, and ``cv_PPLS(None, None, a, K, ctx=ctx)`` / ``crossval_PPLS`` run on them."""
+    ``fold_total``, and ``cv_PPLS(None, None, a, K, ctx=ctx)`` / ``crossval_PPLS`` run on them.
+    ``covariates=True``: every chunk is an ``(X, Y, Z)`` triple; ``[Y Z]`` is streamed centred into a
+    private context and the covariates are partialled out of the cross-products on the device
+    (``Context.xprod_adjust``), which is ``adjust_data`` with an intercept followed by ``scale_data(center
+    =True, scale=scale)`` for rows that are never resident; the result gains ``coefX``, ``coefY`` and
+    ``zcenter``.  It needs ``center=True`` and cannot be combined with ``nr_folds``; ranks take part
+    through a host reducer (``set_reducer``)."""
+    if covariates:
+        if nr_folds is not None:
+            raise ValueError("covariates=True cannot be combined with nr_folds: per-fold adjustment is not provided")
+        if not center:
+            raise ValueError("covariates=True implies an intercept: center must be True")
+        return _stream_covariates(chunks, scale, ctx)
     want = 2 if nr_folds is None else 3
     what = "(X, Y) pair" if nr_folds is None else "(X, Y, fold) triple"
     if nr_folds is not None and int(nr_folds) < 2:
@@ -2477,7 +2676,7 @@ def _fit_parts(obj):
     return W, C, est["B"]
 
 
-def predict_PPLS(object, newdata, XorY=("X", "Y"), ctx=None, rescale=False):
+def predict_PPLS(object, newdata, XorY=("X", "Y"), ctx=None, rescale=False, Znew=None):
     """predict.PPLS (crossval_PPLS.R:12-24): ``newdata W diag(B) C'`` for XorY = "X" (newdata is X,
     the prediction is of Y) or ``newdata C diag(1/B) W'`` for "Y", on the GPU.  A 1-D ``newdata`` is
     one row (R's ``t(newdata)``).  ``ctx``: a context whose data have the fit's shape; by default
@@ -2485,7 +2684,9 @@ def predict_PPLS(object, newdata, XorY=("X", "Y"), ctx=None, rescale=False):
     ``rescale=True``: ``newdata`` is in the units the data were loaded in; with a context whose data
     were scaled on the device (``scale_data``) it is brought to the fit's scale with the stored
     centre and scale of its block, on the host, and the prediction is mapped back to the loaded
-    units of the other block."""
+    units of the other block.  With a context whose data were adjusted for covariates (``adjust_data``)
+    ``Znew``, the new rows' covariates, is required then: their fitted share is taken out of
+    ``newdata`` and added to the prediction (``adjust_new``)."""
     global _PREDICT_CTX
     xy = XorY if isinstance(XorY, str) else XorY[0]          # match.arg
     if xy not in ("X", "Y"):
@@ -2505,6 +2706,13 @@ def predict_PPLS(object, newdata, XorY=("X", "Y"), ctx=None, rescale=False):
         ctx = _PREDICT_CTX
         if (ctx.p, ctx.q) != (p, q):
             ctx.set_data(np.zeros((0, p)), np.zeros((0, q)))   # the shape only
+    if rescale and ctx.adjustment()["k"]:
+        ad, sc = ctx.adjustment(), ctx.scaling()
+        other = "Y" if xy == "X" else "X"
+        x = adjust_new(ctx, nd if xy == "X" else None, nd if xy == "Y" else None, Znew)[0 if xy == "X" else 1]
+        Zc = np.asarray(Znew, dtype=np.float64).reshape(nd.shape[0], ad["k"]) - ad["zcenter"]
+        return (ctx.predict(W, C, B, x, 0 if xy == "X" else 1) * sc["scale" + other] + sc["center" + other]
+                + Zc @ ad["coef" + other])
     if rescale:
         sc = ctx.scaling()
         cin, sin, cout, sout = ((sc["centerX"], sc["scaleX"], sc["centerY"], sc["scaleY"]) if xy == "X" else
@@ -2738,7 +2946,7 @@ def diagnostics_summary(res, p, q, r, sigE, sigF, alpha=0.01, adjust="none"):
 
 
 def diagnostics_PPLS(fit, X=None, Y=None, ctx=None, subset=None, new=False, rescale=False, alpha=0.01, adjust="none",
-                     want_mu=False):
+                     want_mu=False, Z=None):
     """Which rows does a ``PPLS_simult`` fit not explain?  Per row, on the GPU in one pass over the rows:
     the squared Mahalanobis distance ``d2`` under the fitted covariance, its in-plane part ``sd2`` (score
     distance) and off-plane parts ``odx2``, ``ody2`` (squared orthogonal distances in X and Y) and the
@@ -2751,7 +2959,8 @@ def diagnostics_PPLS(fit, X=None, Y=None, ctx=None, subset=None, new=False, resc
     are rows scored against the fit without touching the context's data (any context of the fit's shape:
     streamed, or without rows); with ``rescale=True`` they come in the units the data were loaded in and
     are brought to the fit's with ``ctx.scaling()`` on the host, as ``predict_PPLS`` does -- called once
-    per chunk this is the second pass that screens a ``stream_data`` fit."""
+    per chunk this is the second pass that screens a ``stream_data`` fit.  On a context whose data were
+    adjusted for covariates ``rescale=True`` needs ``Z``, the new rows' covariates (``adjust_new``)."""
     global _PREDICT_CTX
     if adjust not in ("none", "bonferroni"):
         raise ValueError("adjust should be one of \"none\", \"bonferroni\"")
@@ -2787,8 +2996,12 @@ def diagnostics_PPLS(fit, X=None, Y=None, ctx=None, subset=None, new=False, resc
             raise ValueError("Number of columns mismatch!")
         if subset is not None:
             idx = np.ravel(np.asarray(subset, dtype=np.int64))
+            if Z is not None:
+                Z = np.asarray(Z, dtype=np.float64).reshape(X.shape[0], -1)[idx]
             X, Y = X[idx], Y[idx]
-        if rescale:
+        if rescale and ctx.adjustment()["k"]:
+            X, Y = adjust_new(ctx, X, Y, Z)
+        elif rescale:
             sc = ctx.scaling()
             X = (X - sc["centerX"]) / sc["scaleX"]
             Y = (Y - sc["centerY"]) / sc["scaleY"]

@@ -32,6 +32,8 @@
 #include "ppls_o2m.h"
 #include "ppls_permute.h"
 #include "ppls_scale.h"
+#include "ppls_adjust.h"
+#include "ppls_adjust_host.h"
 #include "ppls_cvstream.h"
 #include "ppls_stream.h"
 #include "ppls_varxprod.h"
@@ -200,6 +202,13 @@ struct ppls_ctx {
   std::vector<double> sc_center, sc_scale;
   double scale_ms[3] = {0, 0, 0};
   double scale_bytes[3] = {0, 0, 0};
+  // ppls_adjust_data / ppls_xprod_adjust: the covariate part of that transform,
+  // loaded = resident * scale + center + (z - zcenter) Gamma; adj_k = 0: not adjusted.  adj_gamma is
+  // adj_k x (p + q) row-major.  adj_ms: the last coefficient, apply, Schur and standardise pass (HIP events).
+  int adj_k = 0;
+  std::vector<double> adj_zcenter, adj_gamma;
+  std::vector<double> adj_ss;   // sum_a G_aj^2 per column of the last ppls_adjust_data (the explained sums of squares)
+  double adj_ms[4] = {0, 0, 0, 0};
   // streamed data (ppls_stream_*): S and the column means accumulated from row chunks, no rows
   // resident.  A chunk is staged in one of two fp64 device buffers (each [X rows | Y rows] in the
   // padded row layout, sized for the largest chunk seen); its device work runs on st_stream while
@@ -1376,6 +1385,10 @@ int alloc_data(ppls_ctx* c, int64_t n_local, int p, int q, int64_t n_total) {
   c->have_data = false;
   c->sc_center.clear();   // new data carry no transform (ppls_get_scaling: center 0, scale 1)
   c->sc_scale.clear();
+  c->adj_k = 0;           // ... and no covariate adjustment (ppls_get_adjustment: k = 0)
+  c->adj_zcenter.clear();
+  c->adj_gamma.clear();
+  c->adj_ss.clear();
   c->rb_kept = false;     // kept robust weights belonged to the rows that were here
   return PPLS_OK;
 }
@@ -4990,6 +5003,9 @@ int ppls_set_data_from(ppls_ctx* dst, ppls_ctx* src, const int64_t* rows, int64_
   dst->have_data = true;
   dst->sc_center = src->sc_center;   // the rows keep the transform they carry in src (ppls_scale_data)
   dst->sc_scale = src->sc_scale;
+  dst->adj_k = src->adj_k;           // ... and the covariate adjustment (ppls_adjust_data)
+  dst->adj_zcenter = src->adj_zcenter;
+  dst->adj_gamma = src->adj_gamma;
   if ((rc = compute_ssq(dst))) return rc;   // drops a stale S; collective when sharded (also with no rows)
   return check_finite_data(dst);
 }
@@ -6598,6 +6614,9 @@ int reweight_impl(ppls_ctx* dst, ppls_ctx* src, const int32_t* count, const doub
   dst->n_total = real ? src->n_total : (int64_t)f[2];   // real weights are relative to N
   dst->sc_center = src->sc_center;   // the rows keep the transform they carry in src
   dst->sc_scale = src->sc_scale;
+  dst->adj_k = src->adj_k;
+  dst->adj_zcenter = src->adj_zcenter;
+  dst->adj_gamma = src->adj_gamma;
   dst->mem_free_min = src->mem_free_min;
   dst->xp_ready = true;
   dst->xp_serial = ++g_xp_serial;
@@ -6874,6 +6893,9 @@ int ppls_xprod_permute(ppls_ctx* dst, ppls_ctx* src, const int64_t* perm) {
   dst->n_total = src->n_total;
   dst->sc_center = src->sc_center;   // the rows keep the transform they carry in src
   dst->sc_scale = src->sc_scale;
+  dst->adj_k = src->adj_k;
+  dst->adj_zcenter = src->adj_zcenter;
+  dst->adj_gamma = src->adj_gamma;
   dst->mem_free_min = src->mem_free_min;
   dst->xp_ready = true;
   dst->xp_serial = ++g_xp_serial;
@@ -7187,6 +7209,539 @@ int ppls_xprod_meta_stats(ppls_ctx* c, const double* W, const double* C, const d
     std::copy(pops[(size_t)j].SY.begin(), pops[(size_t)j].SY.end(), o + c->p);
     for (int e = 0; e < 4; ++e) o[(size_t)c->p + c->q + e] = pops[(size_t)j].G[e];
   }
+  return PPLS_OK;
+}
+
+}  // extern "C"
+
+// ============================================================================ covariate adjustment
+// ppls_adjust_data: the resident X, Y <- their least-squares residuals on the design [1 Z] over all
+// ranks' rows.  The host holds Z: it centres and unit-scales the columns, orthonormalises
+// them by two rounds of Cholesky-QR (one all-reduce of the k x k Gram each) and uploads Q; the device
+// forms G = Q'[X Y] in one read of the rows and subtracts Q G in place (ppls_adjust.hip).
+// ppls_xprod_adjust: the same adjustment for contexts that hold only S, as a Schur complement.
+namespace {
+
+// Sum over ranks of a small host vector (every rank calls; a no-op without other ranks).
+int allreduce_hostvec(ppls_ctx* c, std::vector<double>& v) {
+  if (!collective(c)) return PPLS_OK;
+  int rc;
+  CvScratch tmp;
+  double* d = nullptr;
+  if ((rc = tmp.get(c, &d, v.size()))) return rc;
+  HIPCHK(c, hipMemcpyAsync(d, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice, c->stream));
+  if ((rc = allreduce(c, d, v.size()))) return rc;
+  HIPCHK(c, hipMemcpyAsync(v.data(), d, sizeof(double) * v.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return PPLS_OK;
+}
+
+struct AdjustSides {
+  ScaleSide sd[2];
+  int L0, L;   // a row of G on the device: X's ldc values, then Y's
+  bool nt;
+};
+
+AdjustSides adjust_sides(ppls_ctx* c) {
+  AdjustSides s{{{c->X, c->ldx, c->p, 0, ppls_scale_plan(c->n_local, c->p, c->dtype, c->num_cus)},
+                 {c->Y, c->ldy, c->q, c->p, ppls_scale_plan(c->n_local, c->q, c->dtype, c->num_cus)}},
+                0, 0, false};
+  s.L0 = s.sd[0].pl.ldc;
+  s.L = s.L0 + s.sd[1].pl.ldc;
+  s.nt = c->nt_loads > 0 || (c->nt_loads < 0 && 8.0 * c->n_local * (double)(c->ldx + c->ldy) > 256.0 * (1 << 20));
+  return s;
+}
+
+// The n_local x k1 row-major host Q zero-padded to kt columns, on the device.
+int adjust_upload_q(ppls_ctx* c, CvScratch& tmp, const double* Q, int k1, int kt, double** Qd) {
+  int rc;
+  const int64_t n = c->n_local;
+  std::vector<double> pad((size_t)std::max<int64_t>(n, 1) * kt, 0.0);
+  for (int64_t i = 0; i < n; ++i)
+    for (int a = 0; a < k1; ++a) pad[(size_t)i * kt + a] = Q[(size_t)i * k1 + a];
+  if ((rc = tmp.get(c, Qd, pad.size()))) return rc;
+  HIPCHK(c, hipMemcpyAsync(*Qd, pad.data(), sizeof(double) * pad.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return PPLS_OK;
+}
+
+// The coefficient pass: Gd (device, kt rows of s.L doubles) = Q'[X Y], all-reduced; G (host) = its k1
+// rows over the p + q real columns, row-major.
+int adjust_coef_pass(ppls_ctx* c, const AdjustSides& s, CvScratch& tmp, const double* Qd, int k1, int kt, double* Gd,
+                     std::vector<double>& G) {
+  int rc;
+  const int P = c->p + c->q;
+  double *part = nullptr, *Gm = nullptr;
+  const size_t plen = (size_t)kt * std::max((size_t)s.sd[0].pl.nblocks * s.sd[0].pl.ldc, (size_t)s.sd[1].pl.nblocks * s.sd[1].pl.ldc);
+  if ((rc = tmp.get(c, &part, plen))) return rc;
+  if ((rc = tmp.get(c, &Gm, (size_t)kt * std::max(s.L0, s.L - s.L0)))) return rc;
+  HIPCHK(c, hipMemsetAsync(Gd, 0, sizeof(double) * kt * s.L, c->stream));   // a rank without rows contributes zeros
+  CvEvents ev;
+  HIPCHK(c, ev.begin(c->stream));
+  if (c->n_local > 0)
+    for (int m = 0; m < 2; ++m) {
+      const ScaleSide& sd = s.sd[m];
+      HIPCHK(c, ppls_launch_adjust_partials(sd.data, sd.ld, c->n_local, c->dtype, &sd.pl, Qd, kt, s.nt, part, c->stream));
+      HIPCHK(c, ppls_launch_adjust_reduce(part, &sd.pl, kt, Gm, c->stream));
+      // this side's kt x ldc block into its columns of the joint rows
+      HIPCHK(c, hipMemcpy2DAsync(Gd + (m ? s.L0 : 0), sizeof(double) * s.L, Gm, sizeof(double) * sd.pl.ldc,
+                                 sizeof(double) * sd.pl.ldc, (size_t)kt, hipMemcpyDeviceToDevice, c->stream));
+    }
+  HIPCHK(c, ev.end(c->stream));
+  if ((rc = allreduce(c, Gd, (size_t)kt * s.L))) return rc;
+  std::vector<double> h((size_t)kt * s.L);
+  HIPCHK(c, hipMemcpyAsync(h.data(), Gd, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->adj_ms[0] = ev.ms();
+  G.assign((size_t)k1 * P, 0.0);
+  for (int a = 0; a < k1; ++a) {
+    std::copy(h.begin() + (size_t)a * s.L, h.begin() + (size_t)a * s.L + c->p, G.begin() + (size_t)a * P);
+    std::copy(h.begin() + (size_t)a * s.L + s.L0, h.begin() + (size_t)a * s.L + s.L0 + c->q, G.begin() + (size_t)a * P + c->p);
+  }
+  return PPLS_OK;
+}
+
+int adjust_state_check(ppls_ctx* c) {
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NOT_WHILE_OPEN(c, "the data");
+  NEED_ROWS(c);
+  return PPLS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ppls_adjust_data(ppls_ctx* c, const double* Z, int k, int layout, int intercept) {
+  if (!c) return PPLS_E_ARG;
+  int rc;
+  if ((rc = adjust_state_check(c))) return rc;
+  if (c->adj_k > 0) return fail(c, PPLS_E_STATE, "the data are already adjusted for %d covariates: load them again first", c->adj_k);
+  for (size_t j = 0; j < c->sc_scale.size(); ++j)
+    if (c->sc_scale[j] != 1.0 || c->sc_center[j] != 0.0)
+      return fail(c, PPLS_E_STATE, "the data were scaled on the device: adjust before scaling (resid(), then scale())");
+  if (intercept != 0 && intercept != 1) return fail(c, PPLS_E_ARG, "intercept must be 0 or 1");
+  const int k1 = k + intercept, kt = ppls_adjust_kt(k1);
+  if (k < 1 || !kt) return fail(c, PPLS_E_ARG, "k = %d covariates%s: the design needs 1 .. %d columns", k,
+                                intercept ? " and an intercept" : "", PPLS_ADJ_KMAX);
+  if (layout != PPLS_LAYOUT_COLMAJOR && layout != PPLS_LAYOUT_ROWMAJOR) return fail(c, PPLS_E_ARG, "unknown layout %d", layout);
+  // n_total is the same on every rank, so this refusal needs no collective
+  if (c->n_total <= k1)
+    return fail(c, PPLS_E_ARG, "%lld rows (over all ranks) for a design of %d columns: no residual degrees of freedom",
+                (long long)c->n_total, k1);
+  HIPCHK(c, hipSetDevice(c->device));
+  const int64_t n = c->n_local;
+  const int p = c->p, q = c->q, P = p + q;
+  const double N = (double)c->n_total;
+
+  // this rank's rows of Z, row-major; a NULL or non-finite Z rides in the first all-reduce, so that
+  // every rank refuses alike
+  std::vector<double> A((size_t)std::max<int64_t>(n, 1) * k, 0.0), red((size_t)k + 1, 0.0);
+  if (n > 0 && !Z) {
+    red[(size_t)k] = 1.0;
+  } else {
+    for (int64_t i = 0; i < n; ++i)
+      for (int j = 0; j < k; ++j) {
+        const double z = layout == PPLS_LAYOUT_ROWMAJOR ? Z[(size_t)i * k + j] : Z[(size_t)j * n + i];
+        if (!std::isfinite(z)) red[(size_t)k] += 1.0;
+        A[(size_t)i * k + j] = z;
+      }
+    if (red[(size_t)k] == 0.0)
+      for (int64_t i = 0; i < n; ++i)
+        for (int j = 0; j < k; ++j) red[(size_t)j] += A[(size_t)i * k + j];
+  }
+  if ((rc = allreduce_hostvec(c, red))) return rc;
+  if (red[(size_t)k] > 0.0)
+    return fail(c, PPLS_E_ARG, "Z is NULL on a rank with rows, or holds NaN or Inf (%.0f such values or ranks): the data "
+                               "are unchanged", red[(size_t)k]);
+  std::vector<double> zc((size_t)k, 0.0);
+  if (intercept)
+    for (int j = 0; j < k; ++j) zc[(size_t)j] = red[(size_t)j] / N;
+  // the design T = [1 / sqrt(N) | Z - zc], n_local x k1 row-major.  The constant column goes through the
+  // Cholesky-QR rounds with the others: a centred column is orthogonal to it only up to rounding, and
+  // round 1 divides that remainder by the column's pivot
+  std::vector<double> Q((size_t)std::max<int64_t>(n, 1) * k1, 0.0);
+  for (int64_t i = 0; i < n; ++i) {
+    if (intercept) Q[(size_t)i * k1] = 1.0 / std::sqrt(N);
+    for (int j = 0; j < k; ++j) Q[(size_t)i * k1 + intercept + j] = A[(size_t)i * k + j] - zc[(size_t)j];
+  }
+
+  // round 1: the Gram of T, brought to unit diagonal (= the Gram of the unit-norm columns), and
+  // lm.fit's pivot rule on its Cholesky factor
+  std::vector<double> G1((size_t)k1 * k1), L1((size_t)k1 * k1), L2((size_t)k1 * k1), nrm((size_t)k1, 1.0);
+  ppls_adj_gram(Q.data(), n, k1, G1.data());
+  if ((rc = allreduce_hostvec(c, G1))) return rc;
+  for (int j = 0; j < k; ++j) {
+    const double cc = G1[(size_t)(intercept + j) * k1 + intercept + j], raw = cc + N * zc[(size_t)j] * zc[(size_t)j];
+    nrm[(size_t)(intercept + j)] = std::sqrt(cc);
+    if (!(std::sqrt(cc) > PPLS_ADJ_TOL * std::sqrt(raw)) || !std::isfinite(cc))
+      return fail(c, PPLS_E_ARG, "covariate column %d is %s (over all ranks): it is aliased and would be dropped by "
+                                 "lm(); the data are unchanged", j + 1, intercept ? "constant beside the intercept" : "zero");
+  }
+  for (int a = 0; a < k1; ++a)
+    for (int b = 0; b < k1; ++b)
+      G1[(size_t)a * k1 + b] = a == b ? 1.0 : G1[(size_t)a * k1 + b] / (nrm[(size_t)a] * nrm[(size_t)b]);
+  int piv = ppls_adj_chol(G1.data(), k1, PPLS_ADJ_TOL, L1.data());
+  if (piv)
+    return fail(c, PPLS_E_ARG, "covariate column %d is aliased: given the columns before it%s, at most %g of its norm is "
+                               "left (lm.fit's tol); the data are unchanged", piv - intercept,
+                intercept ? " and the intercept" : "", PPLS_ADJ_TOL);
+  for (int64_t i = 0; i < n; ++i)
+    for (int j = 0; j < k1; ++j) Q[(size_t)i * k1 + j] /= nrm[(size_t)j];
+  ppls_adj_solve_rows(Q.data(), n, k1, L1.data());
+  // round 2 (Cholesky-QR2): the Gram of Q1 is within u kappa^2 of I
+  ppls_adj_gram(Q.data(), n, k1, G1.data());
+  if ((rc = allreduce_hostvec(c, G1))) return rc;
+  if ((piv = ppls_adj_chol(G1.data(), k1, 0.0, L2.data())))
+    return fail(c, PPLS_E_ARG, "design column %d: the second Cholesky-QR round lost positive definiteness; the data are "
+                               "unchanged", piv);
+  ppls_adj_solve_rows(Q.data(), n, k1, L2.data());
+
+  const AdjustSides s = adjust_sides(c);
+  CvScratch tmp;
+  double *Qd = nullptr, *Gd = nullptr;
+  std::vector<double> G;
+  if ((rc = adjust_upload_q(c, tmp, Q.data(), k1, kt, &Qd))) return rc;
+  if ((rc = tmp.get(c, &Gd, (size_t)kt * s.L))) return rc;
+  c->adj_ms[0] = c->adj_ms[1] = 0.0;
+  if ((rc = adjust_coef_pass(c, s, tmp, Qd, k1, kt, Gd, G))) return rc;
+  for (size_t e = 0; e < G.size(); ++e)
+    if (!std::isfinite(G[e])) return fail(c, PPLS_E_NUMERIC, "the coefficients Q'[X Y] are not finite; the data are unchanged");
+
+  // from here the rows change
+  c->rb_kept = false;
+  c->em_active = false;
+  c->xp_active = false;
+  {
+    CvEvents ev;
+    HIPCHK(c, ev.begin(c->stream));
+    if (n > 0)
+      for (int m = 0; m < 2; ++m) {
+        const ScaleSide& sd = s.sd[m];
+        HIPCHK(c, ppls_launch_adjust_apply(sd.data, sd.ld, n, sd.cols, c->dtype, &sd.pl, Qd, Gd + (m ? s.L0 : 0), s.L, kt, s.nt,
+                                           c->stream));
+      }
+    HIPCHK(c, ev.end(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->adj_ms[1] = ev.ms();
+  }
+  // the record: T diag(1 / nrm) = Q L2' L1', so the fit Q G = T diag(1 / nrm) H with H = L1^-T L2^-T G:
+  // Gamma = diag(1 / nrm) H's covariate rows, and the constant's share H_0 / sqrt(N) is the column mean
+  std::vector<double> H = G;
+  ppls_adj_backsolve(L2.data(), k1, H.data(), P);
+  ppls_adj_backsolve(L1.data(), k1, H.data(), P);
+  c->adj_k = k;
+  c->adj_zcenter = zc;
+  c->adj_gamma.assign((size_t)k * P, 0.0);
+  for (int a = 0; a < k; ++a)
+    for (int j = 0; j < P; ++j) c->adj_gamma[(size_t)a * P + j] = H[(size_t)(intercept + a) * P + j] / nrm[(size_t)(intercept + a)];
+  c->sc_center.assign((size_t)P, 0.0);
+  c->sc_scale.assign((size_t)P, 1.0);
+  if (intercept)
+    for (int j = 0; j < P; ++j) c->sc_center[(size_t)j] = H[(size_t)j] / std::sqrt(N);
+  c->adj_ss.assign((size_t)P, 0.0);
+  for (int a = 0; a < k1; ++a)
+    for (int j = 0; j < P; ++j) c->adj_ss[(size_t)j] += G[(size_t)a * P + j] * G[(size_t)a * P + j];
+  // the context is what ppls_set_data of the residuals would have left (as after ppls_scale_data)
+  if ((rc = compute_ssq(c))) return rc;
+  return check_finite_data(c);
+}
+
+int ppls_get_adjustment(ppls_ctx* c, int* k, double* zcenter, double* Gamma) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  if (k) *k = c->adj_k;
+  if (zcenter) std::copy(c->adj_zcenter.begin(), c->adj_zcenter.end(), zcenter);
+  if (Gamma) std::copy(c->adj_gamma.begin(), c->adj_gamma.end(), Gamma);
+  return PPLS_OK;
+}
+
+int ppls_adjust_explained(ppls_ctx* c, double* ss) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data || c->adj_k < 1 || c->adj_ss.size() != (size_t)(c->p + c->q))
+    return fail(c, PPLS_E_STATE, "no ppls_adjust_data on these data");
+  if (ss) std::copy(c->adj_ss.begin(), c->adj_ss.end(), ss);
+  return PPLS_OK;
+}
+
+int ppls_adjust_coef(ppls_ctx* c, const double* Q, int k1, double* G) {
+  if (!c) return PPLS_E_ARG;
+  int rc;
+  if ((rc = adjust_state_check(c))) return rc;
+  const int kt = ppls_adjust_kt(k1);
+  if (!kt) return fail(c, PPLS_E_ARG, "k1 = %d outside [1, %d]", k1, PPLS_ADJ_KMAX);
+  if (!G || (c->n_local > 0 && !Q)) return fail(c, PPLS_E_ARG, "NULL argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  const AdjustSides s = adjust_sides(c);
+  CvScratch tmp;
+  double *Qd = nullptr, *Gd = nullptr;
+  std::vector<double> g;
+  if ((rc = adjust_upload_q(c, tmp, Q, k1, kt, &Qd))) return rc;
+  if ((rc = tmp.get(c, &Gd, (size_t)kt * s.L))) return rc;
+  if ((rc = adjust_coef_pass(c, s, tmp, Qd, k1, kt, Gd, g))) return rc;
+  std::copy(g.begin(), g.end(), G);
+  return PPLS_OK;
+}
+
+int ppls_adjust_info(ppls_ctx* c, int k1, int* kt, int64_t* plans) {
+  if (!c) return PPLS_E_ARG;
+  int rc;
+  if ((rc = adjust_state_check(c))) return rc;
+  const int t = ppls_adjust_kt(k1);
+  if (!t) return fail(c, PPLS_E_ARG, "k1 = %d outside [1, %d]", k1, PPLS_ADJ_KMAX);
+  if (kt) *kt = t;
+  if (plans) {
+    const AdjustSides s = adjust_sides(c);
+    for (int m = 0; m < 2; ++m) {
+      const PplsScalePlan& pl = s.sd[m].pl;
+      const int64_t v[5] = {pl.tx, pl.ty, pl.grid_x, pl.grid_y, pl.nblocks};
+      std::copy(v, v + 5, plans + 5 * m);
+    }
+  }
+  return PPLS_OK;
+}
+
+int ppls_adjust_timing(ppls_ctx* c, double* ms4) {
+  if (!c) return PPLS_E_ARG;
+  for (int k = 0; k < 4; ++k)
+    if (ms4) ms4[k] = c->adj_ms[k];
+  return PPLS_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// What ppls_xprod_adjust and ppls_xadjust_matrix share: from the k trailing rows of src (host copy Zr,
+// k x P_src: joint columns of src) F (PPLS_ADJ_KMAX x P_dst, zero where nothing is live), Gamma (k x
+// (p + q), src's units) and the Schur diagonal over dst's joint columns, by the kernel's own fma chain.
+struct SchurPlan {
+  std::vector<double> F, gamma, diag;
+};
+
+int schur_plan(ppls_ctx* e, const std::vector<double>& Zr, const std::vector<double>& sdiag, int P_src, int p, int ldx,
+               int q, int ldy_dst, int k, SchurPlan* out) {
+  const int P = ldx + ldy_dst, z0 = ldx + q;   // the covariates: src's joint columns z0 .. z0 + k - 1
+  std::vector<double> C((size_t)k * k), L((size_t)k * k), d((size_t)k);
+  for (int a = 0; a < k; ++a) {
+    d[(size_t)a] = std::sqrt(Zr[(size_t)a * P_src + z0 + a]);
+    if (!(d[(size_t)a] > 0.0) || !std::isfinite(d[(size_t)a]))
+      return fail(e, PPLS_E_ARG, "covariate column %d has sum of squares %g: S_zz is singular", a + 1,
+                  Zr[(size_t)a * P_src + z0 + a]);
+  }
+  for (int a = 0; a < k; ++a)
+    for (int b = 0; b < k; ++b) {
+      const double v = a >= b ? Zr[(size_t)a * P_src + z0 + b] : Zr[(size_t)b * P_src + z0 + a];   // the lower triangle
+      C[(size_t)a * k + b] = a == b ? 1.0 : v / (d[(size_t)a] * d[(size_t)b]);
+    }
+  const int piv = ppls_adj_chol(C.data(), k, PPLS_ADJ_TOL, L.data());
+  if (piv)
+    return fail(e, PPLS_E_ARG, "covariate column %d is aliased: given the columns before it at most %g of its norm is left "
+                               "(lm.fit's tol): S_zz is singular", piv, PPLS_ADJ_TOL);
+  // F' = Lc^-1 D^-1 S_zd over dst's live joint columns
+  std::vector<double> Ft((size_t)k * P, 0.0);
+  auto live = [&](int c) { return c < p || (c >= ldx && c < ldx + q); };
+  for (int a = 0; a < k; ++a)
+    for (int c = 0; c < P; ++c)
+      if (live(c)) Ft[(size_t)a * P + c] = Zr[(size_t)a * P_src + c] / d[(size_t)a];
+  ppls_adj_fwdsolve(L.data(), k, Ft.data(), P);
+  out->F.assign((size_t)PPLS_ADJ_KMAX * P, 0.0);
+  std::copy(Ft.begin(), Ft.end(), out->F.begin());
+  out->diag.assign((size_t)P, 0.0);
+  for (int c = 0; c < P; ++c)
+    if (live(c)) {
+      double v = sdiag[(size_t)c];
+      for (int a = 0; a < k; ++a) v = std::fma(-Ft[(size_t)a * P + c], Ft[(size_t)a * P + c], v);
+      out->diag[(size_t)c] = v;
+    }
+  // Gamma = S_zz^-1 S_zd = D^-1 Lc^-T F'
+  ppls_adj_backsolve(L.data(), k, Ft.data(), P);
+  out->gamma.assign((size_t)k * (p + q), 0.0);
+  for (int a = 0; a < k; ++a) {
+    for (int j = 0; j < p; ++j) out->gamma[(size_t)a * (p + q) + j] = Ft[(size_t)a * P + j] / d[(size_t)a];
+    for (int j = 0; j < q; ++j) out->gamma[(size_t)a * (p + q) + p + j] = Ft[(size_t)a * P + ldx + j] / d[(size_t)a];
+  }
+  return PPLS_OK;
+}
+
+// d (joint layout of dst, 1 where nothing is divided) from the Schur diagonal: sqrt(diag / denom).
+int schur_scale(ppls_ctx* e, const SchurPlan& pl, int p, int ldx, int q, double denom, std::vector<double>* d) {
+  d->assign(pl.diag.size(), 1.0);
+  for (int j = 0; j < p + q; ++j) {
+    const int c = j < p ? j : ldx + (j - p);
+    const double v = std::sqrt(pl.diag[(size_t)c] / denom);
+    if (!(v > 0.0) || !std::isfinite(v))
+      return fail(e, PPLS_E_ARG, "%c column %d has standard deviation %g after the adjustment: scale = 1 would fill it with "
+                                 "NaN or Inf", j < p ? 'X' : 'Y', (j < p ? j : j - p) + 1, v);
+    (*d)[(size_t)c] = v;
+  }
+  return PPLS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ppls_xprod_adjust(ppls_ctx* dst, ppls_ctx* src, int k, int scale) {
+  if (!dst || !src) return dst ? fail(dst, PPLS_E_ARG, "NULL source context") : PPLS_E_ARG;
+  if (dst == src) return fail(dst, PPLS_E_ARG, "source and destination are the same context");
+  if (dst->device != src->device)
+    return fail(dst, PPLS_E_ARG, "contexts on different devices (%d, %d)", dst->device, src->device);
+  if (!src->have_data) return fail(dst, PPLS_E_STATE, "the source context has no data");
+  if (src->st_state == 1) return fail(dst, PPLS_E_STATE, "the source's stream is open: call ppls_stream_end first");
+  if (dst->st_state == 1) return fail(dst, PPLS_E_STATE, "a stream is open on the destination");
+  if (src->st_state == 2 && src->st_nfolds > 0)
+    return fail(dst, PPLS_E_STATE, "the source was streamed with folds: per-fold adjustment is not provided");
+  if (k < 1 || k > PPLS_ADJ_KMAX || k >= src->q)
+    return fail(dst, PPLS_E_ARG, "k = %d covariates: needs 1 <= k <= %d and k < the source's %d Y columns", k, PPLS_ADJ_KMAX,
+                src->q);
+  if (scale != 0 && scale != 1) return fail(dst, PPLS_E_ARG, "scale must be 0 or 1");
+  if (scale && src->n_total < 2) return fail(dst, PPLS_E_ARG, "scale = 1 needs at least 2 rows");
+  HIPCHK(dst, hipSetDevice(src->device));
+  int rc;
+  // resident rows: S of all of them first, formed and kept (a collective of its own when sharded)
+  if ((rc = xprod_setup(src))) {
+    dst->err = src->err;
+    return rc;
+  }
+  if (!src->xp_ready || !src->xp_S) return fail(dst, PPLS_E_STATE, "the source holds no cross-products");
+  const int p = src->p, q = src->q - k, ldx = src->ldx, P_src = src->ldx + src->ldy;
+  const int ldy = ld_of(q, src->dtype, src->ldpad), P = ldx + ldy, z0 = ldx + q;
+  if (P > P_src) return fail(dst, PPLS_E_STATE, "the destination's layout (%d) exceeds the source's (%d)", P, P_src);
+  // host: the k trailing rows of S and its diagonal (S is the same on every rank: no collective below)
+  std::vector<double> Zr((size_t)k * P_src), sdiag;
+  HIPCHK(dst, hipStreamSynchronize(src->stream));
+  HIPCHK(dst, hipMemcpy(Zr.data(), src->xp_S + (size_t)z0 * P_src, sizeof(double) * Zr.size(), hipMemcpyDeviceToHost));
+  HIPCHK(dst, diag_to_host(src->xp_S, P_src, sdiag));
+  SchurPlan pl;
+  std::vector<double> d;
+  if ((rc = schur_plan(dst, Zr, sdiag, P_src, p, ldx, q, ldy, k, &pl))) return rc;
+  if (scale && (rc = schur_scale(dst, pl, p, ldx, q, (double)(src->n_total - 1), &d))) return rc;
+  CvScratch tmp;
+  double *Fd = nullptr, *dd = nullptr, *Snew = nullptr;
+  if ((rc = tmp.get(src, &Fd, pl.F.size())) || (scale && (rc = tmp.get(src, &dd, d.size())))) {
+    dst->err = src->err;
+    return rc;
+  }
+  const bool reuse = dst->have_data && dst->st_state == 2 && dst->st_nfolds == 0 && dst->xp_ready && dst->xp_S &&
+                     dst->p == p && dst->q == q && dst->ldx == ldx && dst->ldy == ldy;
+  if (!reuse && (rc = dalloc(dst, &Snew, (size_t)P * P))) return rc;
+  // the records, before dst's own are cleared (dst may be adjusted already; src's are read only)
+  std::vector<double> cen((size_t)(p + q), 0.0), scl((size_t)(p + q), 1.0), zc((size_t)k, 0.0);
+  for (int j = 0; j < p + q; ++j) {
+    if (!src->sc_center.empty()) {
+      cen[(size_t)j] = src->sc_center[(size_t)j];
+      scl[(size_t)j] = src->sc_scale[(size_t)j];
+    }
+    if (scale) scl[(size_t)j] *= d[(size_t)(j < p ? j : ldx + (j - p))];
+  }
+  if (!src->sc_center.empty())
+    for (int a = 0; a < k; ++a) zc[(size_t)a] = src->sc_center[(size_t)(p + q + a)];
+  // From here dst ends streamed on the adjusted S, or without data.
+  HIPCHK(dst, hipStreamSynchronize(dst->stream));
+  if (!reuse) {
+    dst->dtype = src->dtype;   // the paddings follow the storage type and the padding option (ld_of)
+    dst->ldpad = src->ldpad;
+    if ((rc = alloc_data(dst, 0, p, q, 0))) { dfree(Snew); return rc; }
+    xprod_free(dst);
+    if (dst->ldx != ldx || dst->ldy != ldy) {
+      dfree(Snew);
+      return fail(dst, PPLS_E_STATE, "adjust: paddings %d, %d differ from the planned %d, %d", dst->ldx, dst->ldy, ldx, ldy);
+    }
+    dst->xp_S = Snew;
+    dst->st_state = 2;
+    dst->st_center = dst->st_scale = 0;
+    dst->n_local = 0;
+  } else {
+    meta_xp_free(dst);
+  }
+  dst->st_rows = dst->st_chunks = 0;
+  dst->have_data = false;
+  dst->em_active = false;
+  dst->xp_active = false;
+  dst->xp_pending_gram = false;
+  hipError_t e = hipMemcpyAsync(Fd, pl.F.data(), sizeof(double) * pl.F.size(), hipMemcpyHostToDevice, src->stream);
+  if (e == hipSuccess && scale) e = hipMemcpyAsync(dd, d.data(), sizeof(double) * d.size(), hipMemcpyHostToDevice, src->stream);
+  CvEvents ev;
+  if (e == hipSuccess) e = ev.begin(src->stream);
+  if (e == hipSuccess) e = ppls_launch_adjust_schur(src->xp_S, P_src, dst->xp_S, p, ldx, q, ldy, Fd, k, src->stream);
+  if (e == hipSuccess) e = ev.end(src->stream);
+  CvEvents ev2;
+  if (e == hipSuccess) e = ev2.begin(src->stream);
+  if (e == hipSuccess && scale) e = ppls_launch_stream_standardise(dst->xp_S, p, ldx, q, ldy, dd, src->stream);
+  if (e == hipSuccess) e = ev2.end(src->stream);
+  std::vector<double> diag;
+  double s2[2];
+  if (e == hipSuccess) e = hipStreamSynchronize(src->stream);
+  if (e == hipSuccess) e = diag_to_host(dst->xp_S, P, diag);
+  if (e == hipSuccess) {
+    dst->adj_ms[2] = ev.ms();
+    dst->adj_ms[3] = scale ? ev2.ms() : 0.0;
+    diag_traces(dst, diag, s2);
+    e = hipMemcpy(dst->ssq, s2, sizeof s2, hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) return resample_drop(dst, fail(dst, PPLS_E_HIP, "adjust: the Schur pass: %s", hipGetErrorString(e)));
+  if ((rc = traces_finite(dst, s2))) return resample_drop(dst, rc);
+  dst->ssq_host[0] = s2[0];
+  dst->ssq_host[1] = s2[1];
+  dst->n_total = src->n_total;
+  dst->sc_center = cen;
+  dst->sc_scale = scl;
+  dst->adj_k = k;
+  dst->adj_zcenter = zc;
+  dst->adj_gamma = pl.gamma;
+  dst->adj_ss.clear();
+  dst->mem_free_min = src->mem_free_min;
+  dst->xp_ready = true;
+  dst->xp_serial = ++g_xp_serial;
+  dst->xp_explicit = true;
+  dst->have_data = true;
+  return PPLS_OK;
+}
+
+int ppls_xadjust_matrix(ppls_ctx* c, const double* S_src, int p, int ldx, int q_src, int ldy_src, int k, int ldy_dst,
+                        int scale, double* S_dst) {
+  if (!c) return PPLS_E_ARG;
+  if (!S_src || !S_dst) return fail(c, PPLS_E_ARG, "NULL argument");
+  const int q = q_src - k;
+  if (k < 1 || k > PPLS_ADJ_KMAX || q < 1) return fail(c, PPLS_E_ARG, "k = %d outside [1, min(%d, q_src - 1)]", k, PPLS_ADJ_KMAX);
+  auto shape_ok = [](int cx, int lx, int cy, int ly) {   // the joint layouts ppls_symtile.h takes
+    return cx >= 1 && cy >= 1 && cx <= lx && cy <= ly && lx % 2 == 0 && ly % 2 == 0 && (int64_t)lx + ly < (1 << 30);
+  };
+  if (!shape_ok(p, ldx, q_src, ldy_src) || !shape_ok(p, ldx, q, ldy_dst) || ldy_dst > ldy_src)
+    return fail(c, PPLS_E_ARG, "bad layout: p %d in %d, q %d in %d, %d in %d", p, ldx, q_src, ldy_src, q, ldy_dst);
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  const int P_src = ldx + ldy_src, P = ldx + ldy_dst, z0 = ldx + q;
+  std::vector<double> Zr(S_src + (size_t)z0 * P_src, S_src + (size_t)(z0 + k) * P_src), sdiag((size_t)P_src), d;
+  for (int j = 0; j < P_src; ++j) sdiag[(size_t)j] = S_src[(size_t)j * P_src + j];
+  SchurPlan pl;
+  if ((rc = schur_plan(c, Zr, sdiag, P_src, p, ldx, q, ldy_dst, k, &pl))) return rc;
+  if (scale && (rc = schur_scale(c, pl, p, ldx, q, 1.0, &d))) return rc;
+  // NaN around the output: entries the kernel must not leave (it writes all P x P) and slack behind it
+  CvScratch tmp;
+  double *Sd = nullptr, *Dd = nullptr, *Fd = nullptr, *dd = nullptr;
+  const size_t guard = 64;
+  if ((rc = tmp.get(c, &Sd, (size_t)P_src * P_src)) || (rc = tmp.get(c, &Dd, (size_t)P * P + 2 * guard)) ||
+      (rc = tmp.get(c, &Fd, pl.F.size())) || (scale && (rc = tmp.get(c, &dd, d.size()))))
+    return rc;
+  HIPCHK(c, hipMemcpyAsync(Sd, S_src, sizeof(double) * P_src * P_src, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(Dd, 0xFF, sizeof(double) * ((size_t)P * P + 2 * guard), c->stream));
+  HIPCHK(c, hipMemcpyAsync(Fd, pl.F.data(), sizeof(double) * pl.F.size(), hipMemcpyHostToDevice, c->stream));
+  if (scale) HIPCHK(c, hipMemcpyAsync(dd, d.data(), sizeof(double) * d.size(), hipMemcpyHostToDevice, c->stream));
+  CvEvents ev;
+  HIPCHK(c, ev.begin(c->stream));
+  HIPCHK(c, ppls_launch_adjust_schur(Sd, P_src, Dd + guard, p, ldx, q, ldy_dst, Fd, k, c->stream));
+  HIPCHK(c, ev.end(c->stream));
+  if (scale) HIPCHK(c, ppls_launch_stream_standardise(Dd + guard, p, ldx, q, ldy_dst, dd, c->stream));
+  std::vector<double> h((size_t)P * P + 2 * guard);
+  HIPCHK(c, hipMemcpyAsync(h.data(), Dd, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->adj_ms[2] = ev.ms();
+  for (size_t g = 0; g < guard; ++g)
+    if (!std::isnan(h[g]) || !std::isnan(h[guard + (size_t)P * P + g]))
+      return fail(c, PPLS_E_NUMERIC, "the Schur kernel wrote outside its P x P output");
+  std::copy(h.begin() + guard, h.begin() + guard + (size_t)P * P, S_dst);
   return PPLS_OK;
 }
 
