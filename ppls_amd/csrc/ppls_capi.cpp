@@ -344,6 +344,27 @@ void dfree(T*& p) {
   p = nullptr;
 }
 
+// A device buffer that is freed on every return path until a context takes it (release).
+struct DevGuard {
+  double* p = nullptr;
+  ~DevGuard() { dfree(p); }
+  double* release() {
+    double* r = p;
+    p = nullptr;
+    return r;
+  }
+};
+
+// A device buffer the context keeps across calls and only ever grows: *len elements, 0 after a failure.
+template <typename T>
+int grow(ppls_ctx* c, T** buf, int64_t* len, int64_t need) {
+  if (*len >= need) return PPLS_OK;
+  *len = 0;
+  const int rc = dalloc(c, buf, (size_t)need);
+  if (!rc) *len = need;
+  return rc;
+}
+
 // Row stride (elements) of the resident X or Y.  16-B rows for narrow data and for the fp64 rows of
 // the split sweep (p <= 2048: its DMA ring streams whole row ranges, alignment beyond 16 B is moot,
 // and C3's 16,000-B rows stay unpadded).  Rows the panel sweep reads (fp32 storage, wider fp64) are
@@ -1353,6 +1374,27 @@ int check_fit_data(ppls_ctx* c) {
   return PPLS_OK;
 }
 
+// The transform record: what the held values carry relative to what was loaded (ppls_get_scaling,
+// ppls_get_adjustment).  Every writer of the whole record goes through here.  adj_ss is
+// ppls_adjust_data's alone and describes its last call: a record from anywhere else has none.
+void record_set(ppls_ctx* c, const std::vector<double>& center, const std::vector<double>& scale, int k,
+                const std::vector<double>& zcenter, const std::vector<double>& gamma) {
+  c->sc_center = center;
+  c->sc_scale = scale;
+  c->adj_k = k;
+  c->adj_zcenter = zcenter;
+  c->adj_gamma = gamma;
+  c->adj_ss.clear();
+}
+
+// dst's rows or cross-products keep the transform they carry in src.
+void record_copy(ppls_ctx* dst, const ppls_ctx* src) {
+  record_set(dst, src->sc_center, src->sc_scale, src->adj_k, src->adj_zcenter, src->adj_gamma);
+}
+
+// ppls_get_scaling: center 0, scale 1; ppls_get_adjustment: k = 0.
+void record_clear(ppls_ctx* c) { record_set(c, {}, {}, 0, {}, {}); }
+
 int alloc_data(ppls_ctx* c, int64_t n_local, int p, int q, int64_t n_total) {
   int rc;
   c->em_active = false;
@@ -1383,13 +1425,114 @@ int alloc_data(ppls_ctx* c, int64_t n_local, int p, int q, int64_t n_total) {
   dfree(c->mu);
   c->part_groups = 0;
   c->have_data = false;
-  c->sc_center.clear();   // new data carry no transform (ppls_get_scaling: center 0, scale 1)
-  c->sc_scale.clear();
-  c->adj_k = 0;           // ... and no covariate adjustment (ppls_get_adjustment: k = 0)
-  c->adj_zcenter.clear();
-  c->adj_gamma.clear();
-  c->adj_ss.clear();
+  record_clear(c);        // new data carry no transform and no covariate adjustment
   c->rb_kept = false;     // kept robust weights belonged to the rows that were here
+  return PPLS_OK;
+}
+
+// ---- contexts derived from another context ---------------------------------------------
+// ppls_set_data_from, ppls_xprod_downdate, ppls_xprod_resample / _weighted, ppls_xprod_permute and
+// ppls_xprod_adjust fill dst from src; the last three leave dst streamed on a derived S with no rows.
+
+// What no pair of contexts may be: missing, one and the same, on two devices.
+int pair_check(ppls_ctx* dst, const ppls_ctx* src) {
+  if (!dst || !src) return dst ? fail(dst, PPLS_E_ARG, "NULL source context") : PPLS_E_ARG;
+  if (dst == src) return fail(dst, PPLS_E_ARG, "source and destination are the same context");
+  if (dst->device != src->device)
+    return fail(dst, PPLS_E_ARG, "contexts on different devices (%d, %d)", dst->device, src->device);
+  return PPLS_OK;
+}
+
+// c without data after an error past the point of no return: never a half-formed S, never an open stream.
+int drop_to_no_data(ppls_ctx* c, int rc) {
+  if (!c->st_state) c->st_state = 2;   // (xprod_free then releases the stream and clears have_data and any EM session)
+  xprod_free(c);
+  c->have_data = false;
+  return rc;
+}
+
+// Whether dst already holds streamed cross-products (no folds) of this shape: the call writes into its S.
+bool derived_reuse(const ppls_ctx* dst, int p, int q, int ldx, int ldy) {
+  return dst->have_data && dst->st_state == 2 && dst->st_nfolds == 0 && dst->xp_ready && dst->xp_S && dst->p == p &&
+         dst->q == q && dst->ldx == ldx && dst->ldy == ldy;
+}
+
+// The point of no return: dst's own pending work is waited for (an EM session may still read the S that is
+// about to be overwritten), then dst is a streamed context of this shape with no rows, no EM session and an S
+// that is not ready -- its own (reuse) or Snew, which it takes.  On any other return than PPLS_OK the
+// caller ends with drop_to_no_data; Snew stays the guard's.  what: the entry point, whose: the planned
+// paddings' origin, both for the messages.
+int derived_begin(ppls_ctx* dst, const char* what, const char* whose, int dtype, int ldpad, int p, int q, int ldx, int ldy,
+                  DevGuard& Snew, bool reuse) {
+  int rc = hipStreamSynchronize(dst->stream) == hipSuccess ? PPLS_OK : fail(dst, PPLS_E_HIP, "%s: dst's stream failed", what);
+  if (!rc && reuse) {
+    meta_xp_free(dst);
+  } else if (!rc) {
+    // (alloc_data / xprod_free do not know the buffers dst keeps across calls: they are dst's, not the data's)
+    dst->dtype = dtype;   // the paddings follow the storage type and the padding option (ld_of)
+    dst->ldpad = ldpad;
+    if (!(rc = alloc_data(dst, 0, p, q, 0))) {
+      xprod_free(dst);
+      if (dst->ldx != ldx || dst->ldy != ldy)
+        rc = fail(dst, PPLS_E_STATE, "%s: paddings %d, %d differ from %s %d, %d", what, dst->ldx, dst->ldy, whose, ldx, ldy);
+    }
+    if (!rc) {
+      dst->xp_S = Snew.release();
+      dst->st_state = 2;
+      dst->st_center = dst->st_scale = 0;
+      dst->n_local = 0;
+    }
+  }
+  dst->st_rows = dst->st_chunks = 0;
+  dst->have_data = false;
+  dst->em_active = false;
+  dst->xp_active = false;
+  dst->xp_pending_gram = false;
+  return rc;
+}
+
+// The close of a call that formed S: the context has data again, under a new serial number.
+void derived_publish(ppls_ctx* c, int64_t n_total, double mem_free_min) {
+  c->n_total = n_total;
+  c->mem_free_min = mem_free_min;
+  c->xp_ready = true;
+  c->xp_serial = ++g_xp_serial;
+  c->xp_explicit = true;   // given by the caller, like ppls_xprod_prepare's: kept until new data or release
+  c->have_data = true;
+}
+
+// The ranks of src agree on a derived call's allocations and arguments before anyone starts work, so that
+// they return together.  noun, alloc_what, bad_what: the messages' parts.
+struct AgreeSpec {
+  const char *noun, *alloc_what, *bad_what;
+  bool args_first;   // which refusal a rank reports when ranks failed in both ways
+  bool drop;         // a failed allocation leaves dst without data, and a rank that failed keeps its own message
+};
+
+// rc_alloc: this rank's allocations; bad: its verdict on its arguments, with the message bad_err; extra
+// (may be NULL): a value summed over the ranks beside the flags.  PPLS_OK: every rank goes on.
+int ranks_agree(ppls_ctx* dst, ppls_ctx* src, const AgreeSpec& sp, int rc_alloc, int bad, const std::string& bad_err,
+                double* extra) {
+  const bool coll = collective(src);
+  double f[3] = {rc_alloc ? 1.0 : 0.0, bad ? 1.0 : 0.0, extra ? *extra : 0.0};
+  int rc;
+  if (coll && (rc = agree(src, f, extra ? 3 : 2))) {
+    dst->err = src->err;
+    return rc;
+  }
+  if (extra) *extra = f[2];
+  for (int t = 0; t < 2; ++t) {
+    if ((t == 0) == sp.args_first) {
+      if (!(f[1] > 0.0)) continue;   // a refusal: dst holds what it held (buffers that grew are not its data)
+      if (bad) dst->err = bad_err;
+      return bad ? bad : fail(dst, PPLS_E_ARG, "%s: %d other rank(s) passed %s", sp.noun, (int)f[1], sp.bad_what);
+    }
+    if (!(f[0] > 0.0)) continue;
+    if (!rc_alloc || (coll && !sp.drop))
+      rc_alloc = fail(dst, PPLS_E_NOMEM, "%s: %d %srank(s) could not allocate %s", sp.noun, (int)f[0], sp.drop ? "other " : "",
+                      sp.alloc_what);
+    return sp.drop ? drop_to_no_data(dst, rc_alloc) : rc_alloc;
+  }
   return PPLS_OK;
 }
 
@@ -4975,13 +5118,10 @@ int cv_upload_coef(ppls_ctx* c, CvScratch& tmp, const double* M, int rowsM, int 
 extern "C" {
 
 int ppls_set_data_from(ppls_ctx* dst, ppls_ctx* src, const int64_t* rows, int64_t nrows, int64_t n_total) {
-  if (!dst || !src) return dst ? fail(dst, PPLS_E_ARG, "NULL source context") : PPLS_E_ARG;
-  if (dst == src) return fail(dst, PPLS_E_ARG, "source and destination are the same context");
+  int rc;
+  if ((rc = pair_check(dst, src))) return rc;
   if (!src->have_data) return fail(dst, PPLS_E_ARG, "the source context has no data");
   if (src->st_state == 2) return fail(dst, PPLS_E_STATE, PPLS_STREAMED_MSG);
-  if (dst->device != src->device)
-    return fail(dst, PPLS_E_ARG, "contexts on different devices (%d, %d)", dst->device, src->device);
-  int rc;
   if ((rc = cv_check_rows(dst, rows, nrows, src->n_local))) return rc;
   if (n_total > 0 && n_total < nrows) return fail(dst, PPLS_E_ARG, "n_total=%lld < %lld local rows", (long long)n_total, (long long)nrows);
   HIPCHK(dst, hipSetDevice(dst->device));
@@ -5001,26 +5141,19 @@ int ppls_set_data_from(ppls_ctx* dst, ppls_ctx* src, const int64_t* rows, int64_
   src->cv_ms[0] += ev.ms();
   src->cv_bytes[0] += cv_gather_bytes(src, nrows, dst->ldx, dst->ldy);
   dst->have_data = true;
-  dst->sc_center = src->sc_center;   // the rows keep the transform they carry in src (ppls_scale_data)
-  dst->sc_scale = src->sc_scale;
-  dst->adj_k = src->adj_k;           // ... and the covariate adjustment (ppls_adjust_data)
-  dst->adj_zcenter = src->adj_zcenter;
-  dst->adj_gamma = src->adj_gamma;
+  record_copy(dst, src);   // the rows keep the transform they carry in src (ppls_scale_data, ppls_adjust_data)
   if ((rc = compute_ssq(dst))) return rc;   // drops a stale S; collective when sharded (also with no rows)
   return check_finite_data(dst);
 }
 
 int ppls_xprod_downdate(ppls_ctx* dst, ppls_ctx* src, const int64_t* out_rows, int64_t n_out) {
-  if (!dst || !src) return dst ? fail(dst, PPLS_E_ARG, "NULL source context") : PPLS_E_ARG;
-  if (dst == src) return fail(dst, PPLS_E_ARG, "source and destination are the same context");
+  int rc;
+  if ((rc = pair_check(dst, src))) return rc;
   if (!src->have_data || !dst->have_data) return fail(dst, PPLS_E_STATE, "no data");
   if (src->st_state == 2 || dst->st_state == 2) return fail(dst, PPLS_E_STATE, PPLS_STREAMED_MSG);
-  if (dst->device != src->device)
-    return fail(dst, PPLS_E_ARG, "contexts on different devices (%d, %d)", dst->device, src->device);
   if (dst->p != src->p || dst->q != src->q || dst->ldx != src->ldx || dst->ldy != src->ldy || dst->dtype != src->dtype)
     return fail(dst, PPLS_E_ARG, "the contexts' data differ in shape, padding or storage type");
   HIPCHK(dst, hipSetDevice(src->device));
-  int rc;
   // S of all rows first (a collective of its own when sharded: every rank is here)
   if ((rc = xprod_setup(src))) {
     dst->err = src->err;
@@ -5035,6 +5168,7 @@ int ppls_xprod_downdate(ppls_ctx* dst, ppls_ctx* src, const int64_t* out_rows, i
   if (!bad && dst->n_local != src->n_local - n_out)
     bad = fail(dst, PPLS_E_ARG, "row counts: %lld resident - %lld held out != %lld training rows on this rank",
                (long long)src->n_local, (long long)n_out, (long long)dst->n_local);
+  const std::string bad_err = dst->err;
   if (bad && !coll) return bad;
   // every allocation of the call, then the ranks agree that all of them succeeded before anyone
   // enters the all-reduce of the held-out Gram (as xprod_setup does for S)
@@ -5046,7 +5180,8 @@ int ppls_xprod_downdate(ppls_ctx* dst, ppls_ctx* src, const int64_t* out_rows, i
   const size_t xb = (size_t)std::max<int64_t>(no, 1) * src->ldx * es, yb = (size_t)std::max<int64_t>(no, 1) * src->ldy * es;
   const GramShape g{P, src->p, src->ldx, src->q, nullptr, src->ldx, nullptr, src->ldy, src->ldy};
   xprod_free(dst);
-  int rc_alloc = dalloc(dst, &dst->xp_S, PP);
+  DevGuard Snew;   // dst's S once the call has succeeded
+  int rc_alloc = dalloc(dst, &Snew.p, PP);
   if (!rc_alloc) rc_alloc = tmp.get(src, &Gout, PP);
   if (!rc_alloc) rc_alloc = cv_upload_rows(src, tmp, out_rows, no, &d_rows);
   if (!rc_alloc) rc_alloc = tmp.get(src, &gX, (xb + 7) / 8 + 64);
@@ -5056,32 +5191,16 @@ int ppls_xprod_downdate(ppls_ctx* dst, ppls_ctx* src, const int64_t* out_rows, i
     rc_alloc = tmp.get(src, &part, (size_t)ppls_gram_part_doubles(P, gram_nsplit(src, g, no, 0)));
     if (!rc_alloc) rc_alloc = gram_queue(src, g, no, 0, &q);
   }
+  if (rc_alloc && !coll && dst->err.empty()) dst->err = src->err;
   double n_out_total = (double)no;
-  if (coll) {
-    double f[3] = {rc_alloc ? 1.0 : 0.0, bad ? 1.0 : 0.0, (double)no};
-    if ((rc = agree(src, f, 3))) { dfree(dst->xp_S); dst->err = src->err; return rc; }
-    if (f[0] > 0.0) {
-      dfree(dst->xp_S);
-      return fail(dst, PPLS_E_NOMEM, "downdate of S: %d rank(s) could not allocate S, the held-out rows or their Gram", (int)f[0]);
-    }
-    if (f[1] > 0.0) {
-      dfree(dst->xp_S);
-      return bad ? bad : fail(dst, PPLS_E_ARG, "downdate of S: %d other rank(s) passed bad held-out rows", (int)f[1]);
-    }
-    n_out_total = f[2];
-  } else if (rc_alloc) {
-    dfree(dst->xp_S);
-    if (dst->err.empty()) dst->err = src->err;
-    return rc_alloc;
-  }
+  const AgreeSpec sp{"downdate of S", "S, the held-out rows or their Gram", "bad held-out rows", false, false};
+  if ((rc = ranks_agree(dst, src, sp, rc_alloc, bad, bad_err, &n_out_total))) return rc;
   // the totals every rank shares: held out + training = all rows, and no more held out than kept
   // (beyond that S - S_out loses more than a direct Gram of the training rows: form S directly)
-  if (n_out_total != (double)(src->n_total - dst->n_total) || n_out_total > (double)dst->n_total) {
-    dfree(dst->xp_S);
+  if (n_out_total != (double)(src->n_total - dst->n_total) || n_out_total > (double)dst->n_total)
     return fail(dst, PPLS_E_ARG, "row counts over all ranks: %lld rows, %.0f held out, %lld training rows%s",
                 (long long)src->n_total, n_out_total, (long long)dst->n_total,
                 n_out_total > (double)dst->n_total ? " (more held out than kept: form S directly)" : "");
-  }
   hipError_t e = hipMemsetAsync((char*)gX + xb, 0, ((xb + 7) / 8 + 64) * 8 - xb, src->stream);
   if (e == hipSuccess) e = hipMemsetAsync((char*)gY + yb, 0, ((yb + 7) / 8 + 64) * 8 - yb, src->stream);
   CvEvents ev;
@@ -5089,7 +5208,7 @@ int ppls_xprod_downdate(ppls_ctx* dst, ppls_ctx* src, const int64_t* out_rows, i
   if (e == hipSuccess) e = cv_gather(src, d_rows, no, gX, gY, src->ldx, src->ldy, src->stream);
   if (e == hipSuccess) e = ev.end(src->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(src->stream);
-  if (e != hipSuccess) { dfree(dst->xp_S); return fail(dst, PPLS_E_HIP, "held-out gather: %s", hipGetErrorString(e)); }
+  if (e != hipSuccess) return fail(dst, PPLS_E_HIP, "held-out gather: %s", hipGetErrorString(e));
   const double gather_ms = ev.ms();
   src->cv_ms[0] += gather_ms;
   src->cv_bytes[0] += cv_gather_bytes(src, no, src->ldx, src->ldy);
@@ -5100,17 +5219,16 @@ int ppls_xprod_downdate(ppls_ctx* dst, ppls_ctx* src, const int64_t* out_rows, i
     const int oz_used = src->oz_used;   // src's record of how its own S was formed stays
     rc = gram_run_s(src, gs, no, Gout, nullptr, part);
     src->oz_used = oz_used;
-    if (rc) { dfree(dst->xp_S); dst->err = src->err; return rc; }
+    if (rc) { dst->err = src->err; return rc; }
   } else {
     HIPCHK(dst, hipMemsetAsync(Gout, 0, sizeof(double) * PP, src->stream));
   }
-  if ((rc = allreduce(src, Gout, PP))) { dfree(dst->xp_S); dst->err = src->err; return rc; }
-  e = ppls_launch_downdate(src->xp_S, Gout, dst->xp_S, (int64_t)PP, src->stream);
+  if ((rc = allreduce(src, Gout, PP))) { dst->err = src->err; return rc; }
+  e = ppls_launch_downdate(src->xp_S, Gout, Snew.p, (int64_t)PP, src->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(src->stream);
-  if (e != hipSuccess) { dfree(dst->xp_S); return fail(dst, PPLS_E_HIP, "downdate of S: %s", hipGetErrorString(e)); }
-  dst->xp_ready = true;
-  dst->xp_serial = ++g_xp_serial;
-  dst->xp_explicit = true;   // given by the caller, like ppls_xprod_prepare's: kept until new data or release
+  if (e != hipSuccess) return fail(dst, PPLS_E_HIP, "downdate of S: %s", hipGetErrorString(e));
+  dst->xp_S = Snew.release();
+  derived_publish(dst, dst->n_total, dst->mem_free_min);   // (the training rows stay as they are)
   src->cv_ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - gather_ms;
   return PPLS_OK;
 }
@@ -5941,12 +6059,8 @@ int stream_fold_order(ppls_ctx* c, int b, const int32_t* fold, int64_t n) {
   for (int k = 0; k < K; ++k) seg[(size_t)k + 1] += seg[(size_t)k];
   std::vector<int64_t> at(seg.begin(), seg.end() - 1), idx((size_t)n);
   for (int64_t i = 0; i < n; ++i) idx[(size_t)at[(size_t)fold[i]]++] = i;
-  if (c->st_idx_len[b] < n) {   // (st_done[b] was waited for: nothing reads the old list)
-    c->st_idx_len[b] = 0;
-    int rc = dalloc(c, &c->st_idx[b], (size_t)n);
-    if (rc) return stream_fail(c, rc);
-    c->st_idx_len[b] = n;
-  }
+  const int rc = grow(c, &c->st_idx[b], &c->st_idx_len[b], n);   // (st_done[b] was waited for: nothing reads the old list)
+  if (rc) return stream_fail(c, rc);
   STREAMCHK(c, hipMemcpy(c->st_idx[b], idx.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice));
   return PPLS_OK;
 }
@@ -5964,13 +6078,6 @@ int stream_fold_check(ppls_ctx* c, const int32_t* fold, bool labelled, int64_t n
   return PPLS_OK;
 }
 
-// Drop a stream that ppls_stream_end refuses: no data afterwards.
-int stream_refuse(ppls_ctx* c, int rc) {
-  xprod_free(c);   // (st_state != 0: releases the stream, clears have_data)
-  c->have_data = false;
-  return rc;
-}
-
 // ---- ppls_stream_end: what the plain and the fold stream share -------------------------------------
 // Sharded, every rank must reach every collective of the call.  A HIP error in this rank's own work
 // between the collectives therefore goes into a flag the ranks agree on (agree), so every rank
@@ -5981,7 +6088,7 @@ int stream_refuse(ppls_ctx* c, int rc) {
   do {                                                                                                              \
     hipError_t e_ = (call);                                                                                         \
     if (e_ != hipSuccess)                                                                                           \
-      return stream_refuse((c), fail((c), PPLS_E_HIP, "%s: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__)); \
+      return drop_to_no_data((c), fail((c), PPLS_E_HIP, "%s: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__)); \
   } while (0)
 
 // A HIP error of this rank's own steps after the collectives: its verdict, which the last collective shares.
@@ -6001,6 +6108,19 @@ void diag_traces(const ppls_ctx* c, const std::vector<double>& diag, double s2[2
   s2[0] = s2[1] = 0.0;
   for (int j = 0; j < c->p; ++j) s2[0] += diag[(size_t)j];
   for (int j = 0; j < c->q; ++j) s2[1] += diag[(size_t)c->ldx + j];
+}
+
+// ||X||^2, ||Y||^2 of a context from the S it holds (P x P, complete on this rank): on the device and the host.
+hipError_t derived_traces(ppls_ctx* c, int P) {
+  std::vector<double> diag;
+  double s2[2];
+  hipError_t e = diag_to_host(c->xp_S, P, diag);
+  if (e != hipSuccess) return e;
+  diag_traces(c, diag, s2);
+  if ((e = hipMemcpy(c->ssq, s2, sizeof s2, hipMemcpyHostToDevice)) != hipSuccess) return e;
+  c->ssq_host[0] = s2[0];
+  c->ssq_host[1] = s2[1];
+  return hipSuccess;
 }
 
 int traces_finite(ppls_ctx* c, const double s2[2]) {
@@ -6166,13 +6286,7 @@ int fold_select(ppls_ctx* c, int fold) {
   const int P = c->ldx + c->ldy;
   HIPCHK(c, ppls_launch_cvs_select(c->st_fS, c->st_nfolds, fold, (int64_t)P * P, c->xp_S, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::vector<double> diag;
-  HIPCHK(c, diag_to_host(c->xp_S, P, diag));
-  double s2[2];
-  diag_traces(c, diag, s2);
-  HIPCHK(c, hipMemcpy(c->ssq, s2, sizeof s2, hipMemcpyHostToDevice));
-  c->ssq_host[0] = s2[0];
-  c->ssq_host[1] = s2[1];
+  HIPCHK(c, derived_traces(c, P));
   int64_t N = 0;
   for (int k = 0; k < c->st_nfolds; ++k)
     if (k != fold) N += c->st_fN[(size_t)k];
@@ -6203,13 +6317,13 @@ int stream_end_merge(ppls_ctx* c, double* S, int K, double* mean_d, std::vector<
   if (!c->st_failed && hipMemcpy(mh.data(), mean_d, sizeof(double) * KP, hipMemcpyDeviceToHost) != hipSuccess)
     c->st_failed = true;
   if (!collective(c))
-    return c->st_failed ? stream_refuse(c, fail(c, PPLS_E_STATE, "the stream failed before ppls_stream_end")) : PPLS_OK;
+    return c->st_failed ? drop_to_no_data(c, fail(c, PPLS_E_STATE, "the stream failed before ppls_stream_end")) : PPLS_OK;
   // {failed, N_rk, N_rk m_rk for all k}: the global counts and means, and the agreement that nobody
   // failed, in one all-reduce
   const size_t nred = 1 + (size_t)K + KP;
   CvScratch tmp;
   double* red = nullptr;
-  if ((rc = tmp.get(c, &red, nred))) return stream_refuse(c, rc);
+  if ((rc = tmp.get(c, &red, nred))) return drop_to_no_data(c, rc);
   std::vector<double> h(nred, 0.0);
   h[0] = c->st_failed ? 1.0 : 0.0;
   for (int k = 0; k < K; ++k) {
@@ -6218,11 +6332,11 @@ int stream_end_merge(ppls_ctx* c, double* S, int K, double* mean_d, std::vector<
       h[1 + (size_t)K + (size_t)k * P + j] = c->st_failed ? 0.0 : Nk[(size_t)k] * mh[(size_t)k * P + j];
   }
   REFUSECHK(c, hipMemcpyAsync(red, h.data(), sizeof(double) * nred, hipMemcpyHostToDevice, c->stream));
-  if ((rc = allreduce(c, red, nred))) return stream_refuse(c, rc);
+  if ((rc = allreduce(c, red, nred))) return drop_to_no_data(c, rc);
   REFUSECHK(c, hipMemcpyAsync(h.data(), red, sizeof(double) * nred, hipMemcpyDeviceToHost, c->stream));
   REFUSECHK(c, hipStreamSynchronize(c->stream));
   if (h[0] > 0.0)
-    return stream_refuse(c, fail(c, PPLS_E_STATE, "the stream failed on %d rank(s) before ppls_stream_end", (int)h[0]));
+    return drop_to_no_data(c, fail(c, PPLS_E_STATE, "the stream failed on %d rank(s) before ppls_stream_end", (int)h[0]));
   // each rank's S_k is centred about its own mean: + N_rk (m_rk - m_k)(m_rk - m_k)', the merge with
   // no partials, state by state
   std::vector<double> d(KP, 0.0);
@@ -6245,10 +6359,10 @@ int stream_end_merge(ppls_ctx* c, double* S, int K, double* mean_d, std::vector<
   for (int k = 0; k < K; ++k) Nk[(size_t)k] = h[(size_t)1 + k];
   // nobody enters the all-reduce of the matrices alone (the pattern of xprod_setup)
   double bad = e == hipSuccess ? 0.0 : 1.0;
-  if ((rc = agree(c, &bad, 1))) return stream_refuse(c, rc);
+  if ((rc = agree(c, &bad, 1))) return drop_to_no_data(c, rc);
   if (bad > 0.0)
-    return stream_refuse(c, fail(c, PPLS_E_HIP, "the cross-rank merge of %s failed on %d rank(s)", what, (int)bad));
-  if ((rc = allreduce(c, S, (size_t)K * PP))) return stream_refuse(c, rc);
+    return drop_to_no_data(c, fail(c, PPLS_E_HIP, "the cross-rank merge of %s failed on %d rank(s)", what, (int)bad));
+  if ((rc = allreduce(c, S, (size_t)K * PP))) return drop_to_no_data(c, rc);
   REFUSECHK(c, hipStreamSynchronize(c->stream));
   return PPLS_OK;
 }
@@ -6362,7 +6476,7 @@ int ppls_stream_end(ppls_ctx* c) {
   if (!c) return PPLS_E_ARG;
   if (c->st_state != 1) return fail(c, PPLS_E_STATE, "no stream is open: call ppls_stream_begin first");
   HIPCHK(c, hipSetDevice(c->device));
-  // Every return from here drops the stream (stream_refuse) or leaves the context streamed.
+  // Every return from here drops the stream (drop_to_no_data) or leaves the context streamed.
   int rc;
   const int p = c->p, q = c->q, P = c->ldx + c->ldy;
   // wait for the pending chunk work; a failure (now or earlier) is agreed on below when sharded
@@ -6385,19 +6499,19 @@ int ppls_stream_end(ppls_ctx* c) {
   // the staging buffers and partials go back before the free memory is read: the smallest free HBM
   // over all ranks, as compute_ssq records it, beside the agreement on the steps above
   const int64_t rows = c->st_rows, chunks = c->st_chunks;
-  stream_release(c);   // (st_state = 0: stream_refuse below still clears S and have_data)
+  stream_release(c);   // (st_state = 0: drop_to_no_data below still clears S and have_data)
   size_t mfree = 0, mtot = 0;
   if (!local) local = end_hip(c, hipMemGetInfo(&mfree, &mtot), "hipMemGetInfo");
   c->mem_free_min = (double)mfree;
   if (collective(c)) {
     CvScratch tmp;
     double* slots_d = nullptr;
-    if ((rc = tmp.get(c, &slots_d, (size_t)c->nranks + 1))) return stream_refuse(c, rc);
+    if ((rc = tmp.get(c, &slots_d, (size_t)c->nranks + 1))) return drop_to_no_data(c, rc);
     std::vector<double> slots((size_t)c->nranks + 1, 0.0);   // {HIP failures, free HBM of rank 0, 1, ...}
     slots[0] = local == PPLS_OK || local == PPLS_E_ARG ? 0.0 : 1.0;
     slots[(size_t)c->rank + 1] = (double)mfree;
     REFUSECHK(c, hipMemcpy(slots_d, slots.data(), sizeof(double) * slots.size(), hipMemcpyHostToDevice));
-    if ((rc = allreduce(c, slots_d, slots.size()))) return stream_refuse(c, rc);
+    if ((rc = allreduce(c, slots_d, slots.size()))) return drop_to_no_data(c, rc);
     REFUSECHK(c, hipStreamSynchronize(c->stream));
     REFUSECHK(c, hipMemcpy(slots.data(), slots_d, sizeof(double) * slots.size(), hipMemcpyDeviceToHost));
     if (slots[0] > 0.0 && (local == PPLS_OK || local == PPLS_E_ARG))
@@ -6406,7 +6520,7 @@ int ppls_stream_end(ppls_ctx* c) {
       c->err = local_err;
     for (size_t k = 1; k < slots.size(); ++k) c->mem_free_min = std::min(c->mem_free_min, slots[k]);
   }
-  if (local) return stream_refuse(c, local);
+  if (local) return drop_to_no_data(c, local);
   c->ssq_host[0] = s2[0];
   c->ssq_host[1] = s2[1];
   c->sc_center = cen;
@@ -6416,13 +6530,9 @@ int ppls_stream_end(ppls_ctx* c) {
   c->st_chunks = chunks;
   c->st_state = 2;
   c->n_local = 0;
-  c->n_total = (int64_t)N;
-  c->xp_ready = true;
-  c->xp_serial = ++g_xp_serial;
-  c->xp_explicit = true;
   c->xp_active = false;
   c->em_active = false;
-  c->have_data = true;
+  derived_publish(c, (int64_t)N, c->mem_free_min);
   return PPLS_OK;
 }
 
@@ -6434,48 +6544,17 @@ int ppls_stream_end(ppls_ctx* c) {
 // of them, into a context that holds S_c and no rows -- the streamed state.
 namespace {
 
-// dst without data after an allocation or HIP error past the point of no return: never a half-formed S.
-int resample_drop(ppls_ctx* dst, int rc) {
-  if (!dst->st_state) dst->st_state = 2;   // (xprod_free then clears have_data and any EM session)
-  xprod_free(dst);
-  dst->have_data = false;
-  return rc;
-}
-
-// dst takes src's shape and S (a P x P buffer it owns from here) as a streamed context with no rows.
-int resample_adopt(ppls_ctx* dst, const ppls_ctx* src, double* S) {
-  int rc;
-  dst->dtype = src->dtype;   // the paddings follow the storage type and the padding option (ld_of)
-  dst->ldpad = src->ldpad;
-  if ((rc = alloc_data(dst, 0, src->p, src->q, 0))) { dfree(S); return rc; }
-  xprod_free(dst);
-  if (dst->ldx != src->ldx || dst->ldy != src->ldy) {
-    dfree(S);
-    return fail(dst, PPLS_E_STATE, "resample: paddings %d, %d differ from the source's %d, %d", dst->ldx, dst->ldy, src->ldx,
-                src->ldy);
-  }
-  dst->xp_S = S;
-  dst->st_state = 2;
-  dst->st_rows = dst->st_chunks = 0;
-  dst->st_center = dst->st_scale = 0;
-  dst->n_local = 0;
-  return PPLS_OK;
-}
-
 // ppls_xprod_resample (count; weight NULL, real false) and ppls_xprod_weighted (real: weight, or NULL for
 // src's kept device weights).  One lifecycle: the agreement across ranks, dst's reused S and partials.
 int reweight_impl(ppls_ctx* dst, ppls_ctx* src, const int32_t* count, const double* weight, bool real) {
-  if (!dst || !src) return dst ? fail(dst, PPLS_E_ARG, "NULL source context") : PPLS_E_ARG;
-  if (dst == src) return fail(dst, PPLS_E_ARG, "source and destination are the same context");
+  int rc;
+  if ((rc = pair_check(dst, src))) return rc;
   if (!src->have_data) return fail(dst, PPLS_E_STATE, "the source context has no data");
   if (src->st_state == 2) return fail(dst, PPLS_E_STATE, PPLS_STREAMED_MSG);
-  if (dst->device != src->device)
-    return fail(dst, PPLS_E_ARG, "contexts on different devices (%d, %d)", dst->device, src->device);
   const bool kept = real && !weight;   // src's device weights, no host round trip
   if (kept && !src->rb_kept)
     return fail(dst, PPLS_E_STATE, "NULL weights and the source keeps none: call ppls_robust_weights on it first");
   HIPCHK(dst, hipSetDevice(src->device));
-  int rc;
   const bool coll = collective(src);
   const int64_t n = src->n_local;
   const int P = src->ldx + src->ldy;
@@ -6509,68 +6588,28 @@ int reweight_impl(ppls_ctx* dst, ppls_ctx* src, const int32_t* count, const doub
   // every allocation of the call before the ranks agree (as xprod_setup does for S): a new S only when
   // dst does not already hold resampled (or plainly streamed) cross-products of this shape, the kept
   // counts and partials only when they have to grow, the Gram's queue on src (kept there per shape)
-  const bool reuse = dst->have_data && dst->st_state == 2 && dst->st_nfolds == 0 && dst->xp_ready && dst->xp_S &&
-                     dst->p == src->p && dst->q == src->q && dst->ldx == src->ldx && dst->ldy == src->ldy;
+  const bool reuse = derived_reuse(dst, src->p, src->q, src->ldx, src->ldy);
   const GramShape g = gram_shape(src, true, 0);
   const int64_t nrun = bad ? 0 : n;
-  double* Snew = nullptr;
-  int rc_alloc = reuse ? PPLS_OK : dalloc(dst, &Snew, PP);
+  DevGuard Snew;
+  int rc_alloc = reuse ? PPLS_OK : dalloc(dst, &Snew.p, PP);
   if (!rc_alloc && nrun > 0) {
-    const int64_t need = ppls_gram_part_doubles(P, gram_nsplit(src, g, nrun, 0));
-    if (dst->rs_part_len < need) {
-      dst->rs_part_len = 0;
-      if (!(rc_alloc = dalloc(dst, &dst->rs_part, (size_t)need))) dst->rs_part_len = need;
-    }
-    if (!rc_alloc && real && !kept && dst->rs_wt_len < nrun) {
-      dst->rs_wt_len = 0;
-      if (!(rc_alloc = dalloc(dst, &dst->rs_wt, (size_t)nrun))) dst->rs_wt_len = nrun;
-    }
-    if (!rc_alloc && !real && dst->rs_cnt_len < nrun) {
-      dst->rs_cnt_len = 0;
-      if (!(rc_alloc = dalloc(dst, &dst->rs_cnt, (size_t)nrun))) dst->rs_cnt_len = nrun;
-    }
+    rc_alloc = grow(dst, &dst->rs_part, &dst->rs_part_len, ppls_gram_part_doubles(P, gram_nsplit(src, g, nrun, 0)));
+    if (!rc_alloc && real && !kept) rc_alloc = grow(dst, &dst->rs_wt, &dst->rs_wt_len, nrun);
+    if (!rc_alloc && !real) rc_alloc = grow(dst, &dst->rs_cnt, &dst->rs_cnt_len, nrun);
     if (!rc_alloc) {
       int* q = nullptr;
       if ((rc_alloc = gram_queue(src, g, nrun, 0, &q))) dst->err = src->err;
     }
   }
-  double f[3] = {rc_alloc ? 1.0 : 0.0, bad ? 1.0 : 0.0, bad ? 0.0 : sum};
-  if (coll && (rc = agree(src, f, 3))) {
-    dfree(Snew);
-    dst->err = src->err;
-    return rc;
-  }
-  if (f[0] > 0.0) {
-    dfree(Snew);
-    if (!rc_alloc) rc_alloc = fail(dst, PPLS_E_NOMEM, "resampled S: %d other rank(s) could not allocate it", (int)f[0]);
-    return resample_drop(dst, rc_alloc);
-  }
-  if (f[1] > 0.0) {
-    dfree(Snew);
-    if (bad) dst->err = bad_err;
-    return bad ? bad : fail(dst, PPLS_E_ARG, "resampled S: %d other rank(s) passed bad %s", (int)f[1], real ? "weights" : "counts");
-  }
-  if (real ? !(f[2] > 0.0) : !(f[2] >= 1.0)) {
-    dfree(Snew);
+  if (bad) sum = 0.0;
+  const AgreeSpec sp{"resampled S", "it", real ? "bad weights" : "bad counts", false, true};
+  if ((rc = ranks_agree(dst, src, sp, rc_alloc, bad, bad_err, &sum))) return rc;
+  if (real ? !(sum > 0.0) : !(sum >= 1.0))
     return fail(dst, PPLS_E_ARG, real ? "the weights are all zero over all ranks" : "the counts sum to 0 over all ranks: a replicate needs rows");
-  }
-  // From here dst ends streamed on S_c, or without data.  Its own pending work first (an EM session may
-  // still read the S that is about to be overwritten); the Gram then runs on src's stream, behind
-  // whatever src has queued, and the sum over ranks goes through src's communicator.
-  int local = hipStreamSynchronize(dst->stream) == hipSuccess ? PPLS_OK : fail(dst, PPLS_E_HIP, "resample: dst's stream failed");
-  if (!reuse) {
-    // (alloc_data / xprod_free inside would not know the kept buffers: they are dst's, not the data's)
-    if (!local) local = resample_adopt(dst, src, Snew);
-    else dfree(Snew);
-    Snew = nullptr;
-  } else {
-    meta_xp_free(dst);
-    dst->st_rows = dst->st_chunks = 0;
-  }
-  dst->have_data = false;
-  dst->em_active = false;
-  dst->xp_active = false;
-  dst->xp_pending_gram = false;
+  // From here dst ends streamed on S_c, or without data.  The Gram runs on src's stream, behind whatever
+  // src has queued, and the sum over ranks goes through src's communicator.
+  int local = derived_begin(dst, "resample", "the source's", src->dtype, src->ldpad, src->p, src->q, src->ldx, src->ldy, Snew, reuse);
   if (!local && n > 0) {
     hipError_t e = hipSuccess;
     // (kept: src->rb_w as it stands)
@@ -6590,38 +6629,21 @@ int reweight_impl(ppls_ctx* dst, ppls_ctx* src, const int32_t* count, const doub
     double b = local ? 1.0 : 0.0;
     if ((rc = agree(src, &b, 1))) {
       dst->err = src->err;
-      return resample_drop(dst, rc);
+      return drop_to_no_data(dst, rc);
     }
     if (b > 0.0 && !local) local = fail(dst, PPLS_E_HIP, "resampled S failed on %d other rank(s)", (int)b);
   }
-  if (local) return resample_drop(dst, local);
+  if (local) return drop_to_no_data(dst, local);
   if ((rc = allreduce(src, dst->xp_S, PP))) {
     dst->err = src->err;
-    return resample_drop(dst, rc);
+    return drop_to_no_data(dst, rc);
   }
   // ||X||^2, ||Y||^2: the traces of S_c's diagonal blocks, in column order (as fold_select takes them)
-  std::vector<double> diag;
-  double s2[2];
   hipError_t e = hipStreamSynchronize(src->stream);
-  if (e == hipSuccess) e = diag_to_host(dst->xp_S, P, diag);
-  if (e == hipSuccess) {
-    diag_traces(dst, diag, s2);
-    e = hipMemcpy(dst->ssq, s2, sizeof s2, hipMemcpyHostToDevice);
-  }
-  if (e != hipSuccess) return resample_drop(dst, fail(dst, PPLS_E_HIP, "resample: traces of S: %s", hipGetErrorString(e)));
-  dst->ssq_host[0] = s2[0];
-  dst->ssq_host[1] = s2[1];
-  dst->n_total = real ? src->n_total : (int64_t)f[2];   // real weights are relative to N
-  dst->sc_center = src->sc_center;   // the rows keep the transform they carry in src
-  dst->sc_scale = src->sc_scale;
-  dst->adj_k = src->adj_k;
-  dst->adj_zcenter = src->adj_zcenter;
-  dst->adj_gamma = src->adj_gamma;
-  dst->mem_free_min = src->mem_free_min;
-  dst->xp_ready = true;
-  dst->xp_serial = ++g_xp_serial;
-  dst->xp_explicit = true;
-  dst->have_data = true;
+  if (e == hipSuccess) e = derived_traces(dst, P);
+  if (e != hipSuccess) return drop_to_no_data(dst, fail(dst, PPLS_E_HIP, "resample: traces of S: %s", hipGetErrorString(e)));
+  record_copy(dst, src);
+  derived_publish(dst, real ? src->n_total : (int64_t)sum, src->mem_free_min);   // real weights are relative to N
   return PPLS_OK;
 }
 
@@ -6760,14 +6782,11 @@ int ppls_xgram_permuted(ppls_ctx* c, int nsplit, const int64_t* perm, double* C,
 }
 
 int ppls_xprod_permute(ppls_ctx* dst, ppls_ctx* src, const int64_t* perm) {
-  if (!dst || !src) return dst ? fail(dst, PPLS_E_ARG, "NULL source context") : PPLS_E_ARG;
-  if (dst == src) return fail(dst, PPLS_E_ARG, "source and destination are the same context");
+  int rc;
+  if ((rc = pair_check(dst, src))) return rc;
   if (!src->have_data) return fail(dst, PPLS_E_STATE, "the source context has no data");
   if (src->st_state == 2) return fail(dst, PPLS_E_STATE, PPLS_STREAMED_MSG);
-  if (dst->device != src->device)
-    return fail(dst, PPLS_E_ARG, "contexts on different devices (%d, %d)", dst->device, src->device);
   HIPCHK(dst, hipSetDevice(src->device));
-  int rc;
   const bool coll = collective(src);
   const int64_t n = src->n_local;
   const int P = src->ldx + src->ldy;
@@ -6788,27 +6807,17 @@ int ppls_xprod_permute(ppls_ctx* dst, ppls_ctx* src, const int64_t* perm) {
   }
   // every allocation of the call before the ranks agree: a new S only when dst does not already hold
   // streamed cross-products of this shape; the index array, the block and the partials only to grow
-  const bool reuse = dst->have_data && dst->st_state == 2 && dst->st_nfolds == 0 && dst->xp_ready && dst->xp_S &&
-                     dst->p == src->p && dst->q == src->q && dst->ldx == src->ldx && dst->ldy == src->ldy;
+  const bool reuse = derived_reuse(dst, src->p, src->q, src->ldx, src->ldy);
   // (dst's diagonal blocks are already src's when its S is the one the last permute left, of this very S of src)
   const bool keep_diag = reuse && dst->pm_self_serial == dst->xp_serial && dst->pm_src_serial == src->xp_serial;
   const int64_t nrun = bad ? 0 : n;
   const PermPlan pl = perm_plan(src, nrun, 0);
-  double* Snew = nullptr;
-  int rc_alloc = reuse ? PPLS_OK : dalloc(dst, &Snew, PP);
-  if (!rc_alloc && dst->pm_blk_len < (int64_t)BL) {
-    dst->pm_blk_len = 0;
-    if (!(rc_alloc = dalloc(dst, &dst->pm_blk, BL))) dst->pm_blk_len = (int64_t)BL;
-  }
+  DevGuard Snew;
+  int rc_alloc = reuse ? PPLS_OK : dalloc(dst, &Snew.p, PP);
+  if (!rc_alloc) rc_alloc = grow(dst, &dst->pm_blk, &dst->pm_blk_len, (int64_t)BL);
   if (!rc_alloc && nrun > 0) {
-    if (dst->rs_part_len < pl.part) {
-      dst->rs_part_len = 0;
-      if (!(rc_alloc = dalloc(dst, &dst->rs_part, (size_t)pl.part))) dst->rs_part_len = pl.part;
-    }
-    if (!rc_alloc && dst->pm_idx_len < pl.ints) {
-      dst->pm_idx_len = 0;
-      if (!(rc_alloc = dalloc(dst, &dst->pm_idx, (size_t)pl.ints))) dst->pm_idx_len = pl.ints;
-    }
+    rc_alloc = grow(dst, &dst->rs_part, &dst->rs_part_len, pl.part);
+    if (!rc_alloc) rc_alloc = grow(dst, &dst->pm_idx, &dst->pm_idx_len, pl.ints);
     if (!rc_alloc) {
       try {
         dst->pm_host.resize((size_t)pl.ints);
@@ -6817,38 +6826,11 @@ int ppls_xprod_permute(ppls_ctx* dst, ppls_ctx* src, const int64_t* perm) {
       }
     }
   }
-  double f[2] = {rc_alloc ? 1.0 : 0.0, bad ? 1.0 : 0.0};
-  if (coll && (rc = agree(src, f, 2))) {
-    dfree(Snew);
-    dst->err = src->err;
-    return rc;
-  }
-  if (f[1] > 0.0) {   // a refusal: dst holds what it held (buffers that grew above are not its data)
-    dfree(Snew);
-    if (bad) dst->err = bad_err;
-    return bad ? bad : fail(dst, PPLS_E_ARG, "permuted S: %d other rank(s) passed a bad permutation", (int)f[1]);
-  }
-  if (f[0] > 0.0) {
-    dfree(Snew);
-    if (!rc_alloc) rc_alloc = fail(dst, PPLS_E_NOMEM, "permuted S: %d other rank(s) could not allocate it", (int)f[0]);
-    return resample_drop(dst, rc_alloc);
-  }
-  // From here dst ends streamed on S_pi, or without data.  Its own pending work first (an EM session may
-  // still read the S that is about to be overwritten); everything else runs on src's stream, behind
+  const AgreeSpec sp{"permuted S", "it", "a bad permutation", true, true};
+  if ((rc = ranks_agree(dst, src, sp, rc_alloc, bad, bad_err, nullptr))) return rc;
+  // From here dst ends streamed on S_pi, or without data.  Everything runs on src's stream, behind
   // whatever src has queued, and the sum over ranks goes through src's communicator.
-  int local = hipStreamSynchronize(dst->stream) == hipSuccess ? PPLS_OK : fail(dst, PPLS_E_HIP, "permute: dst's stream failed");
-  if (!reuse) {
-    if (!local) local = resample_adopt(dst, src, Snew);
-    else dfree(Snew);
-    Snew = nullptr;
-  } else {
-    meta_xp_free(dst);
-    dst->st_rows = dst->st_chunks = 0;
-  }
-  dst->have_data = false;
-  dst->em_active = false;
-  dst->xp_active = false;
-  dst->xp_pending_gram = false;
+  int local = derived_begin(dst, "permute", "the source's", src->dtype, src->ldpad, src->p, src->q, src->ldx, src->ldy, Snew, reuse);
   dst->pm_self_serial = 0;
   if (!local && !keep_diag &&
       hipMemcpyAsync(dst->xp_S, src->xp_S, sizeof(double) * PP, hipMemcpyDeviceToDevice, src->stream) != hipSuccess)
@@ -6874,35 +6856,26 @@ int ppls_xprod_permute(ppls_ctx* dst, ppls_ctx* src, const int64_t* perm) {
     double b = local ? 1.0 : 0.0;
     if ((rc = agree(src, &b, 1))) {
       dst->err = src->err;
-      return resample_drop(dst, rc);
+      return drop_to_no_data(dst, rc);
     }
     if (b > 0.0 && !local) local = fail(dst, PPLS_E_HIP, "permuted S failed on %d other rank(s)", (int)b);
   }
-  if (local) return resample_drop(dst, local);
+  if (local) return drop_to_no_data(dst, local);
   if ((rc = allreduce(src, dst->pm_blk, BL))) {   // the ldx x ldy block only: the diagonal blocks are global already
     dst->err = src->err;
-    return resample_drop(dst, rc);
+    return drop_to_no_data(dst, rc);
   }
   hipError_t e = ppls_launch_xperm_scatter(dst->pm_blk, src->ldx, src->ldy, dst->xp_S, src->stream);
   // ||X||^2, ||Y||^2 are src's: a permutation of rows changes neither
   if (e == hipSuccess) e = hipMemcpyAsync(dst->ssq, src->ssq, 2 * sizeof(double), hipMemcpyDeviceToDevice, src->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(src->stream);
-  if (e != hipSuccess) return resample_drop(dst, fail(dst, PPLS_E_HIP, "permute: writing S: %s", hipGetErrorString(e)));
+  if (e != hipSuccess) return drop_to_no_data(dst, fail(dst, PPLS_E_HIP, "permute: writing S: %s", hipGetErrorString(e)));
   dst->ssq_host[0] = src->ssq_host[0];
   dst->ssq_host[1] = src->ssq_host[1];
-  dst->n_total = src->n_total;
-  dst->sc_center = src->sc_center;   // the rows keep the transform they carry in src
-  dst->sc_scale = src->sc_scale;
-  dst->adj_k = src->adj_k;
-  dst->adj_zcenter = src->adj_zcenter;
-  dst->adj_gamma = src->adj_gamma;
-  dst->mem_free_min = src->mem_free_min;
-  dst->xp_ready = true;
-  dst->xp_serial = ++g_xp_serial;
+  record_copy(dst, src);
+  derived_publish(dst, src->n_total, src->mem_free_min);
   dst->pm_self_serial = dst->xp_serial;
   dst->pm_src_serial = src->xp_serial;
-  dst->xp_explicit = true;
-  dst->have_data = true;
   dst->pm_ms[3] = ms_since(t_call);
   return PPLS_OK;
 }
@@ -7583,10 +7556,8 @@ int schur_scale(ppls_ctx* e, const SchurPlan& pl, int p, int ldx, int q, double 
 extern "C" {
 
 int ppls_xprod_adjust(ppls_ctx* dst, ppls_ctx* src, int k, int scale) {
-  if (!dst || !src) return dst ? fail(dst, PPLS_E_ARG, "NULL source context") : PPLS_E_ARG;
-  if (dst == src) return fail(dst, PPLS_E_ARG, "source and destination are the same context");
-  if (dst->device != src->device)
-    return fail(dst, PPLS_E_ARG, "contexts on different devices (%d, %d)", dst->device, src->device);
+  int rc;
+  if ((rc = pair_check(dst, src))) return rc;
   if (!src->have_data) return fail(dst, PPLS_E_STATE, "the source context has no data");
   if (src->st_state == 1) return fail(dst, PPLS_E_STATE, "the source's stream is open: call ppls_stream_end first");
   if (dst->st_state == 1) return fail(dst, PPLS_E_STATE, "a stream is open on the destination");
@@ -7598,7 +7569,6 @@ int ppls_xprod_adjust(ppls_ctx* dst, ppls_ctx* src, int k, int scale) {
   if (scale != 0 && scale != 1) return fail(dst, PPLS_E_ARG, "scale must be 0 or 1");
   if (scale && src->n_total < 2) return fail(dst, PPLS_E_ARG, "scale = 1 needs at least 2 rows");
   HIPCHK(dst, hipSetDevice(src->device));
-  int rc;
   // resident rows: S of all of them first, formed and kept (a collective of its own when sharded)
   if ((rc = xprod_setup(src))) {
     dst->err = src->err;
@@ -7618,14 +7588,14 @@ int ppls_xprod_adjust(ppls_ctx* dst, ppls_ctx* src, int k, int scale) {
   if ((rc = schur_plan(dst, Zr, sdiag, P_src, p, ldx, q, ldy, k, &pl))) return rc;
   if (scale && (rc = schur_scale(dst, pl, p, ldx, q, (double)(src->n_total - 1), &d))) return rc;
   CvScratch tmp;
-  double *Fd = nullptr, *dd = nullptr, *Snew = nullptr;
+  double *Fd = nullptr, *dd = nullptr;
+  DevGuard Snew;
   if ((rc = tmp.get(src, &Fd, pl.F.size())) || (scale && (rc = tmp.get(src, &dd, d.size())))) {
     dst->err = src->err;
     return rc;
   }
-  const bool reuse = dst->have_data && dst->st_state == 2 && dst->st_nfolds == 0 && dst->xp_ready && dst->xp_S &&
-                     dst->p == p && dst->q == q && dst->ldx == ldx && dst->ldy == ldy;
-  if (!reuse && (rc = dalloc(dst, &Snew, (size_t)P * P))) return rc;
+  const bool reuse = derived_reuse(dst, p, q, ldx, ldy);
+  if (!reuse && (rc = dalloc(dst, &Snew.p, (size_t)P * P))) return rc;
   // the records, before dst's own are cleared (dst may be adjusted already; src's are read only)
   std::vector<double> cen((size_t)(p + q), 0.0), scl((size_t)(p + q), 1.0), zc((size_t)k, 0.0);
   for (int j = 0; j < p + q; ++j) {
@@ -7638,28 +7608,8 @@ int ppls_xprod_adjust(ppls_ctx* dst, ppls_ctx* src, int k, int scale) {
   if (!src->sc_center.empty())
     for (int a = 0; a < k; ++a) zc[(size_t)a] = src->sc_center[(size_t)(p + q + a)];
   // From here dst ends streamed on the adjusted S, or without data.
-  HIPCHK(dst, hipStreamSynchronize(dst->stream));
-  if (!reuse) {
-    dst->dtype = src->dtype;   // the paddings follow the storage type and the padding option (ld_of)
-    dst->ldpad = src->ldpad;
-    if ((rc = alloc_data(dst, 0, p, q, 0))) { dfree(Snew); return rc; }
-    xprod_free(dst);
-    if (dst->ldx != ldx || dst->ldy != ldy) {
-      dfree(Snew);
-      return fail(dst, PPLS_E_STATE, "adjust: paddings %d, %d differ from the planned %d, %d", dst->ldx, dst->ldy, ldx, ldy);
-    }
-    dst->xp_S = Snew;
-    dst->st_state = 2;
-    dst->st_center = dst->st_scale = 0;
-    dst->n_local = 0;
-  } else {
-    meta_xp_free(dst);
-  }
-  dst->st_rows = dst->st_chunks = 0;
-  dst->have_data = false;
-  dst->em_active = false;
-  dst->xp_active = false;
-  dst->xp_pending_gram = false;
+  if ((rc = derived_begin(dst, "adjust", "the planned", src->dtype, src->ldpad, p, q, ldx, ldy, Snew, reuse)))
+    return drop_to_no_data(dst, rc);
   hipError_t e = hipMemcpyAsync(Fd, pl.F.data(), sizeof(double) * pl.F.size(), hipMemcpyHostToDevice, src->stream);
   if (e == hipSuccess && scale) e = hipMemcpyAsync(dd, d.data(), sizeof(double) * d.size(), hipMemcpyHostToDevice, src->stream);
   CvEvents ev;
@@ -7670,32 +7620,16 @@ int ppls_xprod_adjust(ppls_ctx* dst, ppls_ctx* src, int k, int scale) {
   if (e == hipSuccess) e = ev2.begin(src->stream);
   if (e == hipSuccess && scale) e = ppls_launch_stream_standardise(dst->xp_S, p, ldx, q, ldy, dd, src->stream);
   if (e == hipSuccess) e = ev2.end(src->stream);
-  std::vector<double> diag;
-  double s2[2];
   if (e == hipSuccess) e = hipStreamSynchronize(src->stream);
-  if (e == hipSuccess) e = diag_to_host(dst->xp_S, P, diag);
   if (e == hipSuccess) {
     dst->adj_ms[2] = ev.ms();
     dst->adj_ms[3] = scale ? ev2.ms() : 0.0;
-    diag_traces(dst, diag, s2);
-    e = hipMemcpy(dst->ssq, s2, sizeof s2, hipMemcpyHostToDevice);
+    e = derived_traces(dst, P);
   }
-  if (e != hipSuccess) return resample_drop(dst, fail(dst, PPLS_E_HIP, "adjust: the Schur pass: %s", hipGetErrorString(e)));
-  if ((rc = traces_finite(dst, s2))) return resample_drop(dst, rc);
-  dst->ssq_host[0] = s2[0];
-  dst->ssq_host[1] = s2[1];
-  dst->n_total = src->n_total;
-  dst->sc_center = cen;
-  dst->sc_scale = scl;
-  dst->adj_k = k;
-  dst->adj_zcenter = zc;
-  dst->adj_gamma = pl.gamma;
-  dst->adj_ss.clear();
-  dst->mem_free_min = src->mem_free_min;
-  dst->xp_ready = true;
-  dst->xp_serial = ++g_xp_serial;
-  dst->xp_explicit = true;
-  dst->have_data = true;
+  if (e != hipSuccess) return drop_to_no_data(dst, fail(dst, PPLS_E_HIP, "adjust: the Schur pass: %s", hipGetErrorString(e)));
+  if ((rc = traces_finite(dst, dst->ssq_host))) return drop_to_no_data(dst, rc);
+  record_set(dst, cen, scl, k, zc, pl.gamma);
+  derived_publish(dst, src->n_total, src->mem_free_min);
   return PPLS_OK;
 }
 

@@ -636,6 +636,56 @@ def test_xprod_adjust_from_resident_source_and_refusals():
         assert ei.value.code == E_ARG
 
 
+def test_derivations_chain_on_one_destination():
+    """One destination through every call that leaves a derived S, adopting a new S where the
+    shape changes and reusing its own where it does not: after each call it equals, bit for bit, a fresh
+    context given that call alone, and an EM session opened before the call is over."""
+    from ppls_amd import PplsError
+    n, p, q, k = 300, 13, 11, 2
+    X, Y, Z = _data(n, p, q, k, seed=5)
+    rng = np.random.default_rng(9)
+    count = rng.multinomial(n, np.full(n, 1.0 / n)).astype(np.int32)
+    weight = rng.uniform(0.2, 2.0, n)
+    perm1, perm2 = rng.permutation(n), rng.permutation(n)
+    th0 = {qq: _theta(make_problem(n, p, qq, 2, seed=4)[2]) for qq in (q, q + k)}
+    steps = [
+        ("resample", q + k, lambda c, s: c.xprod_resample(s, count)),
+        ("permute", q + k, lambda c, s: c.xprod_permute(s, perm1)),
+        ("adjust", q, lambda c, s: c.xprod_adjust(s, k, True)),           # q changes: a new S on a streamed context
+        ("weighted", q + k, lambda c, s: c.xprod_weighted(s, weight)),    # ... and back
+        ("permute again", q + k, lambda c, s: c.xprod_permute(s, perm2)),
+        ("adjust again", q, lambda c, s: c.xprod_adjust(s, k, False)),
+        ("adjust, reusing S", q, lambda c, s: c.xprod_adjust(s, k, True)),
+    ]
+
+    def state(c):
+        S, ldx = c.xprod_matrix(padded=True)
+        return dict(S=S, ldx=ldx, ssq=c.ssq(), n_total=c.n_total, shape=(c.p, c.q), stream=c.stream_info(),
+                    scaling=c.scaling(), adjustment=c.adjustment())
+
+    def same(a, b):
+        if isinstance(a, dict):
+            return a.keys() == b.keys() and all(same(a[key], b[key]) for key in a)
+        return np.array_equal(a, b) if isinstance(a, np.ndarray) else a == b
+
+    with _ctx() as src, _ctx() as work:
+        src.set_data(X, np.hstack([Y, Z]))
+        for name, q_after, call in steps:
+            if work.streamed:
+                work.em_begin(th0[work.q])
+                work.em_iterate(1)
+            call(work, src)
+            with pytest.raises(PplsError) as ei:
+                work.em_iterate(1)
+            assert ei.value.code == E_STATE, name
+            with _ctx() as fresh:
+                call(fresh, src)
+                got, want = state(work), state(fresh)
+            assert got["shape"] == (p, q_after) and got["stream"]["state"] == "streamed", name
+            for key in want:
+                assert same(got[key], want[key]), f"{name}: {key} differs from a fresh context's"
+
+
 def test_stream_data_with_covariates():
     from ppls_amd import PPLS_simult, stream_data
     n, p, q, k = 130, 9, 6, 2
