@@ -737,6 +737,90 @@ int ppls_robust_get(ppls_ctx* ctx, double* w, double* d2);
  * streamed, NULL weight with nothing kept.  After such a refusal dst holds what it held before. */
 int ppls_xprod_weighted(ppls_ctx* dst, ppls_ctx* src, const double* weight /* host, src's n_local, or NULL */);
 
+/* ---- PO2PLS: X- and Y-specific components, fitted from the cross-products ----------
+ * The reference's wider data model (simulC, Package/PPLS/src/loglC.cpp:268-315):
+ *   x = W t + Wo to + e,  y = C u + Co uo + f,  u = B t + h,
+ * Wo its P_Yosc (structured variation only X has), Co its P_Xosc.  Sizes: r >= 1, rx, ry >= 0,
+ * r + rx <= min(16, p), r + ry <= min(16, q).  Every sigma is a standard deviation.  The latent
+ * vector is ordered z = (t, to | u, uo), k = 2 r + rx + ry.  Loadings need not be orthonormal. */
+typedef struct {
+  double* W;     /* p x r column-major */
+  double* Wo;    /* p x rx (unused when rx = 0) */
+  double* C;     /* q x r */
+  double* Co;    /* q x ry (unused when ry = 0) */
+  double* B;     /* r: diag(B) */
+  double* sigT;  /* r */
+  double* sigTo; /* rx */
+  double* sigUo; /* ry */
+  double sigE;
+  double sigF;
+  double sigH;   /* a scalar, as in EMstepC and PPLS_simult */
+} ppls_po2_theta;
+
+/* EMstepC's list (loglC.cpp:231-249) from S.  Every pointer is nullable (not requested); all
+ * matrices column-major and full, as EMstepC returns them. */
+typedef struct {
+  double* Cxt;   /* p x r:  E[x t'] */
+  double* Cxto;  /* p x rx */
+  double* Cyu;   /* q x r */
+  double* Cyuo;  /* q x ry */
+  double* Ctt;   /* r x r */
+  double* Ctoto; /* rx x rx */
+  double* Ctto;  /* r x rx */
+  double* Cuu;   /* r x r */
+  double* Cuouo; /* ry x ry */
+  double* Cuuo;  /* r x ry */
+  double* Cut;   /* r x r:  E[u t'] */
+  double* Chh;   /* r x r */
+  double* K;     /* k x k:  D Lambda^-1; the posterior means of the rows are [X Gx | Y Gy] K */
+  double Cee;
+  double Cff;
+} ppls_po2_expect;
+
+/* All four use the S the context holds (streamed, fold-selected, resampled, permuted, weighted,
+ * adjusted); on resident rows with no S they form it by the route 'o2m_xprod' uses and keep it until
+ * ppls_xprod_release or new data.  N is the row count ppls_em_run uses.  They need no collective on
+ * sharded contexts (S is replicated), end no ppls_em_begin session, change no option and leave S bit
+ * for bit.  Refusals, each with the outputs and theta untouched: PPLS_E_ARG (sizes outside the above,
+ * a NULL loading, a non-finite value, a sigma that is not above 0), PPLS_E_STATE (no data, or an open
+ * stream), PPLS_E_NUMERIC (Lambda not positive definite, an updated variance not above 0, a
+ * rank-deficient loading update).
+ *
+ * ppls_po2_estep replaces EMstepC (loglC.cpp:116-250): the E-step moments at theta, without the dense
+ * (p+q) x (p+q) inverse of :139-141.  ppls_po2_loglik replaces loglC (:36-113), with the constant
+ * -N (p+q)/2 log 2 pi (as loglC_fast :336; loglC:81 has p alone). */
+int ppls_po2_estep(ppls_ctx* ctx, const ppls_po2_theta* th, int r, int rx, int ry, ppls_po2_expect* out);
+int ppls_po2_loglik(ppls_ctx* ctx, const ppls_po2_theta* th, int r, int rx, int ry, double* out);
+/* The EM loop the reference leaves unwritten (loglC.cpp:228, "Maximization step is done in R"): per
+ * iteration one pass over S at theta_{i-1}, its log-likelihood as a by-product, the stop rule
+ * (i >= 2 and l_{i-1} - l_{i-2} < atol returns theta_{i-1}; atol = -Inf never stops), else one ECM
+ * cycle: W <- orth(Cxt - Wo Ctto'), C <- orth(Cyu - Co Cuuo'); Wo <- orth(Cxto - W Ctto),
+ * Co <- orth(Cyuo - C Cuuo) with the new W, C and the same moments; then the scalars.  One last pass
+ * gives l and the moments at the estimates when the rule never fired: *n_loglik = steps + 1 entries
+ * (at most cap are copied; cap >= max_steps + 1 holds them all), and expect_out belongs to the
+ * returned theta.  The loop runs on the device: loadings, scalars and the history stay there, the
+ * stop rule sets the flag ppls_em_run's kernels use.  type: PPLS_ORTH_SVD (the polar factor) or
+ * PPLS_ORTH_QR (sign_e qr.Q(qr(.)), R's sign rule, functions.R:257-259).  th is overwritten with the estimates in
+ * canonical form: the joint part by PPLS_simult's sign and order rule (EM_W_multi.R:794-799), the
+ * specific components by decreasing sigma, each column's sign so that its sum is >= 0.
+ * *negative_increment (nullable): whether the history has a negative increment. */
+int ppls_po2_em_run(ppls_ctx* ctx, ppls_po2_theta* th, int r, int rx, int ry, int max_steps, double atol, int type,
+                    double* loglik, int cap, int* n_loglik, int* negative_increment, ppls_po2_expect* expect_out);
+
+/* Default start values.  Joint part (W, C, B, sigT, sigE, sigF, sigH): the 'o2m_xprod' sequential fit
+ * ppls_ppls_o2m(ctx, r, 1, 1e-4, ...) -- the cross-covariance directions after one EM step per
+ * component (more steps of that shared-only model pull a joint loading towards the strongest X-only
+ * direction).  That fit runs on a scratch context of the call holding a copy of S (8 P^2
+ * bytes for its duration), because the sequential fit keeps its state in its context: this context's
+ * ppls_em_begin session, options and 'o2m_xprod' record (ppls_o2m_info) stay as they are.  Wo: the dominant rx-dimensional invariant subspace of
+ * (I - P_W) S_xx (I - P_W), P_W the projector onto W's columns, by `steps` orthogonal-iteration steps
+ * of the statistics pass (both sides in one read of S per step; the p x rx projection and QR on the
+ * host) from V0x (p x rx, host, e.g. normal draws), then sigTo = sqrt(diag(V'S_xx V) / N); Co, sigUo
+ * alike from V0y (q x ry).  V0x / V0y are not read when rx / ry = 0.  PPLS_E_NUMERIC: a
+ * rank-deficient block.  theta_out (caller's buffers) is written only on success. */
+int ppls_po2_start(ppls_ctx* ctx, int r, int rx, int ry, const double* V0x, const double* V0y, int steps,
+                   ppls_po2_theta* theta_out);
+
 /* ---- host-side algebra (no GPU; the same code the device finalize runs) ------------------------ */
 /* From the all-reduced sufficient statistics of one sweep with theta (stats = [X'mu_T p x r |
  * Y'mu_U q x r | Gram 2r x 2r], all column-major) compute Expect_M's moments, logl_W(theta) and

@@ -266,6 +266,33 @@ int ppls_xadjust_matrix(ppls_ctx* ctx, const double* S_src, int p, int ldx, int 
  * this context (ppls_xprod_adjust records on dst). */
 int ppls_adjust_timing(ppls_ctx* ctx, double* ms4);
 
+/* ---- PO2PLS ----
+ * The statistics pass and the Gram alone on a caller's S: M = S blockdiag(Gx, Gy) (P x (kx + ky),
+ * column-major), Q = G'M ((kx + ky)^2) and GG = [Gx'Gx (kx^2) | Gy'Gy (ky^2)].  S: host, row-major
+ * P x P with the X block ldx wide (ldx, P - ldx even), uploaded around the launches -- or NULL for the
+ * S the context holds (P, ldx must then be its own).  Gx: ldx x kx, Gy: (P - ldx) x ky host
+ * column-major, padding rows included; 1 <= kx, ky <= 16.  rw: rows of S per wave (1, 2, 4, 8 (a
+ * width <= 8); 0 = what the fit takes).  Every output is written between NaN guards, which are
+ * checked.  A context without data serves when S is given. */
+int ppls_po2_stats(ppls_ctx* ctx, const double* S, int P, int ldx, const double* Gx, int kx, const double* Gy, int ky,
+                   int rw, double* M, double* Q, double* GG);
+/* The small kernel alone on given Q, GG = [Gx'Gx | Gy'Gy] and the scalars of th (its loadings are not
+ * read), for p, q real columns, N rows and the traces ssqX, ssqY: the moment blocks and K into out
+ * (Cxt.. are not written), the log-likelihood, and the kernel's status word (0, or PPLS_PO2_ST_*: -21
+ * a sigma, -22 Lambda not positive definite).  Returns PPLS_E_NUMERIC with out and *loglik untouched
+ * when the status is not 0. */
+int ppls_po2_small(ppls_ctx* ctx, const double* Q, const double* GG, const ppls_po2_theta* th, int r, int rx, int ry,
+                   int p, int q, double N, double ssqX, double ssqY, ppls_po2_expect* out, double* loglik, int* status);
+/* One ECM step at theta exactly as the device leaves it -- pass, Gram, small kernel, loading update of
+ * the given orth type -- with NO canonical form applied: theta_out (caller's buffers, written only on
+ * success) carries the column signs and order of the update itself (the check of R's QR sign rule). */
+int ppls_po2_em_step(ppls_ctx* ctx, const ppls_po2_theta* th, int r, int rx, int ry, int type, ppls_po2_theta* theta_out);
+/* HIP-event times (ms per launch, reps launches back to back each) on the context's S at theta:
+ * ms6 = {the pass (both panels), the Gram, the small kernel, the loading update (polar type), one whole
+ * iteration, the loading update of the QR type -- the same work without the Jacobi polar factor}.
+ * Theta on the device is restored between the parts; nothing of the context changes. */
+int ppls_po2_timing(ppls_ctx* ctx, const ppls_po2_theta* th, int r, int rx, int ry, int reps, double* ms6);
+
 #ifdef __cplusplus
 }
 #endif

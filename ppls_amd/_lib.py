@@ -32,6 +32,17 @@ class PplsExpect(ct.Structure):
                 ("Cee", ct.c_double), ("Cff", ct.c_double), ("Chh", _dp)]
 
 
+class PplsPo2Theta(ct.Structure):
+    _fields_ = [("W", _dp), ("Wo", _dp), ("C", _dp), ("Co", _dp), ("B", _dp), ("sigT", _dp), ("sigTo", _dp),
+                ("sigUo", _dp), ("sigE", ct.c_double), ("sigF", ct.c_double), ("sigH", ct.c_double)]
+
+
+class PplsPo2Expect(ct.Structure):
+    _fields_ = [("Cxt", _dp), ("Cxto", _dp), ("Cyu", _dp), ("Cyuo", _dp), ("Ctt", _dp), ("Ctoto", _dp), ("Ctto", _dp),
+                ("Cuu", _dp), ("Cuouo", _dp), ("Cuuo", _dp), ("Cut", _dp), ("Chh", _dp), ("K", _dp),
+                ("Cee", ct.c_double), ("Cff", ct.c_double)]
+
+
 class PplsSeqFit(ct.Structure):
     _fields_ = [("W", _dp), ("C", _dp), ("B", _dp), ("sig", _dp), ("logvalue", _dp),
                 ("last_increment", _dp), ("number_steps", ct.POINTER(ct.c_int)),
@@ -218,6 +229,21 @@ SIGNATURES = {
     "ppls_xadjust_matrix": (ct.c_int, [ct.c_void_p, _dp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int,
                                        ct.c_int, _dp]),
     "ppls_adjust_timing": (ct.c_int, [ct.c_void_p, _dp]),
+    "ppls_po2_estep": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsPo2Theta), ct.c_int, ct.c_int, ct.c_int,
+                                  ct.POINTER(PplsPo2Expect)]),
+    "ppls_po2_loglik": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsPo2Theta), ct.c_int, ct.c_int, ct.c_int, _dp]),
+    "ppls_po2_em_run": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsPo2Theta), ct.c_int, ct.c_int, ct.c_int, ct.c_int,
+                                   ct.c_double, ct.c_int, _dp, ct.c_int, ct.POINTER(ct.c_int), ct.POINTER(ct.c_int),
+                                   ct.POINTER(PplsPo2Expect)]),
+    "ppls_po2_start": (ct.c_int, [ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, _dp, _dp, ct.c_int, ct.POINTER(PplsPo2Theta)]),
+    "ppls_po2_em_step": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsPo2Theta), ct.c_int, ct.c_int, ct.c_int, ct.c_int,
+                                    ct.POINTER(PplsPo2Theta)]),
+    "ppls_po2_stats": (ct.c_int, [ct.c_void_p, _dp, ct.c_int, ct.c_int, _dp, ct.c_int, _dp, ct.c_int, ct.c_int, _dp, _dp,
+                                  _dp]),
+    "ppls_po2_small": (ct.c_int, [ct.c_void_p, _dp, _dp, ct.POINTER(PplsPo2Theta), ct.c_int, ct.c_int, ct.c_int, ct.c_int,
+                                  ct.c_int, ct.c_double, ct.c_double, ct.c_double, ct.POINTER(PplsPo2Expect), _dp,
+                                  ct.POINTER(ct.c_int)]),
+    "ppls_po2_timing": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsPo2Theta), ct.c_int, ct.c_int, ct.c_int, ct.c_int, _dp]),
 }
 
 
@@ -319,3 +345,89 @@ class Expect:
         return dict(mu_T=self.mu_T, mu_U=self.mu_U, Ctt=np.diag(self.Ctt), Cuu=np.diag(self.Cuu),
                     Cut=np.diag(self.Cut), Cee=np.array([[self.Cee]]), Cff=np.array([[self.Cff]]),
                     Chh=np.array(self.Chh))
+
+
+class Po2Theta:
+    """Host-side PO2PLS theta (owned numpy buffers, column-major): W, Wo, C, Co, B, sigT, sigTo, sigUo
+    and the scalars sigE, sigF, sigH.  Diagonal matrices or vectors are taken for B and the sigmas."""
+
+    def __init__(self, W, Wo, C, Co, B, sigT, sigTo, sigUo, sigE, sigF, sigH):
+        self.W = np.asfortranarray(np.array(W, dtype=np.float64, ndmin=2))
+        self.C = np.asfortranarray(np.array(C, dtype=np.float64, ndmin=2))
+        p, q = self.W.shape[0], self.C.shape[0]
+        self.Wo = np.asfortranarray(np.array(Wo, dtype=np.float64).reshape(p, -1)) if Wo is not None else np.zeros((p, 0), order="F")
+        self.Co = np.asfortranarray(np.array(Co, dtype=np.float64).reshape(q, -1)) if Co is not None else np.zeros((q, 0), order="F")
+
+        def vec(v, n):
+            if n == 0:
+                return np.zeros(0)
+            v = np.asarray(v, dtype=np.float64)
+            v = np.diag(v) if v.ndim == 2 else np.broadcast_to(np.ravel(v), (n,))
+            return np.ascontiguousarray(v, dtype=np.float64).copy()
+
+        self.B = vec(B, self.r)
+        self.sigT = vec(sigT, self.r)
+        self.sigTo = vec(sigTo, self.rx)
+        self.sigUo = vec(sigUo, self.ry)
+        self.sigE, self.sigF, self.sigH = (float(np.ravel(v)[0]) for v in (sigE, sigF, sigH))
+        if self.C.shape[1] != self.r:
+            raise ValueError("W and C need the same number of joint components")
+
+    r = property(lambda self: self.W.shape[1])
+    rx = property(lambda self: self.Wo.shape[1])
+    ry = property(lambda self: self.Co.shape[1])
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls(d["W"], d.get("Wo"), d["C"], d.get("Co"), d["B"], d["sigT"], d.get("sigTo", ()), d.get("sigUo", ()),
+                   d["sigE"], d["sigF"], d["sigH"])
+
+    def copy(self):
+        return Po2Theta(self.W, self.Wo, self.C, self.Co, self.B, self.sigT, self.sigTo, self.sigUo, self.sigE, self.sigF,
+                        self.sigH)
+
+    def struct(self) -> PplsPo2Theta:
+        return PplsPo2Theta(dptr(self.W), dptr(self.Wo) if self.rx else None, dptr(self.C), dptr(self.Co) if self.ry else None,
+                            dptr(self.B), dptr(self.sigT), dptr(self.sigTo) if self.rx else None,
+                            dptr(self.sigUo) if self.ry else None, self.sigE, self.sigF, self.sigH)
+
+    def pull(self, s: PplsPo2Theta):
+        self.sigE, self.sigF, self.sigH = s.sigE, s.sigF, s.sigH
+
+    def as_dict(self):
+        return dict(W=self.W.copy(), Wo=self.Wo.copy(), C=self.C.copy(), Co=self.Co.copy(), B=np.diag(self.B),
+                    sigT=np.diag(self.sigT), sigTo=np.diag(self.sigTo), sigUo=np.diag(self.sigUo), sigE=self.sigE,
+                    sigF=self.sigF, sigH=self.sigH)
+
+
+class Po2Expect:
+    """Host buffers for EMstepC's list from S (ppls_po2_expect)."""
+
+    NAMES = ("Cxt", "Cxto", "Cyu", "Cyuo", "Ctt", "Ctoto", "Ctto", "Cuu", "Cuouo", "Cuuo", "Cut", "Chh", "K")
+
+    def __init__(self, p, q, r, rx, ry, want_cdz=True):
+        k = 2 * r + rx + ry
+        shapes = dict(Cxt=(p, r), Cxto=(p, rx), Cyu=(q, r), Cyuo=(q, ry), Ctt=(r, r), Ctoto=(rx, rx), Ctto=(r, rx),
+                      Cuu=(r, r), Cuouo=(ry, ry), Cuuo=(r, ry), Cut=(r, r), Chh=(r, r), K=(k, k))
+        self.want_cdz = want_cdz
+        for n, sh in shapes.items():
+            setattr(self, n, np.zeros(sh, order="F"))
+        self.Cee = self.Cff = 0.0
+
+    def struct(self) -> PplsPo2Expect:
+        def ptr(n):
+            a = getattr(self, n)
+            if a.size == 0 or (not self.want_cdz and n in ("Cxt", "Cxto", "Cyu", "Cyuo")):
+                return None
+            return dptr(a)
+        return PplsPo2Expect(*[ptr(n) for n in self.NAMES], 0.0, 0.0)
+
+    def pull(self, s: PplsPo2Expect):
+        self.Cee, self.Cff = s.Cee, s.Cff
+
+    def as_dict(self):
+        d = {n: np.array(getattr(self, n)) for n in self.NAMES
+             if self.want_cdz or n not in ("Cxt", "Cxto", "Cyu", "Cyuo")}
+        d["Cee"] = np.array([[self.Cee]])
+        d["Cff"] = np.array([[self.Cff]])
+        return d

@@ -12,6 +12,8 @@ Same names, argument meaning, return structure and error behaviour as the R func
 * ``meta_PPLSi``   Package/PPLS/R/EM_W_multi.R:509-589
 * ``PPLS_to_o2m``  Package/PPLS/R/PPLS_to_o2m.R:28-80
 * ``variances_PPLS_simult``  Package/PPLS/R/EM_W_multi.R:830-860 (variances.PPLS_simult)
+* ``PO2PLS_Expect`` / ``PO2PLS_logl`` / ``PO2PLS``  Package/PPLS/src/loglC.cpp:116-250 (EMstepC), :36-113 (loglC), and
+  the loop the reference leaves unwritten (:228)
 
 Every call goes through the C ABI (include/ppls.h) into the HIP kernels on the GPU; matrices
 are numpy arrays, R lists are dicts.  Passing ``X=None, Y=None`` uses the data already resident
@@ -28,7 +30,8 @@ import warnings
 import numpy as np
 
 from . import _lib
-from ._lib import Expect, PplsError, Theta, dptr
+from ._lib import Expect, Po2Expect, Po2Theta, PplsError, Theta, dptr
+from .po2 import canonical_PO2PLS, simulate_PO2PLS, summary_PO2PLS  # noqa: F401
 
 
 def pop_rows(pop_sizes, row0, n_local):
@@ -1038,6 +1041,104 @@ class Context:
         U = np.zeros((self.n_local, k), order="F")
         self._chk(self._L.ppls_scores(self.h, dptr(W), dptr(C), int(k), dptr(T), dptr(U)))
         return T, U
+
+    # -- PO2PLS from the cross-products
+    def po2_estep(self, th: Po2Theta, want_cdz=True) -> Po2Expect:
+        """EMstepC's list (loglC.cpp:116-250) at theta, from the S the context holds."""
+        e = Po2Expect(self.p, self.q, th.r, th.rx, th.ry, want_cdz)
+        ts, es = th.struct(), e.struct()
+        self._chk(self._L.ppls_po2_estep(self.h, ct.byref(ts), th.r, th.rx, th.ry, ct.byref(es)))
+        e.pull(es)
+        return e
+
+    def po2_loglik(self, th: Po2Theta) -> float:
+        """loglC's value (loglC.cpp:36-113) at theta, from S."""
+        out = ct.c_double()
+        ts = th.struct()
+        self._chk(self._L.ppls_po2_loglik(self.h, ct.byref(ts), th.r, th.rx, th.ry, ct.byref(out)))
+        return out.value
+
+    def po2_em_run(self, th: Po2Theta, max_steps=100, atol=1e-4, type_=_lib.PPLS_ORTH_SVD, want_eout=True):
+        """The PO2PLS EM loop on the device; returns (estimates, loglik history, Po2Expect or None,
+        negative increment seen)."""
+        est = th.copy()
+        e = Po2Expect(self.p, self.q, th.r, th.rx, th.ry) if want_eout else None
+        ll = np.zeros(int(max_steps) + 1)
+        n, neg = ct.c_int(), ct.c_int()
+        ts = est.struct()
+        es = e.struct() if e is not None else None
+        self._chk(self._L.ppls_po2_em_run(self.h, ct.byref(ts), th.r, th.rx, th.ry, int(max_steps), float(atol), int(type_),
+                                          dptr(ll), len(ll), ct.byref(n), ct.byref(neg),
+                                          ct.byref(es) if es is not None else None))
+        est.pull(ts)
+        if e is not None:
+            e.pull(es)
+        return est, ll[:n.value].copy(), e, bool(neg.value)
+
+    def po2_start(self, r, rx, ry, V0x=None, V0y=None, steps=10) -> Po2Theta:
+        """ppls_po2_start: the default start values -- the joint part from the one-step 'o2m_xprod' sequential
+        fit, the specific loadings from ``steps`` orthogonal-iteration steps of the statistics pass started
+        at V0x (p x rx) and V0y (q x ry), sigTo / sigUo from V'S V / N."""
+        r, rx, ry = int(r), int(rx), int(ry)
+        th = Po2Theta(np.zeros((self.p, r)), np.zeros((self.p, rx)), np.zeros((self.q, r)), np.zeros((self.q, ry)),
+                      np.zeros(r), np.zeros(r), np.zeros(rx), np.zeros(ry), 1.0, 1.0, 1.0)
+        vx = np.asfortranarray(np.asarray(V0x, dtype=np.float64).reshape(self.p, rx)) if rx else None
+        vy = np.asfortranarray(np.asarray(V0y, dtype=np.float64).reshape(self.q, ry)) if ry else None
+        ts = th.struct()
+        self._chk(self._L.ppls_po2_start(self.h, r, rx, ry, dptr(vx), dptr(vy), int(steps), ct.byref(ts)))
+        th.pull(ts)
+        return th
+
+    def po2_em_step(self, th: Po2Theta, type_=_lib.PPLS_ORTH_SVD) -> Po2Theta:
+        """One ECM step at theta as the device leaves it (ppls_po2_em_step): no canonical form."""
+        out = th.copy()
+        ts, os_ = th.struct(), out.struct()
+        self._chk(self._L.ppls_po2_em_step(self.h, ct.byref(ts), th.r, th.rx, th.ry, int(type_), ct.byref(os_)))
+        out.pull(os_)
+        return out
+
+    def po2_stats(self, Gx, Gy, S=None, ldx=None, rw=0):
+        """The PO2 statistics pass and Gram alone: (M, Q, Gx'Gx, Gy'Gy) for loadings Gx (ldx x kx), Gy
+        (ldy x ky) given with their padding rows, on a host S (row-major P x P, X block ldx wide) or,
+        S = None, on the context's own."""
+        Gx = np.asfortranarray(np.array(Gx, dtype=np.float64, ndmin=2))
+        Gy = np.asfortranarray(np.array(Gy, dtype=np.float64, ndmin=2))
+        kx, ky = Gx.shape[1], Gy.shape[1]
+        ldx = Gx.shape[0] if ldx is None else int(ldx)
+        P = ldx + Gy.shape[0]
+        if S is not None:
+            S = np.ascontiguousarray(S, dtype=np.float64)
+            if S.shape != (P, P):
+                raise ValueError(f"S must be {P} x {P}")
+        k = kx + ky
+        M, Q, GG = np.zeros((P, k), order="F"), np.zeros((k, k), order="F"), np.zeros(kx * kx + ky * ky)
+        self._chk(self._L.ppls_po2_stats(self.h, dptr(S) if S is not None else None, P, ldx, dptr(Gx), kx, dptr(Gy), ky,
+                                         int(rw), dptr(M), dptr(Q), dptr(GG)))
+        return M, Q, GG[:kx * kx].reshape(kx, kx, order="F").copy(), GG[kx * kx:].reshape(ky, ky, order="F").copy()
+
+    def po2_small(self, Q, GGx, GGy, th: Po2Theta, p, q, N, ssqX, ssqY):
+        """The small kernel alone: (Po2Expect without C_dz or None, loglik or None, status word)."""
+        k = 2 * th.r + th.rx + th.ry
+        Q = np.asfortranarray(np.array(Q, dtype=np.float64).reshape(k, k))
+        GG = np.concatenate([np.ravel(np.asarray(GGx, dtype=np.float64), order="F"),
+                             np.ravel(np.asarray(GGy, dtype=np.float64), order="F")])
+        e = Po2Expect(int(p), int(q), th.r, th.rx, th.ry, want_cdz=False)
+        ts, es = th.struct(), e.struct()
+        ll, st = ct.c_double(float("nan")), ct.c_int()
+        rc = self._L.ppls_po2_small(self.h, dptr(Q), dptr(GG), ct.byref(ts), th.r, th.rx, th.ry, int(p), int(q), float(N),
+                                    float(ssqX), float(ssqY), ct.byref(es), ct.byref(ll), ct.byref(st))
+        if rc == -3:   # PPLS_E_NUMERIC: the status word says why
+            return None, None, st.value
+        self._chk(rc)
+        e.pull(es)
+        return e, ll.value, st.value
+
+    def po2_timing(self, th: Po2Theta, reps=50):
+        """HIP-event ms per launch: dict(pass, gram, small, update, iteration, update_qr)."""
+        ms = np.zeros(6)
+        ts = th.struct()
+        self._chk(self._L.ppls_po2_timing(self.h, ct.byref(ts), th.r, th.rx, th.ry, int(reps), dptr(ms)))
+        return dict(zip(("pass", "gram", "small", "update", "iteration", "update_qr"), ms.tolist()))
 
     # -- cross-validation (crossval_PPLS.R:12-114)
     @staticmethod
@@ -3016,3 +3117,79 @@ def diagnostics_PPLS(fit, X=None, Y=None, ctx=None, subset=None, new=False, resc
     out = dict(res)
     out.update(diagnostics_summary(res, p, q, r, th.sigE, th.sigF, alpha=alpha, adjust=adjust))
     return out
+
+
+# ---------------------------------------------------------------------------- PO2PLS
+def _po2_theta(W, C, P_Yosc, P_Xosc, B_T, sigX, sigY, sigH, sigT, sigTo, sigUo):
+    return Po2Theta(W, P_Yosc, C, P_Xosc, B_T, sigT, sigTo if sigTo is not None else (), sigUo if sigUo is not None else (),
+                    sigX, sigY, sigH)
+
+
+def PO2PLS_Expect(X, Y, W, C, P_Yosc, P_Xosc, B_T, sigX, sigY, sigH, sigT, sigTo, sigUo, ctx=None):
+    """EMstepC (loglC.cpp:116-250) from the cross-products: its list of expected sample covariances
+    (Cxt, Cxto, Ctt, Ctto, Ctoto, Cyu, Cyuo, Cuu, Cuuo, Cuouo, Cut, Chh as full matrices), with Cee and
+    Cff as the scalars tr(.)/p, tr(.)/q of its diag_Cee, diag_Cff, and K = D Lambda^-1 (the posterior
+    means of the rows are [X Gx | Y Gy] K).  ``X = Y = None``: the context's data, rows or S alone."""
+    ctx = _ctx_with(X, Y, ctx)
+    return ctx.po2_estep(_po2_theta(W, C, P_Yosc, P_Xosc, B_T, sigX, sigY, sigH, sigT, sigTo, sigUo)).as_dict()
+
+
+def PO2PLS_logl(X, Y, W, C, P_Yosc, P_Xosc, B_T, sigX, sigY, sigH, sigT, sigTo, sigUo, ctx=None):
+    """loglC's value (loglC.cpp:36-113) from the cross-products, with the constant -N (p+q)/2 log 2 pi."""
+    ctx = _ctx_with(X, Y, ctx)
+    return ctx.po2_loglik(_po2_theta(W, C, P_Yosc, P_Xosc, B_T, sigX, sigY, sigH, sigT, sigTo, sigUo))
+
+
+def PO2PLS(X, Y, r, rx, ry, EMsteps=100, atol=1e-4, type="SVD", init="ppls", rng=None, ctx=None, start_steps=10):
+    """Fit the PO2PLS model -- PPLS_simult's plus rx X-specific and ry Y-specific components (the
+    reference's simulC model, loglC.cpp:268-315) -- by EM on the cross-products S, on the device.
+
+    Returns dict(Expectations, loglik, estimates, class="PO2PLS"): estimates has W, Wo, C, Co, B, sigT,
+    sigTo, sigUo (diagonal matrices), sigE, sigF, sigH in canonical form; loglik has steps + 1 entries;
+    Expectations is ``PO2PLS_Expect`` at the estimates.  ``X = Y = None``: the context's data -- any
+    context that holds S (streamed, fold-selected, resampled, permuted, weighted, adjusted) or rows.
+
+    ``init="ppls"`` (``ppls_po2_start``): the joint part from the 'o2m_xprod' sequential fit with ONE EM
+    step per component -- the cross-covariance directions.  More steps are worse: every step of that
+    shared-only model pulls a joint loading towards the strongest X-only direction (on the recovery
+    problem of tests/po2_bar.py the start's loading-space error grows from 0.4-0.6 at 1 step to 1.4 at 5
+    and 20 steps, and from the 20-step start the EM stays at the shared-only optimum for more than 300
+    steps; from the 1-step start it recovers within 100).
+
+    The specific loadings come from ``start_steps`` orthogonal-iteration steps of the statistics pass,
+    started at normal draws from ``rng``.
+
+    ``init=dict(W, Wo, C, Co, B, sigT, sigTo, sigUo, sigE, sigF, sigH)`` is taken as given (loadings need
+    not be orthonormal).  ``type``: "SVD" (the polar factor) or "QR" (R's sign rule), as PPLS_simult.
+    Warns "Negative increments of likelihood" as PPLS_simult does."""
+    ctx = _ctx_with(X, Y, ctx)
+    r, rx, ry = int(r), int(rx), int(ry)
+    t = _orth_type(type)
+    if isinstance(init, dict):
+        th = Po2Theta.from_dict(init)
+        if (th.r, th.rx, th.ry) != (r, rx, ry):
+            raise ValueError(f"init has (r, rx, ry) = {(th.r, th.rx, th.ry)}, asked for {(r, rx, ry)}")
+    elif init == "ppls":
+        rng = rng if rng is not None else np.random.default_rng()
+        th = ctx.po2_start(r, rx, ry, rng.standard_normal((ctx.p, rx)), rng.standard_normal((ctx.q, ry)), start_steps)
+    else:
+        raise ValueError("init must be 'ppls' or a dict of starting values")
+    est, ll, eout, neg = ctx.po2_em_run(th, int(EMsteps), float(atol), t, want_eout=True)
+    if neg:
+        warnings.warn("Negative increments of likelihood")
+    return {"Expectations": eout.as_dict(), "loglik": ll, "estimates": est.as_dict(), "class": "PO2PLS"}
+
+
+def scores_PO2PLS(fit, X=None, Y=None, ctx=None):
+    """The posterior means of the latent variables of the rows, [X Gx | Y Gy] K (n_local x k, columns
+    in the order t, t_o, u, u_o), by the ``ppls_scores`` pass with zero-padded columns and K on the host.
+    Refused (PPLS_E_STATE) on a context that holds no rows."""
+    ctx = _ctx_with(X, Y, ctx)
+    e = fit["estimates"]
+    Gx, Gy = np.hstack([e["W"], e["Wo"]]), np.hstack([e["C"], e["Co"]])
+    kx, ky = Gx.shape[1], Gy.shape[1]
+    km = max(kx, ky)
+    Gxp, Gyp = np.zeros((ctx.p, km)), np.zeros((ctx.q, km))
+    Gxp[:, :kx], Gyp[:, :ky] = Gx, Gy
+    T, Us = ctx.scores(Gxp, Gyp)
+    return np.hstack([T[:, :kx], Us[:, :ky]]) @ np.asarray(fit["Expectations"]["K"])

@@ -37,6 +37,7 @@
 #include "ppls_cvstream.h"
 #include "ppls_stream.h"
 #include "ppls_varxprod.h"
+#include "ppls_po2.h"
 #include "ppls_xprod.h"
 #include "ppls_xprod_meta.h"
 
@@ -7676,6 +7677,706 @@ int ppls_xadjust_matrix(ppls_ctx* c, const double* S_src, int p, int ldx, int q_
     if (!std::isnan(h[g]) || !std::isnan(h[guard + (size_t)P * P + g]))
       return fail(c, PPLS_E_NUMERIC, "the Schur kernel wrote outside its P x P output");
   std::copy(h.begin() + guard, h.begin() + guard + (size_t)P * P, S_dst);
+  return PPLS_OK;
+}
+
+}  // extern "C"
+
+// ============================================================================ PO2PLS
+// X- and Y-specific components fitted from S (ppls_po2.hip).  Replaces the reference's loglC
+// (Package/PPLS/src/loglC.cpp:36-113) and EMstepC (:116-250) and supplies the M-step it lacks (:228).
+namespace {
+
+struct Po2Shape {
+  int r, rx, ry, kx, ky, k;
+};
+
+// The device side of one PO2 call: scratch that lives as long as the call, and the kernels' arguments.
+struct Po2Dev {
+  CvScratch tmp;
+  PplsPo2Args a{};
+  double *Gx0 = nullptr, *Gy0 = nullptr;   // timing: the uploaded theta, to restore it
+  PplsPo2Scalars* sc0 = nullptr;
+  PplsPo2Scalars hsc{};
+  int rw = 0;
+};
+
+int po2_shape(ppls_ctx* c, int r, int rx, int ry, int p, int q, Po2Shape* s) {
+  if (r < 1 || rx < 0 || ry < 0 || r + rx > PPLS_RMAX || r + ry > PPLS_RMAX || r + rx > p || r + ry > q)
+    return fail(c, PPLS_E_ARG, "PO2PLS sizes r=%d rx=%d ry=%d outside r >= 1, rx, ry >= 0, r + rx <= min(%d, p=%d), r + ry <= min(%d, q=%d)",
+                r, rx, ry, PPLS_RMAX, p, PPLS_RMAX, q);
+  *s = {r, rx, ry, r + rx, r + ry, 2 * r + rx + ry};
+  return PPLS_OK;
+}
+
+bool po2_sigma_ok(double v) { return std::isfinite(v) && v > 0.0; }
+
+int po2_check_scalars(ppls_ctx* c, const ppls_po2_theta* th, const Po2Shape& s) {
+  if (!th || !th->B || !th->sigT || (s.rx && !th->sigTo) || (s.ry && !th->sigUo)) return fail(c, PPLS_E_ARG, "NULL argument");
+  bool ok = po2_sigma_ok(th->sigE) && po2_sigma_ok(th->sigF) && po2_sigma_ok(th->sigH);
+  for (int j = 0; j < s.r; ++j) ok = ok && po2_sigma_ok(th->sigT[j]) && std::isfinite(th->B[j]);
+  for (int j = 0; j < s.rx; ++j) ok = ok && po2_sigma_ok(th->sigTo[j]);
+  for (int j = 0; j < s.ry; ++j) ok = ok && po2_sigma_ok(th->sigUo[j]);
+  if (!ok) return fail(c, PPLS_E_ARG, "PO2PLS theta: every sigma must be finite and above 0, B finite");
+  return PPLS_OK;
+}
+
+int po2_check_theta(ppls_ctx* c, const ppls_po2_theta* th, const Po2Shape& s, int p, int q) {
+  int rc;
+  if ((rc = po2_check_scalars(c, th, s))) return rc;
+  if (!th->W || !th->C || (s.rx && !th->Wo) || (s.ry && !th->Co)) return fail(c, PPLS_E_ARG, "NULL argument");
+  bool ok = true;
+  for (size_t e = 0; e < (size_t)p * s.r && ok; ++e) ok = std::isfinite(th->W[e]);
+  for (size_t e = 0; e < (size_t)p * s.rx && ok; ++e) ok = std::isfinite(th->Wo[e]);
+  for (size_t e = 0; e < (size_t)q * s.r && ok; ++e) ok = std::isfinite(th->C[e]);
+  for (size_t e = 0; e < (size_t)q * s.ry && ok; ++e) ok = std::isfinite(th->Co[e]);
+  if (!ok) return fail(c, PPLS_E_ARG, "PO2PLS theta: non-finite loadings");
+  return PPLS_OK;
+}
+
+void po2_pack_scalars(const ppls_po2_theta* th, const Po2Shape& s, PplsPo2Scalars* h) {
+  memset(h, 0, sizeof *h);
+  for (int j = 0; j < s.r; ++j) { h->b[j] = th->B[j]; h->sT[j] = th->sigT[j]; }
+  for (int j = 0; j < s.rx; ++j) h->sTo[j] = th->sigTo[j];
+  for (int j = 0; j < s.ry; ++j) h->sUo[j] = th->sigUo[j];
+  h->sE = th->sigE; h->sF = th->sigF; h->sH = th->sigH;
+}
+
+// [A | Ao] (rows x (ca + co), column-major) into ld-padded device columns (padding rows zero).
+int po2_upload_side(ppls_ctx* c, const double* A, int ca, const double* Ao, int co, int rows, int ld, double* dst) {
+  std::vector<double> h((size_t)ld * (ca + co), 0.0);
+  for (int j = 0; j < ca; ++j) std::copy(A + (size_t)j * rows, A + (size_t)(j + 1) * rows, h.begin() + (size_t)j * ld);
+  for (int j = 0; j < co; ++j) std::copy(Ao + (size_t)j * rows, Ao + (size_t)(j + 1) * rows, h.begin() + (size_t)(ca + j) * ld);
+  HIPCHK(c, hipMemcpy(dst, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
+  return PPLS_OK;
+}
+
+// Scratch, arguments and theta on the device, for the context's S.
+int po2_setup(ppls_ctx* c, Po2Dev& d, const ppls_po2_theta* th, const Po2Shape& s, int hist, bool keep_copy) {
+  int rc;
+  const int ldx = c->ldx, ldy = c->ldy, P = ldx + ldy;
+  PplsPo2Args& a = d.a;
+  int* ints = nullptr;
+  if ((rc = d.tmp.get(c, &a.Gx, (size_t)ldx * s.kx)) || (rc = d.tmp.get(c, &a.Gy, (size_t)ldy * s.ky)) ||
+      (rc = d.tmp.get(c, &a.sc, 1)) || (rc = d.tmp.get(c, &a.M, (size_t)P * s.k)) || (rc = d.tmp.get(c, &a.Q, (size_t)s.k * s.k)) ||
+      (rc = d.tmp.get(c, &a.GGx, (size_t)s.kx * s.kx)) || (rc = d.tmp.get(c, &a.GGy, (size_t)s.ky * s.ky)) ||
+      (rc = d.tmp.get(c, &a.sm, 1)) || (rc = d.tmp.get(c, &a.Z, (size_t)PPLS_RMAX * P)) ||
+      (rc = d.tmp.get(c, &a.loglik, (size_t)hist)) || (rc = d.tmp.get(c, &ints, 4)))
+    return rc;
+  if (keep_copy && ((rc = d.tmp.get(c, &d.Gx0, (size_t)ldx * s.kx)) || (rc = d.tmp.get(c, &d.Gy0, (size_t)ldy * s.ky)) ||
+                    (rc = d.tmp.get(c, &d.sc0, 1))))
+    return rc;
+  HIPCHK(c, hipMemset(ints, 0, 4 * sizeof(int)));
+  a.status = ints;
+  a.stop = nullptr;
+  a.stop_mirror = nullptr;
+  a.S = c->xp_S;
+  a.ldx = ldx; a.ldy = ldy; a.p = c->p; a.q = c->q; a.r = s.r; a.rx = s.rx; a.ry = s.ry;
+  a.N = (double)c->n_total; a.ssqX = c->ssq_host[0]; a.ssqY = c->ssq_host[1]; a.atol = 0.0;
+  if ((rc = po2_upload_side(c, th->W, s.r, th->Wo, s.rx, c->p, ldx, a.Gx))) return rc;
+  if ((rc = po2_upload_side(c, th->C, s.r, th->Co, s.ry, c->q, ldy, a.Gy))) return rc;
+  po2_pack_scalars(th, s, &d.hsc);
+  HIPCHK(c, hipMemcpy(a.sc, &d.hsc, sizeof d.hsc, hipMemcpyHostToDevice));
+  if (keep_copy) {
+    HIPCHK(c, hipMemcpy(d.Gx0, a.Gx, sizeof(double) * ldx * s.kx, hipMemcpyDeviceToDevice));
+    HIPCHK(c, hipMemcpy(d.Gy0, a.Gy, sizeof(double) * ldy * s.ky, hipMemcpyDeviceToDevice));
+    HIPCHK(c, hipMemcpy(d.sc0, a.sc, sizeof d.hsc, hipMemcpyDeviceToDevice));
+  }
+  // rows of S per wave: the tile kernel's rule at the wider panel (option xprod_rw forces it where it fits)
+  const int wmax = std::max(s.kx, s.ky);
+  d.rw = ppls_xprod_tile_rows(P, wmax, c->xprod_rw, c->num_cus);
+  return PPLS_OK;
+}
+
+// M = S G by the two panels (X columns with Gx, Y columns with Gy): one read of S.
+int po2_panels(ppls_ctx* c, const PplsPo2Args& a, int kx, int ky, int rw) {
+  const int P = a.ldx + a.ldy;
+  HIPCHK(c, ppls_launch_po2_panel(a.S, P, 0, a.ldx, a.Gx, a.ldx, kx, rw, a.M, a.stop, c->stream));
+  HIPCHK(c, ppls_launch_po2_panel(a.S, P, a.ldx, a.ldy, a.Gy, a.ldy, ky, rw, a.M + (size_t)kx * P, a.stop, c->stream));
+  return PPLS_OK;
+}
+
+int po2_pass(ppls_ctx* c, Po2Dev& d, const Po2Shape& s) {
+  int rc;
+  if ((rc = po2_panels(c, d.a, s.kx, s.ky, d.rw))) return rc;
+  HIPCHK(c, ppls_launch_po2_gram(&d.a, c->stream));
+  return PPLS_OK;
+}
+
+int po2_status(ppls_ctx* c, const Po2Dev& d) {
+  int st = 0;
+  HIPCHK(c, hipMemcpy(&st, d.a.status, sizeof st, hipMemcpyDeviceToHost));
+  switch (st) {
+    case 0: return PPLS_OK;
+    case PPLS_PO2_ST_SIGMA: return fail(c, PPLS_E_NUMERIC, "PO2PLS: a sigma is not finite and above 0 (status %d)", st);
+    case PPLS_PO2_ST_LAMBDA: return fail(c, PPLS_E_NUMERIC, "PO2PLS: Lambda = Sigma_z^-1 + D G'G is not positive definite (status %d)", st);
+    case PPLS_PO2_ST_VAR: return fail(c, PPLS_E_NUMERIC, "PO2PLS: an updated variance is not finite and above 0 (status %d)", st);
+    default: return fail(c, PPLS_E_NUMERIC, "PO2PLS: rank-deficient loading update (status %d)", st);
+  }
+}
+
+void po2_block(const std::vector<double>& Z, int k, int r0, int nr, int c0, int nc, double* out) {
+  if (!out) return;
+  for (int j = 0; j < nc; ++j)
+    for (int i = 0; i < nr; ++i) out[(size_t)j * nr + i] = Z[(size_t)(c0 + j) * k + r0 + i];
+}
+
+// The moment blocks of *sm; with M (P x k, device) also C_dz = M K / N.
+int po2_expect_out(ppls_ctx* c, const PplsPo2Args& a, const Po2Shape& s, bool with_M, ppls_po2_expect* out) {
+  if (!out) return PPLS_OK;
+  std::vector<PplsPo2Small> hv(1);
+  PplsPo2Small& h = hv[0];
+  HIPCHK(c, hipMemcpy(&h, a.sm, sizeof h, hipMemcpyDeviceToHost));
+  const int k = s.k, r = s.r, kx = s.kx;
+  std::vector<double> Z(h.Czz, h.Czz + (size_t)k * k);
+  po2_block(Z, k, 0, r, 0, r, out->Ctt);
+  po2_block(Z, k, r, s.rx, r, s.rx, out->Ctoto);
+  po2_block(Z, k, 0, r, r, s.rx, out->Ctto);
+  po2_block(Z, k, kx, r, kx, r, out->Cuu);
+  po2_block(Z, k, kx + r, s.ry, kx + r, s.ry, out->Cuouo);
+  po2_block(Z, k, kx, r, kx + r, s.ry, out->Cuuo);
+  po2_block(Z, k, kx, r, 0, r, out->Cut);
+  if (out->Chh) std::copy(h.Chh, h.Chh + (size_t)r * r, out->Chh);
+  if (out->K) std::copy(h.K, h.K + (size_t)k * k, out->K);
+  out->Cee = h.Cee;
+  out->Cff = h.Cff;
+  if (with_M && (out->Cxt || out->Cxto || out->Cyu || out->Cyuo)) {
+    const int P = a.ldx + a.ldy;
+    std::vector<double> M((size_t)P * k);
+    HIPCHK(c, hipMemcpy(M.data(), a.M, sizeof(double) * M.size(), hipMemcpyDeviceToHost));
+    auto cdz = [&](int row0, int rows, int col0, int cols, double* o) {
+      if (!o) return;
+      for (int j = 0; j < cols; ++j)
+        for (int i = 0; i < rows; ++i) {
+          double acc = 0.0;
+          for (int m = 0; m < k; ++m) acc += M[(size_t)m * P + row0 + i] * h.K[(size_t)(col0 + j) * k + m];
+          o[(size_t)j * rows + i] = acc / a.N;
+        }
+    };
+    cdz(0, a.p, 0, r, out->Cxt);
+    cdz(0, a.p, r, s.rx, out->Cxto);
+    cdz(a.ldx, a.q, kx, r, out->Cyu);
+    cdz(a.ldx, a.q, kx + r, s.ry, out->Cyuo);
+  }
+  return PPLS_OK;
+}
+
+// What every fitting entry needs: data, no open stream, a usable S (formed and kept on resident rows).
+int po2_ready(ppls_ctx* c) {
+  int rc;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  if (c->st_state == 1) return fail(c, PPLS_E_STATE, "a stream is open: call ppls_stream_end first");
+  if ((rc = check_fit_data(c))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return o2m_ready(c);
+}
+
+// Theta on the host in the ABI's layout (owned buffers), read back from the device's padded columns.
+struct Po2Host {
+  std::vector<double> W, Wo, C, Co, B, T, To, Uo;
+  PplsPo2Scalars hs{};
+  ppls_po2_theta view() {
+    return {W.data(), Wo.data(), C.data(), Co.data(), B.data(), T.data(), To.data(), Uo.data(), hs.sE, hs.sF, hs.sH};
+  }
+};
+
+// The device's theta of d into h; PPLS_E_NUMERIC if any of it is not finite (`after`: for the message).
+int po2_pull(ppls_ctx* c, const Po2Dev& d, const Po2Shape& s, Po2Host& h, const char* after) {
+  const int p = c->p, q = c->q, ldx = c->ldx, ldy = c->ldy;
+  std::vector<double> gx((size_t)ldx * s.kx), gy((size_t)ldy * s.ky);
+  PplsPo2Scalars& hs = h.hs;
+  HIPCHK(c, hipMemcpy(gx.data(), d.a.Gx, sizeof(double) * gx.size(), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(gy.data(), d.a.Gy, sizeof(double) * gy.size(), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(&hs, d.a.sc, sizeof hs, hipMemcpyDeviceToHost));
+  bool fin = std::isfinite(hs.sE) && std::isfinite(hs.sF) && std::isfinite(hs.sH);
+  for (double v : gx) fin = fin && std::isfinite(v);
+  for (double v : gy) fin = fin && std::isfinite(v);
+  for (int j = 0; j < PPLS_RMAX; ++j) fin = fin && std::isfinite(hs.b[j]) && std::isfinite(hs.sT[j]) && std::isfinite(hs.sTo[j]) && std::isfinite(hs.sUo[j]);
+  if (!fin) return fail(c, PPLS_E_NUMERIC, "PO2PLS: non-finite estimates after %s", after);
+  h.W.assign((size_t)p * s.r, 0.0); h.Wo.assign((size_t)p * std::max(s.rx, 1), 0.0);
+  h.C.assign((size_t)q * s.r, 0.0); h.Co.assign((size_t)q * std::max(s.ry, 1), 0.0);
+  h.B.assign(s.r, 0.0); h.T.assign(s.r, 0.0); h.To.assign(std::max(s.rx, 1), 0.0); h.Uo.assign(std::max(s.ry, 1), 0.0);
+  for (int j = 0; j < s.r; ++j) {
+    std::copy(gx.begin() + (size_t)j * ldx, gx.begin() + (size_t)j * ldx + p, h.W.begin() + (size_t)j * p);
+    std::copy(gy.begin() + (size_t)j * ldy, gy.begin() + (size_t)j * ldy + q, h.C.begin() + (size_t)j * q);
+    h.B[j] = hs.b[j];
+    h.T[j] = hs.sT[j];
+  }
+  for (int j = 0; j < s.rx; ++j) {
+    std::copy(gx.begin() + (size_t)(s.r + j) * ldx, gx.begin() + (size_t)(s.r + j) * ldx + p, h.Wo.begin() + (size_t)j * p);
+    h.To[j] = hs.sTo[j];
+  }
+  for (int j = 0; j < s.ry; ++j) {
+    std::copy(gy.begin() + (size_t)(s.r + j) * ldy, gy.begin() + (size_t)(s.r + j) * ldy + q, h.Co.begin() + (size_t)j * q);
+    h.Uo[j] = hs.sUo[j];
+  }
+  return PPLS_OK;
+}
+
+// Theta h into the caller's buffers.
+void po2_give(const Po2Host& h, const Po2Shape& s, int p, int q, ppls_po2_theta* th) {
+  std::copy(h.W.begin(), h.W.end(), th->W);
+  std::copy(h.C.begin(), h.C.end(), th->C);
+  if (s.rx) std::copy(h.Wo.begin(), h.Wo.begin() + (size_t)p * s.rx, th->Wo);
+  if (s.ry) std::copy(h.Co.begin(), h.Co.begin() + (size_t)q * s.ry, th->Co);
+  for (int j = 0; j < s.r; ++j) { th->B[j] = h.B[j]; th->sigT[j] = h.T[j]; }
+  for (int j = 0; j < s.rx; ++j) th->sigTo[j] = h.To[j];
+  for (int j = 0; j < s.ry; ++j) th->sigUo[j] = h.Uo[j];
+  th->sigE = h.hs.sE; th->sigF = h.hs.sF; th->sigH = h.hs.sH;
+}
+
+// One E-step at theta on scratch that is set up already (its stop flag detached): theta up, pass, Gram,
+// small kernel (mode 0) into loglik[0], status.
+int po2_estep_again(ppls_ctx* c, Po2Dev& d, const ppls_po2_theta* th, const Po2Shape& s) {
+  int rc;
+  d.a.stop = nullptr;
+  d.a.stop_mirror = nullptr;
+  if ((rc = po2_upload_side(c, th->W, s.r, th->Wo, s.rx, c->p, c->ldx, d.a.Gx))) return rc;
+  if ((rc = po2_upload_side(c, th->C, s.r, th->Co, s.ry, c->q, c->ldy, d.a.Gy))) return rc;
+  po2_pack_scalars(th, s, &d.hsc);
+  HIPCHK(c, hipMemcpy(d.a.sc, &d.hsc, sizeof d.hsc, hipMemcpyHostToDevice));
+  if ((rc = po2_pass(c, d, s))) return rc;
+  HIPCHK(c, ppls_launch_po2_small(&d.a, 1, 0, 0, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return po2_status(c, d);
+}
+
+// One E-step at theta: pass, Gram, small kernel (mode 0), status.
+int po2_estep_core(ppls_ctx* c, Po2Dev& d, const ppls_po2_theta* th, const Po2Shape& s) {
+  int rc;
+  if ((rc = po2_setup(c, d, th, s, 1, false))) return rc;
+  if ((rc = po2_pass(c, d, s))) return rc;
+  HIPCHK(c, ppls_launch_po2_small(&d.a, 1, 0, 0, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return po2_status(c, d);
+}
+
+// Canonical form: the joint part by PPLS_simult's rule (:794-799), the specific components by decreasing
+// sigma (stable), each column's sign so that its sum is >= 0.
+void po2_canonical(ppls_po2_theta* th, const Po2Shape& s, int p, int q) {
+  ppls_theta joint = {th->W, th->C, th->B, th->sigT, th->sigE, th->sigF, th->sigH};
+  canonicalize(&joint, p, q, s.r);
+  auto spec = [](double* L, double* sig, int rows, int n) {
+    if (n == 0) return;
+    std::vector<int> ord(n);
+    for (int j = 0; j < n; ++j) ord[j] = j;
+    std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return sig[x] > sig[y]; });
+    std::vector<double> L2((size_t)rows * n), s2(n);
+    for (int j = 0; j < n; ++j) {
+      double sum = 0.0;
+      for (int i = 0; i < rows; ++i) sum += L[(size_t)ord[j] * rows + i];
+      const double sg = sum < 0.0 ? -1.0 : 1.0;
+      for (int i = 0; i < rows; ++i) L2[(size_t)j * rows + i] = sg * L[(size_t)ord[j] * rows + i];
+      s2[j] = sig[ord[j]];
+    }
+    std::copy(L2.begin(), L2.end(), L);
+    std::copy(s2.begin(), s2.end(), sig);
+  };
+  spec(th->Wo, th->sigTo, p, s.rx);
+  spec(th->Co, th->sigUo, q, s.ry);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ppls_po2_estep(ppls_ctx* c, const ppls_po2_theta* th, int r, int rx, int ry, ppls_po2_expect* out) {
+  if (!c) return PPLS_E_ARG;
+  if (!out) return fail(c, PPLS_E_ARG, "NULL argument");
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  int rc;
+  Po2Shape s;
+  if ((rc = po2_shape(c, r, rx, ry, c->p, c->q, &s)) || (rc = po2_check_theta(c, th, s, c->p, c->q))) return rc;
+  if ((rc = po2_ready(c))) return rc;
+  Po2Dev d;
+  if ((rc = po2_estep_core(c, d, th, s))) return rc;
+  return po2_expect_out(c, d.a, s, true, out);
+}
+
+int ppls_po2_loglik(ppls_ctx* c, const ppls_po2_theta* th, int r, int rx, int ry, double* out) {
+  if (!c) return PPLS_E_ARG;
+  if (!out) return fail(c, PPLS_E_ARG, "NULL argument");
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  int rc;
+  Po2Shape s;
+  if ((rc = po2_shape(c, r, rx, ry, c->p, c->q, &s)) || (rc = po2_check_theta(c, th, s, c->p, c->q))) return rc;
+  if ((rc = po2_ready(c))) return rc;
+  Po2Dev d;
+  if ((rc = po2_estep_core(c, d, th, s))) return rc;
+  HIPCHK(c, hipMemcpy(out, d.a.loglik, sizeof(double), hipMemcpyDeviceToHost));
+  return PPLS_OK;
+}
+
+int ppls_po2_em_run(ppls_ctx* c, ppls_po2_theta* th, int r, int rx, int ry, int max_steps, double atol, int type,
+                    double* loglik, int cap, int* n_loglik, int* negative_increment, ppls_po2_expect* eout) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  int rc;
+  Po2Shape s;
+  if ((rc = po2_shape(c, r, rx, ry, c->p, c->q, &s)) || (rc = po2_check_theta(c, th, s, c->p, c->q))) return rc;
+  if (max_steps < 1) return fail(c, PPLS_E_ARG, "EMsteps must be >= 1");
+  if (type != PPLS_ORTH_SVD && type != PPLS_ORTH_QR) return fail(c, PPLS_E_ARG, "type must be SVD (0) or QR (1)");
+  if (cap < 0 || (cap > 0 && !loglik) || std::isnan(atol)) return fail(c, PPLS_E_ARG, "bad loglik buffer or atol");
+  if ((rc = po2_ready(c))) return rc;
+  const int p = c->p, q = c->q;
+  Po2Dev d;
+  if ((rc = po2_setup(c, d, th, s, max_steps + 2, false))) return rc;
+  const bool do_check = !(atol == -INFINITY);
+  if ((rc = ensure_stop(c)) || (rc = reset_stop(c))) return rc;
+  d.a.stop = c->stop_d;
+  d.a.stop_mirror = c->stop_mirror_dev;
+  d.a.atol = atol;
+  d.a.type = type;
+  struct EvGuard {
+    std::vector<hipEvent_t> evs;
+    ~EvGuard() {
+      for (auto e : evs) (void)hipEventDestroy(e);
+    }
+  } guard;
+  constexpr int LOOKAHEAD = 8;   // as ppls_em_run: the host stays at most this many passes ahead of the flag
+  for (int i = 1; i <= max_steps + 1; ++i) {
+    if (i > LOOKAHEAD) {
+      HIPCHK(c, hipEventSynchronize(guard.evs[(size_t)(i - 1 - LOOKAHEAD) % LOOKAHEAD]));
+      if (__atomic_load_n(c->stop_mirror, __ATOMIC_ACQUIRE) != 0) break;
+    }
+    const bool last = i == max_steps + 1;
+    if ((rc = po2_pass(c, d, s))) return rc;
+    HIPCHK(c, ppls_launch_po2_small(&d.a, i, last ? 0 : 1, do_check ? 1 : 0, c->stream));
+    if (!last) HIPCHK(c, ppls_launch_po2_update(&d.a, c->stream));
+    const size_t e = (size_t)(i - 1) % LOOKAHEAD;
+    if (guard.evs.size() <= e) {
+      hipEvent_t ev;
+      HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      guard.evs.push_back(ev);
+    }
+    HIPCHK(c, hipEventRecord(guard.evs[e], c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if ((rc = po2_status(c, d))) return rc;
+  int stopv[2] = {0, 0};
+  HIPCHK(c, hipMemcpy(stopv, c->stop_d, sizeof stopv, hipMemcpyDeviceToHost));
+  const int npass = stopv[0] > 0 ? stopv[0] : max_steps + 1;   // passes run = entries of the history
+  if (stopv[1])
+    return fail(c, PPLS_E_NUMERIC, "PO2PLS: the log-likelihood increment of EM iteration %d is NaN", npass - 1);
+  std::vector<double> l((size_t)npass);
+  HIPCHK(c, hipMemcpy(l.data(), d.a.loglik, sizeof(double) * npass, hipMemcpyDeviceToHost));
+  for (int i = 0; i < npass; ++i)
+    if (!std::isfinite(l[i])) return fail(c, PPLS_E_NUMERIC, "PO2PLS: non-finite log-likelihood %g at pass %d", l[i], i + 1);
+  // the estimates, in canonical form.  The moments of the last pass belong to them as the device holds them;
+  // the canonical form permutes and flips latent coordinates, so Expectations come from one more E-step at
+  // the canonical estimates, on the same scratch
+  Po2Host h;
+  char after[48];
+  snprintf(after, sizeof after, "%d EM iterations", npass - 1);
+  if ((rc = po2_pull(c, d, s, h, after))) return rc;
+  ppls_po2_theta est = h.view();
+  po2_canonical(&est, s, p, q);
+  h.hs.sE = est.sigE; h.hs.sF = est.sigF; h.hs.sH = est.sigH;
+  if (eout) {
+    if ((rc = po2_estep_again(c, d, &est, s))) return rc;
+    if ((rc = po2_expect_out(c, d.a, s, true, eout))) return rc;
+  }
+  po2_give(h, s, p, q, th);
+  for (int i = 0; i < npass && i < cap; ++i) loglik[i] = l[i];
+  if (n_loglik) *n_loglik = npass;
+  if (negative_increment) {
+    int neg = 0;
+    for (int i = 1; i < npass; ++i) neg |= (l[i] - l[i - 1] < 0);
+    *negative_increment = neg;
+  }
+  return PPLS_OK;
+}
+
+int ppls_po2_start(ppls_ctx* c, int r, int rx, int ry, const double* V0x, const double* V0y, int steps, ppls_po2_theta* out) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  int rc;
+  Po2Shape s;
+  if ((rc = po2_shape(c, r, rx, ry, c->p, c->q, &s))) return rc;
+  if (!out || !out->W || !out->C || !out->B || !out->sigT || (rx && (!out->Wo || !out->sigTo || !V0x)) ||
+      (ry && (!out->Co || !out->sigUo || !V0y)))
+    return fail(c, PPLS_E_ARG, "NULL argument");
+  if (steps < 0) return fail(c, PPLS_E_ARG, "steps must be >= 0");
+  const int p = c->p, q = c->q;
+  for (size_t e = 0; e < (size_t)p * rx; ++e)
+    if (!std::isfinite(V0x[e])) return fail(c, PPLS_E_ARG, "V0x has non-finite entries");
+  for (size_t e = 0; e < (size_t)q * ry; ++e)
+    if (!std::isfinite(V0y[e])) return fail(c, PPLS_E_ARG, "V0y has non-finite entries");
+  if ((rc = po2_ready(c))) return rc;
+  // the joint part: the 'o2m_xprod' sequential fit, one EM step per component (more steps of the
+  // shared-only model pull a joint loading towards the strongest X-only direction)
+  // The sequential fit keeps its state in its context (ensure_r: the loadings of an ppls_em_begin session, the
+  // 'o2m_xprod' record), so it runs on a context of this call that holds a copy of S and nothing else: c's
+  // session, options and records stay as they are.
+  std::vector<double> W((size_t)p * r), C((size_t)q * r), B(r), sig((size_t)r * 4);
+  ppls_seq_fit f = {W.data(), C.data(), B.data(), sig.data(), nullptr, nullptr, nullptr, nullptr, 0, 0};
+  {
+    struct Tmp {
+      ppls_ctx* t = nullptr;
+      ~Tmp() { ppls_ctx_destroy(t); }
+    } tmp;
+    const int Pj = c->ldx + c->ldy;
+    if ((rc = ppls_ctx_create(c->device, &tmp.t))) return fail(c, rc, "PO2PLS start: no scratch context");
+    ppls_ctx* t = tmp.t;
+    DevGuard Snew;
+    if ((rc = dalloc(t, &Snew.p, (size_t)Pj * Pj))) return fail(c, rc, "PO2PLS start: %s", t->err.c_str());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    rc = derived_begin(t, "PO2PLS start", "the source's", c->dtype, c->ldpad, p, q, c->ldx, c->ldy, Snew, false);
+    if (!rc) {
+      hipError_t e = hipMemcpy(t->xp_S, c->xp_S, sizeof(double) * Pj * Pj, hipMemcpyDeviceToDevice);
+      if (e == hipSuccess) e = hipMemcpy(t->ssq, c->ssq_host, sizeof c->ssq_host, hipMemcpyHostToDevice);
+      if (e != hipSuccess) rc = fail(t, PPLS_E_HIP, "copy of S: %s", hipGetErrorString(e));
+    }
+    if (rc) return fail(c, rc, "PO2PLS start: %s", t->err.c_str());
+    t->ssq_host[0] = c->ssq_host[0];
+    t->ssq_host[1] = c->ssq_host[1];
+    t->o2m_path = c->o2m_path;
+    t->xprod_rw = c->xprod_rw;
+    derived_publish(t, c->n_total, c->mem_free_min);
+    if ((rc = ppls_ppls_o2m(t, r, 1, 1e-4, 0, nullptr, &f))) return fail(c, rc, "PO2PLS start, joint fit: %s", t->err.c_str());
+  }
+  if (f.ncomp < r) return fail(c, PPLS_E_NUMERIC, "PO2PLS start: the joint fit stopped after %d of %d components", f.ncomp, r);
+  // the specific parts: orthogonal iteration on (I - P_W) S_xx (I - P_W) and (I - P_C) S_yy (I - P_C), both
+  // sides in one pass over S per step (the panel kernel); the p x rx projection and QR run on the host
+  const int ldx = c->ldx, ldy = c->ldy, P = ldx + ldy, wx = std::max(rx, 1), wy = std::max(ry, 1);
+  struct Side {
+    int n, w, ld;
+    std::vector<double> Qb, V, A, sg;
+  } sd[2] = {{p, rx, ldx, {}, {}, {}, {}}, {q, ry, ldy, {}, {}, {}, {}}};
+  auto project_orth = [&](Side& t, const double* src) -> int {   // V <- orth((I - Qb Qb') src)
+    if (t.w == 0) return PPLS_OK;
+    const int jr = r;
+    std::vector<double> Z(src, src + (size_t)t.n * t.w);
+    for (int j = 0; j < t.w; ++j)
+      for (int m = 0; m < jr; ++m) {
+        const double d = hdot(&t.Qb[(size_t)m * t.n], &Z[(size_t)j * t.n], t.n);
+        for (int i = 0; i < t.n; ++i) Z[(size_t)j * t.n + i] -= d * t.Qb[(size_t)m * t.n + i];
+      }
+    t.V.resize(Z.size());
+    if (host_orth(Z.data(), t.n, t.w, PPLS_ORTH_QR, t.V.data()) != PPLS_OK)
+      return fail(c, PPLS_E_NUMERIC, "PO2PLS start: rank-deficient specific block");
+    return PPLS_OK;
+  };
+  for (int m = 0; m < 2; ++m) {
+    Side& t = sd[m];
+    t.Qb.resize((size_t)t.n * r);
+    if (host_orth(m ? C.data() : W.data(), t.n, r, PPLS_ORTH_QR, t.Qb.data()) != PPLS_OK)
+      return fail(c, PPLS_E_NUMERIC, "PO2PLS start: rank-deficient joint loadings");
+    if ((rc = project_orth(t, m ? V0y : V0x))) return rc;
+    t.sg.assign(t.w, 0.0);
+  }
+  CvScratch tmp;
+  PplsPo2Args a{};
+  if ((rc = tmp.get(c, &a.Gx, (size_t)ldx * wx)) || (rc = tmp.get(c, &a.Gy, (size_t)ldy * wy)) ||
+      (rc = tmp.get(c, &a.M, (size_t)P * (wx + wy))))
+    return rc;
+  a.S = c->xp_S; a.ldx = ldx; a.ldy = ldy;
+  const int rw = ppls_xprod_tile_rows(P, std::max(wx, wy), c->xprod_rw, c->num_cus);
+  std::vector<double> hx((size_t)ldx * wx, 0.0), hy((size_t)ldy * wy, 0.0), hM((size_t)P * (wx + wy));
+  for (int it = 0; it <= steps && (rx || ry); ++it) {   // the last pass gives V'S V alone; a side without columns is not launched
+    for (int j = 0; j < rx; ++j) std::copy(&sd[0].V[(size_t)j * p], &sd[0].V[(size_t)j * p] + p, &hx[(size_t)j * ldx]);
+    for (int j = 0; j < ry; ++j) std::copy(&sd[1].V[(size_t)j * q], &sd[1].V[(size_t)j * q] + q, &hy[(size_t)j * ldy]);
+    HIPCHK(c, hipMemcpyAsync(a.Gx, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(a.Gy, hy.data(), sizeof(double) * hy.size(), hipMemcpyHostToDevice, c->stream));
+    if (rx) HIPCHK(c, ppls_launch_po2_panel(a.S, P, 0, ldx, a.Gx, ldx, wx, rw, a.M, nullptr, c->stream));
+    if (ry) HIPCHK(c, ppls_launch_po2_panel(a.S, P, ldx, ldy, a.Gy, ldy, wy, rw, a.M + (size_t)wx * P, nullptr, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hM.data(), a.M, sizeof(double) * hM.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int m = 0; m < 2; ++m) {
+      Side& t = sd[m];
+      if (t.w == 0) continue;
+      t.A.resize((size_t)t.n * t.w);
+      for (int j = 0; j < t.w; ++j)   // S_xx V: the X rows of the X panel; S_yy V: the Y rows of the Y panel
+        std::copy(&hM[(size_t)((m ? wx : 0) + j) * P + (m ? ldx : 0)], &hM[(size_t)((m ? wx : 0) + j) * P + (m ? ldx : 0)] + t.n,
+                  &t.A[(size_t)j * t.n]);
+      if (it == steps) {
+        for (int j = 0; j < t.w; ++j) {
+          const double v = hdot(&t.V[(size_t)j * t.n], &t.A[(size_t)j * t.n], t.n) / (double)c->n_total;
+          if (!(v > 0.0) || !std::isfinite(v)) return fail(c, PPLS_E_NUMERIC, "PO2PLS start: a specific variance is not above 0");
+          t.sg[j] = std::sqrt(v);
+        }
+      } else if ((rc = project_orth(t, t.A.data()))) {
+        return rc;
+      }
+    }
+  }
+  std::copy(W.begin(), W.end(), out->W);
+  std::copy(C.begin(), C.end(), out->C);
+  for (int k = 0; k < r; ++k) {
+    out->B[k] = B[k];
+    out->sigT[k] = sig[(size_t)3 * r + k];
+  }
+  out->sigE = sig[(size_t)0 * r + r - 1];
+  out->sigF = sig[(size_t)1 * r + r - 1];
+  out->sigH = sig[(size_t)2 * r + r - 1];
+  if (rx) {
+    std::copy(sd[0].V.begin(), sd[0].V.end(), out->Wo);
+    std::copy(sd[0].sg.begin(), sd[0].sg.end(), out->sigTo);
+  }
+  if (ry) {
+    std::copy(sd[1].V.begin(), sd[1].V.end(), out->Co);
+    std::copy(sd[1].sg.begin(), sd[1].sg.end(), out->sigUo);
+  }
+  return PPLS_OK;
+}
+
+int ppls_po2_em_step(ppls_ctx* c, const ppls_po2_theta* th, int r, int rx, int ry, int type, ppls_po2_theta* out) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  int rc;
+  Po2Shape s;
+  if ((rc = po2_shape(c, r, rx, ry, c->p, c->q, &s)) || (rc = po2_check_theta(c, th, s, c->p, c->q))) return rc;
+  if (type != PPLS_ORTH_SVD && type != PPLS_ORTH_QR) return fail(c, PPLS_E_ARG, "type must be SVD (0) or QR (1)");
+  if (!out || !out->W || !out->C || !out->B || !out->sigT || (rx && (!out->Wo || !out->sigTo)) || (ry && (!out->Co || !out->sigUo)))
+    return fail(c, PPLS_E_ARG, "NULL argument");
+  if ((rc = po2_ready(c))) return rc;
+  Po2Dev d;
+  if ((rc = po2_setup(c, d, th, s, 1, false))) return rc;
+  d.a.type = type;
+  if ((rc = po2_pass(c, d, s))) return rc;
+  HIPCHK(c, ppls_launch_po2_small(&d.a, 1, 1, 0, c->stream));
+  HIPCHK(c, ppls_launch_po2_update(&d.a, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if ((rc = po2_status(c, d))) return rc;
+  Po2Host h;
+  if ((rc = po2_pull(c, d, s, h, "one ECM step"))) return rc;
+  po2_give(h, s, c->p, c->q, out);
+  return PPLS_OK;
+}
+
+int ppls_po2_stats(ppls_ctx* c, const double* S, int P, int ldx, const double* Gx, int kx, const double* Gy, int ky,
+                   int rw, double* M, double* Q, double* GG) {
+  if (!c) return PPLS_E_ARG;
+  if (!Gx || !Gy || !M || !Q || !GG) return fail(c, PPLS_E_ARG, "NULL argument");
+  if (kx < 1 || ky < 1 || kx > PPLS_RMAX || ky > PPLS_RMAX) return fail(c, PPLS_E_ARG, "widths kx=%d ky=%d outside [1,%d]", kx, ky, PPLS_RMAX);
+  const int ldy = P - ldx, k = kx + ky;
+  if (ldx < 2 || ldy < 2 || (ldx & 1) || (ldy & 1) || P >= (1 << 30)) return fail(c, PPLS_E_ARG, "bad layout P=%d ldx=%d", P, ldx);
+  const int wmax = std::max(kx, ky);
+  if (!(rw == 0 || rw == 1 || rw == 2 || rw == 4 || (rw == 8 && wmax <= 8))) return fail(c, PPLS_E_ARG, "rw=%d", rw);
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  const double* Sd = nullptr;
+  CvScratch tmp;
+  if (S) {
+    double* up = nullptr;
+    if ((rc = tmp.get(c, &up, (size_t)P * P))) return rc;
+    HIPCHK(c, hipMemcpy(up, S, sizeof(double) * P * P, hipMemcpyHostToDevice));
+    Sd = up;
+  } else {
+    if (!c->have_data || !c->xp_ready || !c->xp_S) return fail(c, PPLS_E_STATE, "no cross-products S are ready");
+    if (P != c->ldx + c->ldy || ldx != c->ldx) return fail(c, PPLS_E_ARG, "P=%d ldx=%d are not the context's %d, %d", P, ldx, c->ldx + c->ldy, c->ldx);
+    Sd = c->xp_S;
+  }
+  const size_t guard = 64, nM = (size_t)P * k, nQ = (size_t)k * k, nGx = (size_t)kx * kx, nGy = (size_t)ky * ky;
+  double *gxd = nullptr, *gyd = nullptr, *out = nullptr;
+  const size_t nout = nM + nQ + nGx + nGy + 5 * guard;
+  if ((rc = tmp.get(c, &gxd, (size_t)ldx * kx)) || (rc = tmp.get(c, &gyd, (size_t)ldy * ky)) || (rc = tmp.get(c, &out, nout))) return rc;
+  HIPCHK(c, hipMemcpy(gxd, Gx, sizeof(double) * ldx * kx, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(gyd, Gy, sizeof(double) * ldy * ky, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemsetAsync(out, 0xFF, sizeof(double) * nout, c->stream));
+  PplsPo2Args a{};
+  a.S = Sd; a.ldx = ldx; a.ldy = ldy; a.p = ldx; a.q = ldy; a.r = 1; a.rx = kx - 1; a.ry = ky - 1;
+  a.Gx = gxd; a.Gy = gyd;
+  a.M = out + guard;
+  a.Q = a.M + nM + guard;
+  a.GGx = a.Q + nQ + guard;
+  a.GGy = a.GGx + nGx + guard;
+  if (rw == 0) rw = ppls_xprod_tile_rows(P, wmax, c->xprod_rw, c->num_cus);
+  if (rw == 8 && wmax > 8) rw = 4;
+  if ((rc = po2_panels(c, a, kx, ky, rw))) return rc;
+  HIPCHK(c, ppls_launch_po2_gram(&a, c->stream));
+  std::vector<double> h(nout);
+  HIPCHK(c, hipMemcpyAsync(h.data(), out, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t offs[5] = {0, guard + nM, 2 * guard + nM + nQ, 3 * guard + nM + nQ + nGx, 4 * guard + nM + nQ + nGx + nGy};
+  for (size_t o : offs)
+    for (size_t g = 0; g < guard; ++g)
+      if (!std::isnan(h[o + g])) return fail(c, PPLS_E_NUMERIC, "a PO2 statistics kernel wrote outside its output");
+  std::copy(h.begin() + guard, h.begin() + guard + nM, M);
+  std::copy(h.begin() + offs[1] + guard, h.begin() + offs[1] + guard + nQ, Q);
+  std::copy(h.begin() + offs[2] + guard, h.begin() + offs[2] + guard + nGx, GG);
+  std::copy(h.begin() + offs[3] + guard, h.begin() + offs[3] + guard + nGy, GG + nGx);
+  return PPLS_OK;
+}
+
+int ppls_po2_small(ppls_ctx* c, const double* Q, const double* GG, const ppls_po2_theta* th, int r, int rx, int ry, int p,
+                   int q, double N, double ssqX, double ssqY, ppls_po2_expect* out, double* loglik, int* status) {
+  if (!c) return PPLS_E_ARG;
+  if (!Q || !GG) return fail(c, PPLS_E_ARG, "NULL argument");
+  int rc;
+  Po2Shape s;
+  if ((rc = po2_shape(c, r, rx, ry, p, q, &s))) return rc;
+  if (!th || !th->B || !th->sigT || (rx && !th->sigTo) || (ry && !th->sigUo)) return fail(c, PPLS_E_ARG, "NULL argument");
+  if (!(N > 0.0)) return fail(c, PPLS_E_ARG, "N must be above 0");
+  HIPCHK(c, hipSetDevice(c->device));
+  CvScratch tmp;
+  PplsPo2Args a{};
+  int* ints = nullptr;
+  const size_t nQ = (size_t)s.k * s.k, nGx = (size_t)s.kx * s.kx, nGy = (size_t)s.ky * s.ky;
+  if ((rc = tmp.get(c, &a.Q, nQ)) || (rc = tmp.get(c, &a.GGx, nGx)) || (rc = tmp.get(c, &a.GGy, nGy)) || (rc = tmp.get(c, &a.sc, 1)) ||
+      (rc = tmp.get(c, &a.sm, 1)) || (rc = tmp.get(c, &a.loglik, 1)) || (rc = tmp.get(c, &ints, 4)))
+    return rc;
+  PplsPo2Scalars hs;
+  po2_pack_scalars(th, s, &hs);
+  HIPCHK(c, hipMemcpy(a.Q, Q, sizeof(double) * nQ, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(a.GGx, GG, sizeof(double) * nGx, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(a.GGy, GG + nGx, sizeof(double) * nGy, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(a.sc, &hs, sizeof hs, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemset(ints, 0, 4 * sizeof(int)));
+  a.status = ints;
+  a.p = p; a.q = q; a.r = r; a.rx = rx; a.ry = ry; a.N = N; a.ssqX = ssqX; a.ssqY = ssqY;
+  HIPCHK(c, ppls_launch_po2_small(&a, 1, 0, 0, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int st = 0;
+  HIPCHK(c, hipMemcpy(&st, ints, sizeof st, hipMemcpyDeviceToHost));
+  if (status) *status = st;
+  if (st != 0) return fail(c, PPLS_E_NUMERIC, "PO2PLS small kernel: status %d", st);
+  if (loglik) HIPCHK(c, hipMemcpy(loglik, a.loglik, sizeof(double), hipMemcpyDeviceToHost));
+  return po2_expect_out(c, a, s, false, out);
+}
+
+int ppls_po2_timing(ppls_ctx* c, const ppls_po2_theta* th, int r, int rx, int ry, int reps, double* ms6) {
+  if (!c || !ms6 || reps < 1) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  int rc;
+  Po2Shape s;
+  if ((rc = po2_shape(c, r, rx, ry, c->p, c->q, &s)) || (rc = po2_check_theta(c, th, s, c->p, c->q))) return rc;
+  if ((rc = po2_ready(c))) return rc;
+  Po2Dev d;
+  if ((rc = po2_setup(c, d, th, s, 2, true))) return rc;
+  const size_t nx = sizeof(double) * c->ldx * s.kx, ny = sizeof(double) * c->ldy * s.ky;
+  auto restore = [&]() -> hipError_t {
+    hipError_t e = hipMemcpyAsync(d.a.Gx, d.Gx0, nx, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d.a.Gy, d.Gy0, ny, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d.a.sc, d.sc0, sizeof(PplsPo2Scalars), hipMemcpyDeviceToDevice, c->stream);
+    return e;
+  };
+  // warm every kernel once, then time each part reps times between two events
+  if ((rc = po2_pass(c, d, s))) return rc;
+  HIPCHK(c, ppls_launch_po2_small(&d.a, 1, 0, 0, c->stream));
+  for (int part = 0; part < 6; ++part) {
+    d.a.type = part == 5 ? PPLS_ORTH_QR : PPLS_ORTH_SVD;   // part 5: the update without the polar factor
+    HIPCHK(c, restore());
+    if ((rc = po2_pass(c, d, s))) return rc;
+    HIPCHK(c, ppls_launch_po2_small(&d.a, 1, 0, 0, c->stream));   // moments of theta for the update's inputs
+    CvEvents ev;
+    HIPCHK(c, ev.begin(c->stream));
+    for (int i = 0; i < reps; ++i) {
+      if (part == 0) { if ((rc = po2_panels(c, d.a, s.kx, s.ky, d.rw))) return rc; }
+      else if (part == 1) HIPCHK(c, ppls_launch_po2_gram(&d.a, c->stream));
+      else if (part == 2) HIPCHK(c, ppls_launch_po2_small(&d.a, 1, 0, 0, c->stream));
+      else if (part == 3 || part == 5) HIPCHK(c, ppls_launch_po2_update(&d.a, c->stream));   // the same M, K, Czz every launch
+      else {
+        if ((rc = po2_pass(c, d, s))) return rc;
+        HIPCHK(c, ppls_launch_po2_small(&d.a, 1, 1, 0, c->stream));
+        HIPCHK(c, ppls_launch_po2_update(&d.a, c->stream));
+      }
+    }
+    HIPCHK(c, ev.end(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ms6[part] = ev.ms() / reps;
+    if ((rc = po2_status(c, d))) return rc;
+  }
   return PPLS_OK;
 }
 
