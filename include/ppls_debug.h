@@ -40,6 +40,27 @@ int ppls_xprod_tile_timing(ppls_ctx* ctx, int reps, double* ms);
 /* One statistics step from S for theta: stats = [X'mu_T p x r | Y'mu_U q x r | Gram 2r x 2r], all
  * column-major, as ppls_finalize_host takes them (unit parity against the sweep and a host S B). */
 int ppls_xprod_stats(ppls_ctx* ctx, const ppls_theta* th, int r, double* stats);
+/* The pass of ppls_xprod_stats alone on a caller's inputs, through the launcher the EM loop uses: M = S
+ * blockdiag(W, C) (P x 2r column-major, padding rows included) and stats in the kernel's own padded layout
+ * [X'mu_T ldx x r | Y'mu_U ldy x r | Gram 2r x 2r], ldy = P - ldx.  S: host, row-major P x P with the X
+ * block ldx wide (ldx, ldy even, >= 2), uploaded around the launch -- or NULL for the S the context holds
+ * (P, ldx must then be its own); a context without data serves when S is given.  W (ldx x r) and C
+ * (ldy x r): host column-major, padding rows included.  alpha, beta, gamma, delta (r each) are written
+ * into the device scalars as given: no theta is involved.  1 <= r <= 16; rw rows of S per wave (1, 2, 4,
+ * 8 (r <= 8); 0 = what a fit takes); with_gram 0 leaves the Gram slot unwritten (the finalize forms it);
+ * stop: the value of the device stop flag the launch is given (1: both kernels return at once).  Every
+ * output is written between NaN guards, which are checked (PPLS_E_NUMERIC when one was written); what
+ * the launch did not write reads NaN.  *rw_used, *nt_used (nullable): the rows per wave and the
+ * instantiation (1 non-temporal, 0 cached) that ran.  Bad arguments are PPLS_E_ARG before any launch. */
+int ppls_xprod_pass(ppls_ctx* ctx, const double* S, int P, int ldx, const double* W, const double* C,
+                    const double* alpha, const double* beta, const double* gamma, const double* delta, int r, int rw,
+                    int with_gram, int stop, double* M, double* stats, int* rw_used, int* nt_used);
+/* Whether the tile kernel of that pass takes its non-temporal instantiation for a P x P matrix of doubles
+ * (1) or the cached one (0): 8 P^2 bytes against 200 MiB.  Host only; the launcher itself calls it. */
+int ppls_xprod_tile_nt(int P);
+/* Rows of S per wave of the tile kernel for r components on num_cus compute units (rw_opt 1, 2, 4 or 8
+ * (r <= 8) forces it; else 2 while P / 8 >= 2 num_cus, else 1).  Host only. */
+int ppls_xprod_tile_rows(int P, int r, int rw_opt, int num_cus);
 /* One statistics step by the sweep for theta, the twin of ppls_xprod_stats: the kernel is the one
  * ppls_sweep_kernel names under the context's current options; stats in the same layout.  want_mu:
  * the sweep also writes the moments (its waits then drain the DMA ring instead of counting), and mu

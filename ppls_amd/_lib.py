@@ -132,6 +132,10 @@ SIGNATURES = {
     "ppls_xprod_setup_times": (ct.c_int, [ct.c_void_p, _dp, _dp, _dp]),
     "ppls_xprod_tile_timing": (ct.c_int, [ct.c_void_p, ct.c_int, _dp]),
     "ppls_xprod_stats": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsTheta), ct.c_int, _dp]),
+    "ppls_xprod_pass": (ct.c_int, [ct.c_void_p, _dp, ct.c_int, ct.c_int, _dp, _dp, _dp, _dp, _dp, _dp, ct.c_int, ct.c_int,
+                                   ct.c_int, ct.c_int, _dp, _dp, ct.POINTER(ct.c_int), ct.POINTER(ct.c_int)]),
+    "ppls_xprod_tile_nt": (ct.c_int, [ct.c_int]),
+    "ppls_xprod_tile_rows": (ct.c_int, [ct.c_int, ct.c_int, ct.c_int, ct.c_int]),
     "ppls_sweep_stats": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsTheta), ct.c_int, ct.c_int, _dp, _dp]),
     "ppls_finalize_stats": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsTheta), ct.c_int, ct.c_int, ct.c_int, _dp, _dp, _dp,
                                        _dp, ct.c_int, ct.c_int, _dp, _dp, _dp, ct.POINTER(PplsExpect), _dp, _dp,

@@ -953,6 +953,35 @@ class Context:
         G = out[(self.p + self.q) * r:].reshape(2 * r, 2 * r).T
         return SX, SY, G
 
+    def xprod_pass(self, W, C, coef, S=None, rw=0, with_gram=True, stop=False):
+        """The cross-product statistics pass alone (``ppls_xprod_pass``): W (ldx x r) and C (ldy x r) with
+        their padding rows, coef = (alpha, beta, gamma, delta) of r values each, on a host S (row-major
+        P x P, X block ldx wide) or, S = None, on the context's own.  Returns a dict: M (P x 2r), SX
+        (ldx x r), SY (ldy x r) and G (2r x 2r) as the kernels left them (NaN where nothing was written),
+        rw and nt (the rows per wave and the instantiation that ran: 1 non-temporal, 0 cached)."""
+        W = np.asfortranarray(np.array(W, dtype=np.float64, ndmin=2))
+        C = np.asfortranarray(np.array(C, dtype=np.float64, ndmin=2))
+        r = W.shape[1]
+        if C.shape[1] != r:
+            raise ValueError("W and C need the same number of components")
+        ldx, ldy = W.shape[0], C.shape[0]
+        P = ldx + ldy
+        cf = [np.ascontiguousarray(np.ravel(v), dtype=np.float64) for v in coef]
+        if len(cf) != 4 or any(v.size != r for v in cf):
+            raise ValueError("coef must be (alpha, beta, gamma, delta) of r values each")
+        if S is not None:
+            S = np.ascontiguousarray(S, dtype=np.float64)
+            if S.shape != (P, P):
+                raise ValueError(f"S must be {P} x {P}")
+        M, st = np.zeros((P, 2 * r), order="F"), np.zeros(P * r + 4 * r * r)
+        rwu, ntu = ct.c_int(), ct.c_int()
+        self._chk(self._L.ppls_xprod_pass(self.h, dptr(S), P, ldx, dptr(W), dptr(C), dptr(cf[0]), dptr(cf[1]), dptr(cf[2]),
+                                          dptr(cf[3]), r, int(rw), int(bool(with_gram)), int(bool(stop)), dptr(M), dptr(st),
+                                          ct.byref(rwu), ct.byref(ntu)))
+        return dict(M=M, SX=st[:ldx * r].reshape(ldx, r, order="F").copy(),
+                    SY=st[ldx * r:P * r].reshape(ldy, r, order="F").copy(),
+                    G=st[P * r:].reshape(2 * r, 2 * r, order="F").copy(), rw=rwu.value, nt=ntu.value)
+
     def sweep_stats(self, th: Theta, want_mu=False):
         """One statistics step by the sweep for theta (the kernel ``sweep_kernel(r)`` names, under the
         current options): (X'mu_T p x r, Y'mu_U q x r, Gram 2r x 2r, mu), mu = this rank's

@@ -8299,6 +8299,70 @@ int ppls_po2_stats(ppls_ctx* c, const double* S, int P, int ldx, const double* G
   return PPLS_OK;
 }
 
+// The PPLS_simult statistics pass alone (ppls_xprod.hip), the twin of ppls_po2_stats for the tile and Gram
+// kernels of xprod_stats(): the launch goes through ppls_launch_xprod_tile.
+int ppls_xprod_pass(ppls_ctx* c, const double* S, int P, int ldx, const double* W, const double* C, const double* alpha,
+                    const double* beta, const double* gamma, const double* delta, int r, int rw, int with_gram, int stop,
+                    double* M, double* stats, int* rw_used, int* nt_used) {
+  if (!c) return PPLS_E_ARG;
+  if (!W || !C || !alpha || !beta || !gamma || !delta || !M || !stats) return fail(c, PPLS_E_ARG, "NULL argument");
+  if (r < 1 || r > PPLS_RMAX) return fail(c, PPLS_E_ARG, "r=%d outside [1,%d]", r, PPLS_RMAX);
+  const int ldy = P - ldx;
+  if (ldx < 2 || ldy < 2 || (ldx & 1) || (ldy & 1) || P >= (1 << 30)) return fail(c, PPLS_E_ARG, "bad layout P=%d ldx=%d", P, ldx);
+  if (!(rw == 0 || rw == 1 || rw == 2 || rw == 4 || (rw == 8 && r <= 8))) return fail(c, PPLS_E_ARG, "rw=%d at r=%d", rw, r);
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  const double* Sd = nullptr;
+  CvScratch tmp;
+  if (S) {
+    double* up = nullptr;
+    if ((rc = tmp.get(c, &up, (size_t)P * P))) return rc;
+    HIPCHK(c, hipMemcpy(up, S, sizeof(double) * P * P, hipMemcpyHostToDevice));
+    Sd = up;
+  } else {
+    if (!c->have_data || !c->xp_ready || !c->xp_S) return fail(c, PPLS_E_STATE, "no cross-products S are ready");
+    if (P != c->ldx + c->ldy || ldx != c->ldx) return fail(c, PPLS_E_ARG, "P=%d ldx=%d are not the context's %d, %d", P, ldx, c->ldx + c->ldy, c->ldx);
+    Sd = c->xp_S;
+  }
+  const size_t guard = 64, nM = (size_t)P * 2 * r, nst = (size_t)P * r + (size_t)4 * r * r, nout = nM + nst + 3 * guard;
+  double *wd = nullptr, *cd = nullptr, *out = nullptr;
+  PplsScalars* scd = nullptr;
+  int* stopd = nullptr;
+  if ((rc = tmp.get(c, &wd, (size_t)ldx * r)) || (rc = tmp.get(c, &cd, (size_t)ldy * r)) || (rc = tmp.get(c, &out, nout)) ||
+      (rc = tmp.get(c, &scd, 1)) || (rc = tmp.get(c, &stopd, 2)))
+    return rc;
+  PplsScalars s;
+  memset(&s, 0, sizeof s);
+  for (int k = 0; k < r; ++k) {
+    s.alpha[k] = alpha[k];
+    s.beta[k] = beta[k];
+    s.gamma[k] = gamma[k];
+    s.delta[k] = delta[k];
+  }
+  const int hstop[2] = {stop ? 1 : 0, 0};
+  HIPCHK(c, hipMemcpy(wd, W, sizeof(double) * ldx * r, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(cd, C, sizeof(double) * ldy * r, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(scd, &s, sizeof s, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(stopd, hstop, sizeof hstop, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemsetAsync(out, 0xFF, sizeof(double) * nout, c->stream));
+  if (rw == 0) rw = ppls_xprod_tile_rows(P, r, c->xprod_rw, c->num_cus);
+  if (rw_used) *rw_used = rw;
+  if (nt_used) *nt_used = ppls_xprod_tile_nt(P);
+  double* Md = out + guard;
+  double* std_ = Md + nM + guard;
+  HIPCHK(c, ppls_launch_xprod_tile(Sd, ldx, ldy, r, rw, wd, cd, scd, std_, Md, stopd, with_gram ? 1 : 0, c->stream));
+  std::vector<double> h(nout);
+  HIPCHK(c, hipMemcpyAsync(h.data(), out, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t offs[3] = {0, guard + nM, 2 * guard + nM + nst};
+  for (size_t o : offs)
+    for (size_t g = 0; g < guard; ++g)
+      if (!std::isnan(h[o + g])) return fail(c, PPLS_E_NUMERIC, "a cross-product statistics kernel wrote outside its output");
+  std::copy(h.begin() + guard, h.begin() + guard + nM, M);
+  std::copy(h.begin() + offs[1] + guard, h.begin() + offs[1] + guard + nst, stats);
+  return PPLS_OK;
+}
+
 int ppls_po2_small(ppls_ctx* c, const double* Q, const double* GG, const ppls_po2_theta* th, int r, int rx, int ry, int p,
                    int q, double N, double ssqX, double ssqY, ppls_po2_expect* out, double* loglik, int* status) {
   if (!c) return PPLS_E_ARG;

@@ -30,6 +30,9 @@ hipError_t ppls_launch_gram_joint(const void* X, int ldx, int xcols, int xreal, 
 
 // Rows of S per wave of the tile kernel (rw_opt 1, 2, 4 or 8 (r <= 8) forces it; 0 = auto).
 int ppls_xprod_tile_rows(int P, int r, int rw_opt, int num_cus);
+// Whether the tile kernel takes its non-temporal instantiation for a P x P matrix of doubles (1) or the
+// cached one (0): 8 P^2 bytes against 200 MiB (the Infinity Cache holds 256 MiB).
+int ppls_xprod_tile_nt(int P);
 
 // One iteration's statistics from S (P x P row-major, P = ldx + ldy, symmetric) and theta = (Wp, Cp,
 // sc): stats = [X'mu_T (ldx x r) | Y'mu_U (ldy x r) | Gram (2r x 2r)], the layout the sweeps'

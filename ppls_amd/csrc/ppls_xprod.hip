@@ -148,7 +148,7 @@ hipError_t launch_tile(const double* S, int ldx, int ldy, const double* Wp, cons
   const int P = ldx + ldy;
   constexpr int NWV = ppls_xp_waves(R);
   const unsigned blocks = (unsigned)((P + NWV * RW - 1) / (NWV * RW));
-  if (8.0 * P * (double)P > 200.0 * (1 << 20))   // S beyond the Infinity Cache: non-temporal loads
+  if (ppls_xprod_tile_nt(P))   // S beyond the Infinity Cache: non-temporal loads
     hipLaunchKernelGGL((ppls_xprod_tile_kernel<R, RW, true>), dim3(blocks), dim3(64 * NWV), 0, st, S, ldx, ldy, Wp, Cp, sc,
                        stats, M, stop);
   else
@@ -176,6 +176,8 @@ int ppls_xprod_tile_rows(int P, int r, int rw_opt, int num_cus) {
   if (rw_opt == 1 || rw_opt == 2 || rw_opt == 4 || (rw_opt == 8 && r <= 8)) return rw_opt;
   return P / 8 >= 2 * num_cus ? 2 : 1;   // two rows per wave while >= 2 workgroups per CU remain
 }
+
+int ppls_xprod_tile_nt(int P) { return 8.0 * P * (double)P > 200.0 * (1 << 20) ? 1 : 0; }
 
 hipError_t ppls_launch_xprod_tile(const double* S, int ldx, int ldy, int r, int rw, const double* Wp,
                                   const double* Cp, const PplsScalars* sc, double* stats, double* M, const int* stop,
