@@ -821,6 +821,51 @@ int ppls_po2_em_run(ppls_ctx* ctx, ppls_po2_theta* th, int r, int rx, int ry, in
 int ppls_po2_start(ppls_ctx* ctx, int r, int rx, int ry, const double* V0x, const double* V0y, int steps,
                    ppls_po2_theta* theta_out);
 
+/* ---- choosing (r, rx, ry): batched fits, prediction, cross-validation ---------------
+ * ppls_po2_em_run for m models at once on the S the context holds (1 <= m <= 256; shapes may repeat,
+ * so restarts of one model are a batch too).  Every model runs ppls_po2_em_run's loop with its own stop
+ * rule: one that stops, or fails, freezes while the others go on, and model j's estimates, history and
+ * count are bit for bit those of ppls_po2_em_run(ctx, &th[j], r[j], rx[j], ry[j], ...) alone.  Per
+ * pass the models share the panel launches (their loading columns lie side by side: ceil(sum kx / 16)
+ * + ceil(sum ky / 16) launches for the whole batch) and one launch each of the Gram, the k x k algebra
+ * and the loading update; the device holds m (8 P k + 16 * 8 P) bytes plus small terms.
+ * th: m thetas, in: the starts, out: the estimates in canonical form.  loglik: m x cap, model-major
+ * (nullable with cap = 0); n_loglik, status: m; negative_increment: m, nullable.
+ * Every model and shape is validated before any device work, with ppls_po2_em_run's refusals and
+ * everything untouched.  Otherwise the call returns PPLS_OK and status[j] is PPLS_OK or
+ * PPLS_E_NUMERIC; for a failed model th[j] and row j of loglik are untouched, n_loglik[j] = 0, and
+ * ppls_last_error names the first failed model and its reason.  The context rules are
+ * ppls_po2_em_run's: no session is ended, no option changed, S is left bit for bit. */
+int ppls_po2_em_run_batch(ppls_ctx* ctx, int m, ppls_po2_theta* th, const int* r, const int* rx, const int* ry, int max_steps,
+                          double atol, int type, double* loglik, int cap, int* n_loglik, int* negative_increment,
+                          int* status);
+
+/* The linear map of the model's prediction (host only, no GPU), in the form ppls_predict and
+ * ppls_heldout_sse(_fold) take (their W need not be orthonormal):
+ *   xory = 0:  E[y | x] = C diag(B) E[t | x].  Lambda_x = diag(sigT, sigTo)^-2 + Gx'Gx / sigE^2, Gx = [W Wo];
+ *              L (p x r) = the first r columns of Gx Lambda_x^-1 / sigE^2, Bp = B:
+ *              ppls_predict(ctx, L, C, Bp, r, 0, ...) is the prediction of y.
+ *   xory = 1:  E[x | y] = W diag(beta) E[u | y], beta_j = sigT_j^2 b_j / (sigT_j^2 b_j^2 + sigH^2).
+ *              Lambda_y = diag(sigT^2 b^2 + sigH^2, sigUo^2)^-1 + Gy'Gy / sigF^2, Gy = [C Co];
+ *              L (q x r) = the first r columns of Gy Lambda_y^-1 / sigF^2, Bp = 1 / beta (the form
+ *              ppls_predict(xory = 1) divides by): ppls_predict(ctx, W, L, Bp, r, 1, ...).
+ * Lambda is factored by Cholesky on the host.  PPLS_E_ARG as for the other PO2 entries; PPLS_E_NUMERIC:
+ * Lambda not positive definite, or (xory = 1) a b_j that is 0.  L, Bp are written only on success. */
+int ppls_po2_predict_map(const ppls_po2_theta* th, int r, int rx, int ry, int p, int q, int xory, double* L, double* Bp);
+
+/* Cross-validated X -> Y prediction error of ncand candidate sizes on a context streamed with folds
+ * (anything else: PPLS_E_STATE, as ppls_cv_ppls_stream).  Per fold f: ppls_stream_select(f); per candidate
+ * the start ppls_po2_start gives on that selection from the leading rx / ry columns of V0x (p x max rx) /
+ * V0y (q x max ry); one ppls_po2_em_run_batch over the candidates; per fitted candidate
+ * ppls_po2_predict_map(xory = 0) and ppls_heldout_sse_fold(L, C, B, r, f):
+ * rmsep = sqrt(sse[r - 1] / (N_f q)), cond = mag / sse, steps = the EM iterations run.  All outputs
+ * nfolds x ncand, fold-major; cond, steps and fits (caller's buffers, written for fitted candidates) are
+ * nullable.  A failed start or fit gives NaN and its status (PPLS_E_NUMERIC).  The context ends selected
+ * on -1, also on an error return. */
+int ppls_po2_cv_stream(ppls_ctx* ctx, int ncand, const int* r, const int* rx, const int* ry, int max_steps, double atol,
+                       int type, const double* V0x, const double* V0y, int start_steps, double* rmsep, double* cond,
+                       int* steps, int* status, ppls_po2_theta* fits);
+
 /* ---- host-side algebra (no GPU; the same code the device finalize runs) ------------------------ */
 /* From the all-reduced sufficient statistics of one sweep with theta (stats = [X'mu_T p x r |
  * Y'mu_U q x r | Gram 2r x 2r], all column-major) compute Expect_M's moments, logl_W(theta) and

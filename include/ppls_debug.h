@@ -313,6 +313,20 @@ int ppls_po2_em_step(ppls_ctx* ctx, const ppls_po2_theta* th, int r, int rx, int
  * iteration, the loading update of the QR type -- the same work without the Jacobi polar factor}.
  * Theta on the device is restored between the parts; nothing of the context changes. */
 int ppls_po2_timing(ppls_ctx* ctx, const ppls_po2_theta* th, int r, int rx, int ry, int reps, double* ms6);
+/* The twin of ppls_po2_stats for the batched pass: m models' loadings side by side, Gx
+ * ldx x sum kx and Gy (P - ldx) x sum ky (host, column-major, padding rows included), through the shared
+ * panel launches in chunks of 16 columns and the batched Gram.  Outputs packed model after model:
+ * M (P x (kx_j + ky_j)), Q ((kx_j + ky_j)^2), GG ([kx_j^2 | ky_j^2]).  1 <= m <= 256; S as in
+ * ppls_po2_stats.  Every output lies between NaN fills, which are checked. */
+/* HIP-event times (ms per EM iteration: the mean over reps rounds of `steps` forced iterations each, after one
+ * untimed round) on the context's S for m models from their thetas: ms4 = {one batched iteration (shared panels, one
+ * Gram, small and update launch for all models), the same iteration of the m models one after another through the
+ * single-model launches, the batched pass alone (panels and Gram), the m single passes one after another}.  Device
+ * time only: no uploads, no read-back.  Nothing of the context changes. */
+int ppls_po2_timing_batch(ppls_ctx* ctx, int m, const ppls_po2_theta* th, const int* r, const int* rx, const int* ry,
+                          int steps, int reps, double* ms4);
+int ppls_po2_stats_batch(ppls_ctx* ctx, const double* S, int P, int ldx, int m, const int* kx, const int* ky,
+                         const double* Gx, const double* Gy, double* M, double* Q, double* GG);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,8 @@ from .api import (PPLS, Context, Expect_M, Maximiz_M, PPLS_simult, PPLS_simult_t
                   crossval_PPLS, scale_data, adjust_data, adjust_new, stream_data, fold_labels, population_labels, bootstrap_counts,
                   align_signs, bootstrap_summary, bootstrap_PPLS_simult, permutation_indices, permutation_pvalues,
                   permutation_PPLS, diagnostics_PPLS, robust_PPLS_simult, PO2PLS, PO2PLS_Expect, PO2PLS_logl,
-                  simulate_PO2PLS, scores_PO2PLS, summary_PO2PLS, canonical_PO2PLS)
+                  simulate_PO2PLS, scores_PO2PLS, summary_PO2PLS, canonical_PO2PLS, po2_predict_map, predict_PO2PLS,
+                  cv_PO2PLS, crossval_PO2PLS)
 
 __all__ = ["Context", "fconstraint", "Expect_M", "Maximiz_M", "PPLS_simult", "PPLS", "PPLSi", "initial_guess", "print_PPLS", "scores_PPLS",
            "PPLS_simult_to_o2m", "PPLS_to_o2m", "meta_EMstep", "meta_PPLSi", "variances_PPLS_simult", "logl_W", "loglC_fast", "Theta",
@@ -18,4 +19,5 @@ __all__ = ["Context", "fconstraint", "Expect_M", "Maximiz_M", "PPLS_simult", "PP
            "cv_blocks", "predict_PPLS", "cv_PPLS", "crossval_PPLS", "scale_data", "adjust_data", "adjust_new", "stream_data", "fold_labels", "population_labels",
            "bootstrap_counts", "align_signs", "bootstrap_summary", "bootstrap_PPLS_simult", "permutation_indices",
            "permutation_pvalues", "permutation_PPLS", "diagnostics_PPLS", "robust_PPLS_simult", "PO2PLS", "PO2PLS_Expect",
-           "PO2PLS_logl", "simulate_PO2PLS", "scores_PO2PLS", "summary_PO2PLS", "canonical_PO2PLS"]
+           "PO2PLS_logl", "simulate_PO2PLS", "scores_PO2PLS", "summary_PO2PLS", "canonical_PO2PLS", "po2_predict_map",
+           "predict_PO2PLS", "cv_PO2PLS", "crossval_PO2PLS"]

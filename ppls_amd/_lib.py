@@ -20,6 +20,7 @@ PPLS_LAYOUT_COLMAJOR = 0
 PPLS_LAYOUT_ROWMAJOR = 1
 
 _dp = ct.POINTER(ct.c_double)
+_ip = ct.POINTER(ct.c_int)
 
 
 class PplsTheta(ct.Structure):
@@ -248,6 +249,14 @@ SIGNATURES = {
                                   ct.c_int, ct.c_double, ct.c_double, ct.c_double, ct.POINTER(PplsPo2Expect), _dp,
                                   ct.POINTER(ct.c_int)]),
     "ppls_po2_timing": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsPo2Theta), ct.c_int, ct.c_int, ct.c_int, ct.c_int, _dp]),
+    "ppls_po2_em_run_batch": (ct.c_int, [ct.c_void_p, ct.c_int, ct.POINTER(PplsPo2Theta), _ip, _ip, _ip, ct.c_int, ct.c_double,
+                                         ct.c_int, _dp, ct.c_int, _ip, _ip, _ip]),
+    "ppls_po2_timing_batch": (ct.c_int, [ct.c_void_p, ct.c_int, ct.POINTER(PplsPo2Theta), _ip, _ip, _ip, ct.c_int, ct.c_int, _dp]),
+    "ppls_po2_stats_batch": (ct.c_int, [ct.c_void_p, _dp, ct.c_int, ct.c_int, ct.c_int, _ip, _ip, _dp, _dp, _dp, _dp, _dp]),
+    "ppls_po2_predict_map": (ct.c_int, [ct.POINTER(PplsPo2Theta), ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int,
+                                        _dp, _dp]),
+    "ppls_po2_cv_stream": (ct.c_int, [ct.c_void_p, ct.c_int, _ip, _ip, _ip, ct.c_int, ct.c_double, ct.c_int, _dp, _dp, ct.c_int,
+                                      _dp, _dp, _ip, _ip, ct.POINTER(PplsPo2Theta)]),
 }
 
 

@@ -31,7 +31,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import Expect, Po2Expect, Po2Theta, PplsError, Theta, dptr
-from .po2 import canonical_PO2PLS, simulate_PO2PLS, summary_PO2PLS  # noqa: F401
+from .po2 import canonical_PO2PLS, po2_predict_map, select_grid_PO2PLS, simulate_PO2PLS, summary_PO2PLS  # noqa: F401
 
 
 def pop_rows(pop_sizes, row0, n_local):
@@ -1168,6 +1168,115 @@ class Context:
         ts = th.struct()
         self._chk(self._L.ppls_po2_timing(self.h, ct.byref(ts), th.r, th.rx, th.ry, int(reps), dptr(ms)))
         return dict(zip(("pass", "gram", "small", "update", "iteration", "update_qr"), ms.tolist()))
+
+    # -- batched PO2PLS fits and cross-validation over (r, rx, ry)
+    def po2_em_run_batch(self, thetas, max_steps=100, atol=1e-4, type_=_lib.PPLS_ORTH_SVD):
+        """ppls_po2_em_run_batch: the EM loop of every Po2Theta in ``thetas`` (shapes may differ or repeat)
+        at once on the context's S.  Returns (estimates, histories, negative increments, status): lists with
+        one entry per model; a failed model (status -3) keeps its start and an empty history."""
+        ests = [t.copy() for t in thetas]
+        m, cap = len(ests), int(max_steps) + 1
+        structs = [t.struct() for t in ests]
+        arr = (_lib.PplsPo2Theta * max(m, 1))(*structs)
+        ia = lambda v: np.ascontiguousarray(v, dtype=np.int32)   # noqa: E731
+        ip = lambda a: a.ctypes.data_as(_lib._ip)                # noqa: E731
+        r, rx, ry = ia([t.r for t in ests]), ia([t.rx for t in ests]), ia([t.ry for t in ests])
+        ll = np.zeros((max(m, 1), cap))
+        n, neg, st = np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.int32)
+        self._chk(self._L.ppls_po2_em_run_batch(self.h, m, arr, ip(r), ip(rx), ip(ry), int(max_steps), float(atol), int(type_),
+                                                dptr(ll), cap, ip(n), ip(neg), ip(st)))
+        for t, s in zip(ests, arr):
+            t.pull(s)
+        return ests, [ll[j, :n[j]].copy() for j in range(m)], [bool(v) for v in neg[:m]], [int(v) for v in st[:m]]
+
+    def po2_stats_batch(self, Gxs, Gys, S=None, ldx=None):
+        """The batched statistics pass and Gram alone (ppls_po2_stats_batch): per model (M, Q, Gx'Gx, Gy'Gy)
+        as ``po2_stats`` returns them, for lists of padded loadings Gxs[j] (ldx x kx_j), Gys[j] (ldy x ky_j)."""
+        Gxs = [np.asfortranarray(np.array(G, dtype=np.float64, ndmin=2)) for G in Gxs]
+        Gys = [np.asfortranarray(np.array(G, dtype=np.float64, ndmin=2)) for G in Gys]
+        m = len(Gxs)
+        if m < 1 or len(Gys) != m:
+            raise ValueError("one Gx and one Gy per model, at least one model")
+        ldx = Gxs[0].shape[0] if ldx is None else int(ldx)
+        P = ldx + Gys[0].shape[0]
+        if any(G.shape[0] != ldx for G in Gxs) or any(G.shape[0] != P - ldx for G in Gys):
+            raise ValueError("every model's loadings need the same padded row counts")
+        if S is not None:
+            S = np.ascontiguousarray(S, dtype=np.float64)
+            if S.shape != (P, P):
+                raise ValueError(f"S must be {P} x {P}")
+        kx = np.ascontiguousarray([G.shape[1] for G in Gxs], dtype=np.int32)
+        ky = np.ascontiguousarray([G.shape[1] for G in Gys], dtype=np.int32)
+        k = kx + ky
+        Gx, Gy = np.asfortranarray(np.hstack(Gxs)), np.asfortranarray(np.hstack(Gys))
+        M, Q, GG = np.zeros(int(P * k.sum())), np.zeros(int((k * k).sum())), np.zeros(int((kx * kx + ky * ky).sum()))
+        ip = lambda a: a.ctypes.data_as(_lib._ip)                # noqa: E731
+        self._chk(self._L.ppls_po2_stats_batch(self.h, dptr(S) if S is not None else None, P, ldx, m, ip(kx), ip(ky), dptr(Gx),
+                                               dptr(Gy), dptr(M), dptr(Q), dptr(GG)))
+        out, oM, oQ, oG = [], 0, 0, 0
+        for j in range(m):
+            a, b, kk = int(kx[j]), int(ky[j]), int(k[j])
+            out.append((M[oM:oM + P * kk].reshape(P, kk, order="F").copy(), Q[oQ:oQ + kk * kk].reshape(kk, kk, order="F").copy(),
+                        GG[oG:oG + a * a].reshape(a, a, order="F").copy(),
+                        GG[oG + a * a:oG + a * a + b * b].reshape(b, b, order="F").copy()))
+            oM, oQ, oG = oM + P * kk, oQ + kk * kk, oG + a * a + b * b
+        return out
+
+    def po2_timing_batch(self, thetas, steps=50, reps=3):
+        """HIP-event ms per EM iteration (ppls_po2_timing_batch): dict(batch, sequential, batch_pass,
+        sequential_pass) -- the batched iteration and pass against the same models one after another through
+        the single-model launches, device time only."""
+        structs = [t.struct() for t in thetas]
+        arr = (_lib.PplsPo2Theta * len(thetas))(*structs)
+        ia = lambda v: np.ascontiguousarray(v, dtype=np.int32)   # noqa: E731
+        ip = lambda a: a.ctypes.data_as(_lib._ip)                # noqa: E731
+        r, rx, ry = ia([t.r for t in thetas]), ia([t.rx for t in thetas]), ia([t.ry for t in thetas])
+        ms = np.zeros(4)
+        self._chk(self._L.ppls_po2_timing_batch(self.h, len(thetas), arr, ip(r), ip(rx), ip(ry), int(steps), int(reps), dptr(ms)))
+        return dict(zip(("batch", "sequential", "batch_pass", "sequential_pass"), ms.tolist()))
+
+    def po2_cv_stream(self, cands, max_steps=100, atol=1e-4, type_=_lib.PPLS_ORTH_SVD, V0x=None, V0y=None, start_steps=10,
+                      want_fits=False):
+        """ppls_po2_cv_stream on a context streamed with folds: ``cands`` a list of (r, rx, ry).  Returns
+        dict(rmsep, cond, steps, status) of K x len(cands) arrays, with ``want_fits`` also ``fits`` (K lists of
+        Po2Theta, None where the candidate failed)."""
+        K = int(self.stream_fold_info()["nr_folds"])
+        nc = len(cands)
+        ia = lambda v: np.ascontiguousarray(v, dtype=np.int32)   # noqa: E731
+        ip = lambda a: a.ctypes.data_as(_lib._ip)                # noqa: E731
+        r, rx, ry = (ia([c[i] for c in cands]) for i in range(3))
+        mrx, mry = int(rx.max()) if nc else 0, int(ry.max()) if nc else 0
+        vx = np.asfortranarray(np.asarray(V0x, dtype=np.float64).reshape(self.p, -1)[:, :mrx]) if mrx else None
+        vy = np.asfortranarray(np.asarray(V0y, dtype=np.float64).reshape(self.q, -1)[:, :mry]) if mry else None
+        if (mrx and vx.shape[1] < mrx) or (mry and vy.shape[1] < mry):
+            raise ValueError("V0x / V0y need max(rx) / max(ry) columns")
+        Kn = max(K, 1) * max(nc, 1)
+        rmsep, cond = np.full(Kn, np.nan), np.full(Kn, np.nan)
+        steps, status = np.zeros(Kn, np.int32), np.zeros(Kn, np.int32)
+        fits, arr = None, None
+        if want_fits and K and nc:
+            fits = [[Po2Theta(np.zeros((self.p, c[0])), np.zeros((self.p, c[1])), np.zeros((self.q, c[0])), np.zeros((self.q, c[2])),
+                              np.zeros(c[0]), np.zeros(c[0]), np.zeros(c[1]), np.zeros(c[2]), 1.0, 1.0, 1.0) for c in cands]
+                    for _ in range(K)]
+            arr = (_lib.PplsPo2Theta * (K * nc))(*[t.struct() for f in fits for t in f])
+        try:
+            self._chk(self._L.ppls_po2_cv_stream(self.h, nc, ip(r), ip(rx), ip(ry), int(max_steps), float(atol), int(type_),
+                                                 dptr(vx), dptr(vy), int(start_steps), dptr(rmsep), dptr(cond), ip(steps),
+                                                 ip(status), arr))
+        finally:
+            if self._stream_folds:
+                self.n_total = self.stream_info()["n_total"]     # selected on -1 again
+        sh = (K, nc)
+        out = dict(rmsep=rmsep[:K * nc].reshape(sh), cond=cond[:K * nc].reshape(sh), steps=steps[:K * nc].reshape(sh),
+                   status=status[:K * nc].reshape(sh))
+        if fits is not None:
+            for f in range(K):
+                for j in range(nc):
+                    fits[f][j].pull(arr[f * nc + j])
+                    if out["status"][f, j] != 0:
+                        fits[f][j] = None
+            out["fits"] = fits
+        return out
 
     # -- cross-validation (crossval_PPLS.R:12-114)
     @staticmethod
@@ -3207,6 +3316,107 @@ def PO2PLS(X, Y, r, rx, ry, EMsteps=100, atol=1e-4, type="SVD", init="ppls", rng
     if neg:
         warnings.warn("Negative increments of likelihood")
     return {"Expectations": eout.as_dict(), "loglik": ll, "estimates": est.as_dict(), "class": "PO2PLS"}
+
+
+def predict_PO2PLS(fit, newdata, XorY="X", ctx=None, rescale=False, Znew=None):
+    """The PO2PLS prediction E[y | x] (``XorY="X"``) or E[x | y] ("Y") of the rows of ``newdata``, on the GPU:
+    the map of ``po2_predict_map`` fed through ``predict_PPLS``'s path, so ``ctx``, ``rescale`` and ``Znew``
+    mean what they mean there (scaled and covariate-adjusted contexts included).  ``fit``: a PO2PLS fit
+    or its ``estimates``."""
+    xy = XorY if isinstance(XorY, str) else XorY[0]
+    e = fit["estimates"] if "estimates" in fit else fit
+    L, Bp = po2_predict_map(e, xy)
+    obj = dict(W=L, C=np.asarray(e["C"], dtype=np.float64), B=Bp) if xy == "X" else \
+        dict(W=np.asarray(e["W"], dtype=np.float64), C=L, B=Bp)
+    return predict_PPLS(obj, newdata, xy, ctx=ctx, rescale=rescale, Znew=Znew)
+
+
+def crossval_PO2PLS(X, Y, r, rx, ry, nr_folds, folds=None, rng=None, ctx=None, EMsteps=100, atol=1e-4, type="SVD",
+                    start_steps=10, return_fits=False):
+    """Choose PO2PLS's component counts by cross-validated X -> Y prediction error.
+
+    ``r``, ``rx``, ``ry``: lists; the grid is their product, in that order (list the small models first:
+    ties, and cells within rounding of each other, go to the cell listed first).  Per fold all cells are
+    fitted at once on the training cross-products (``ppls_po2_em_run_batch``) from ``ppls_po2_start``'s
+    values (normal draws from ``rng``, the same for every fold and cell), and the held-out error comes from
+    the fold's own cross-products.  Cells outside the model's size limits are refused before any device work.
+
+    Returns dict(errors (len(r) x len(rx) x len(ry): the fold-mean RMSEP, NaN where any fold failed),
+    per_fold, cond, steps (each K x grid), failed (bool, K x grid), which_error (index triple or None),
+    best ((r, rx, ry) or None), time, class="cvPO2PLS"), with ``return_fits`` also ``fits`` (K lists in grid
+    order of estimates dicts or None) and ``grid``.  A NaN cell never wins while a finite cell exists.
+
+    ``X = Y = None`` with a context streamed with ``nr_folds`` folds runs on the stream's folds.  With resident
+    rows (``X``, ``Y`` or a context that holds rows) the rows are streamed, device to device and as they
+    are loaded (no centring or scaling), into a fold stream on a second context of the call, which then takes
+    the same path; the source is left untouched.  Warns about cancellation as ``cv_PPLS`` does."""
+    tic = time.perf_counter()
+    rs, rxs, rys = ([int(v) for v in np.atleast_1d(a)] for a in (r, rx, ry))
+    K = int(nr_folds)
+    if K < 2:
+        raise ValueError("Cross-validation with 1 fold does not make sense, use 2 folds or more")
+    if not rs or not rxs or not rys:
+        raise ValueError("r, rx and ry must each hold at least one value")
+    t = _orth_type(type)
+    streamed = X is None and ctx is not None and bool(ctx._stream_folds)
+    if streamed:
+        if K != int(ctx._stream_folds):
+            raise ValueError(f"nr_folds={K}, but the rows were streamed with {ctx._stream_folds} folds")
+        if folds is not None:
+            raise ValueError("folds= cannot be given: the folds are those the rows were streamed with")
+        src = ctx
+    else:
+        src = _ctx_with(X, Y, ctx)
+    p, q = src.p, src.q
+    grid = [(a, b, c) for a in rs for b in rxs for c in rys]
+    for a, b, c in grid:     # the library's limits, checked before any device work
+        if a < 1 or b < 0 or c < 0 or a + b > min(16, p) or a + c > min(16, q):
+            raise ValueError(f"grid cell (r, rx, ry) = {(a, b, c)} outside r >= 1, rx, ry >= 0, r + rx <= min(16, p={p}), "
+                             f"r + ry <= min(16, q={q})")
+    if len(grid) > 256:
+        raise ValueError(f"{len(grid)} grid cells: one batch holds at most 256")
+    rng = rng if rng is not None else np.random.default_rng()
+    own = None
+    try:
+        if streamed:
+            cv = src
+        else:
+            fold_of = fold_labels(int(src.n_total), K, folds, rng)
+            lo = int(src.row0)
+            cv = own = Context(src.device)
+            cv.stream_begin(p, q, False, False, nr_folds=K)
+            cv.stream_rows_from(src, fold=fold_of[lo: lo + src.n_local])
+            cv.stream_end()
+        V0x, V0y = rng.standard_normal((p, max(rxs))), rng.standard_normal((q, max(rys)))
+        res = cv.po2_cv_stream(grid, int(EMsteps), float(atol), t, V0x, V0y, int(start_steps), want_fits=return_fits)
+    finally:
+        if own is not None:
+            own.close()
+    shape = (K, len(rs), len(rxs), len(rys))
+    per_fold, cond, steps = (res[k].reshape(shape) for k in ("rmsep", "cond", "steps"))
+    failed = res["status"].reshape(shape) != 0
+    with np.errstate(invalid="ignore"):
+        lost = np.argwhere(np.abs(res["cond"]) * 64 * 2.0 ** -53 > _COND_LIMIT)
+    for f, j in lost:
+        warnings.warn(f"fold {int(f)}, (r, rx, ry) = {grid[int(j)]}: the held-out error from cross-products keeps "
+                      f"few digits (mag / sse = {res['cond'][f, j]:.3g})")
+    errors, which = select_grid_PO2PLS(per_fold, failed)
+    out = {"errors": errors, "per_fold": per_fold, "cond": cond, "steps": steps, "failed": failed, "which_error": which,
+           "best": None if which is None else (rs[which[0]], rxs[which[1]], rys[which[2]]),
+           "time": time.perf_counter() - tic, "class": "cvPO2PLS"}
+    if return_fits:
+        out["grid"] = grid
+        out["fits"] = [[None if th is None else th.as_dict() for th in f] for f in res["fits"]]
+    return out
+
+
+def cv_PO2PLS(X, Y, r, rx, ry, nr_folds, folds=None, rng=None, ctx=None, per_fold=False, **args):
+    """The cross-validated RMSEP of Y predicted from X by one PO2PLS model (r, rx, ry): ``crossval_PO2PLS``
+    on a grid of one cell (its ``EMsteps``, ``atol``, ``type``, ``start_steps``).  Returns the fold mean (NaN
+    when a fold failed), with ``per_fold=True`` also the per-fold errors."""
+    res = crossval_PO2PLS(X, Y, [int(r)], [int(rx)], [int(ry)], nr_folds, folds=folds, rng=rng, ctx=ctx, **args)
+    err = float(res["errors"][0, 0, 0])
+    return (err, res["per_fold"][:, 0, 0, 0].copy()) if per_fold else err
 
 
 def scores_PO2PLS(fit, X=None, Y=None, ctx=None):

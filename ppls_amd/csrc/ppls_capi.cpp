@@ -7770,6 +7770,7 @@ int po2_setup(ppls_ctx* c, Po2Dev& d, const ppls_po2_theta* th, const Po2Shape& 
   a.status = ints;
   a.stop = nullptr;
   a.stop_mirror = nullptr;
+  a.My = a.M + (size_t)s.kx * P;
   a.S = c->xp_S;
   a.ldx = ldx; a.ldy = ldy; a.p = c->p; a.q = c->q; a.r = s.r; a.rx = s.rx; a.ry = s.ry;
   a.N = (double)c->n_total; a.ssqX = c->ssq_host[0]; a.ssqY = c->ssq_host[1]; a.atol = 0.0;
@@ -7792,7 +7793,7 @@ int po2_setup(ppls_ctx* c, Po2Dev& d, const ppls_po2_theta* th, const Po2Shape& 
 int po2_panels(ppls_ctx* c, const PplsPo2Args& a, int kx, int ky, int rw) {
   const int P = a.ldx + a.ldy;
   HIPCHK(c, ppls_launch_po2_panel(a.S, P, 0, a.ldx, a.Gx, a.ldx, kx, rw, a.M, a.stop, c->stream));
-  HIPCHK(c, ppls_launch_po2_panel(a.S, P, a.ldx, a.ldy, a.Gy, a.ldy, ky, rw, a.M + (size_t)kx * P, a.stop, c->stream));
+  HIPCHK(c, ppls_launch_po2_panel(a.S, P, a.ldx, a.ldy, a.Gy, a.ldy, ky, rw, a.My, a.stop, c->stream));
   return PPLS_OK;
 }
 
@@ -7881,13 +7882,13 @@ struct Po2Host {
 };
 
 // The device's theta of d into h; PPLS_E_NUMERIC if any of it is not finite (`after`: for the message).
-int po2_pull(ppls_ctx* c, const Po2Dev& d, const Po2Shape& s, Po2Host& h, const char* after) {
+int po2_pull(ppls_ctx* c, const PplsPo2Args& a, const Po2Shape& s, Po2Host& h, const char* after) {
   const int p = c->p, q = c->q, ldx = c->ldx, ldy = c->ldy;
   std::vector<double> gx((size_t)ldx * s.kx), gy((size_t)ldy * s.ky);
   PplsPo2Scalars& hs = h.hs;
-  HIPCHK(c, hipMemcpy(gx.data(), d.a.Gx, sizeof(double) * gx.size(), hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(gy.data(), d.a.Gy, sizeof(double) * gy.size(), hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(&hs, d.a.sc, sizeof hs, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(gx.data(), a.Gx, sizeof(double) * gx.size(), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(gy.data(), a.Gy, sizeof(double) * gy.size(), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(&hs, a.sc, sizeof hs, hipMemcpyDeviceToHost));
   bool fin = std::isfinite(hs.sE) && std::isfinite(hs.sF) && std::isfinite(hs.sH);
   for (double v : gx) fin = fin && std::isfinite(v);
   for (double v : gy) fin = fin && std::isfinite(v);
@@ -7974,6 +7975,154 @@ void po2_canonical(ppls_po2_theta* th, const Po2Shape& s, int p, int q) {
   };
   spec(th->Wo, th->sigTo, p, s.rx);
   spec(th->Co, th->sigUo, q, s.ry);
+}
+
+// ---- the batched iteration: m models on one S.  All models' Gx columns lie side by side in one
+// ldx x sum kx buffer (Gy alike) and the X and Y parts of their M in one P x sum kx and one P x sum ky buffer,
+// so one pass is ceil(sum kx / 16) + ceil(sum ky / 16) panel launches whatever m is; a chunk may straddle two
+// models (the panel's output does not depend, column by column, on the width it is launched at).  Everything
+// else -- stop pair, status, scalars, moments, history, Q, G'G, the update's scratch -- is per model.
+struct Po2Batch {
+  CvScratch tmp;
+  int m = 0, sumx = 0, sumy = 0, max_entries = 0, rw = 0, hist = 0, P = 0, ldx = 0, ldy = 0;
+  std::vector<Po2Shape> sh;
+  std::vector<int> offx, offy;   // first column of model j in the shared X and Y buffers
+  std::vector<PplsPo2Args> ha;
+  PplsPo2Args* da = nullptr;
+  const double* S = nullptr;
+  double *Gx = nullptr, *Gy = nullptr, *Mx = nullptr, *My = nullptr, *Q = nullptr, *GGx = nullptr, *GGy = nullptr;
+  size_t qstride = 0, gstride = 0;
+  int* ints = nullptr;      // per model {stop[0], stop[1], status, unused}
+  int* mirror = nullptr;    // host-mapped: slot j = model j's stop pass
+  ~Po2Batch() {
+    if (mirror) (void)hipHostFree(mirror);
+  }
+};
+
+// The buffers and the device array of arguments.  guard: doubles left between the outputs (the debug entry
+// fills and checks them).  loop: also what the small and update kernels need (else the pass and Gram alone).
+int po2_batch_alloc(ppls_ctx* c, Po2Batch& b, const double* S, int ldx, int ldy, int p, int q, const std::vector<Po2Shape>& sh,
+                    int hist, size_t guard, bool loop, int type, double atol) {
+  int rc;
+  const int m = (int)sh.size(), P = ldx + ldy;
+  b.m = m; b.sh = sh; b.hist = hist; b.P = P; b.ldx = ldx; b.ldy = ldy; b.S = S;
+  b.offx.assign(m, 0); b.offy.assign(m, 0);
+  for (int j = 0; j < m; ++j) {
+    b.offx[j] = b.sumx; b.offy[j] = b.sumy;
+    b.sumx += sh[j].kx; b.sumy += sh[j].ky;
+    b.max_entries = std::max(b.max_entries, sh[j].k * (sh[j].k + 1) / 2 + sh[j].kx * (sh[j].kx + 1) / 2 + sh[j].ky * (sh[j].ky + 1) / 2);
+  }
+  b.qstride = (size_t)PPLS_PO2_KMAX * PPLS_PO2_KMAX + guard;
+  b.gstride = (size_t)PPLS_RMAX * PPLS_RMAX + guard;
+  PplsPo2Scalars* sc = nullptr;
+  PplsPo2Small* sm = nullptr;
+  double *Z = nullptr, *ll = nullptr, *Mall = nullptr;
+  if ((rc = b.tmp.get(c, &b.Gx, (size_t)ldx * b.sumx)) || (rc = b.tmp.get(c, &b.Gy, (size_t)ldy * b.sumy)) ||
+      (rc = b.tmp.get(c, &Mall, (size_t)P * (b.sumx + b.sumy) + 3 * guard)) || (rc = b.tmp.get(c, &b.Q, b.qstride * m)) ||
+      (rc = b.tmp.get(c, &b.GGx, b.gstride * m)) || (rc = b.tmp.get(c, &b.GGy, b.gstride * m)) || (rc = b.tmp.get(c, &b.da, (size_t)m)))
+    return rc;
+  b.Mx = Mall + guard;
+  b.My = b.Mx + (size_t)P * b.sumx + guard;
+  if (loop) {
+    if ((rc = b.tmp.get(c, &sc, (size_t)m)) || (rc = b.tmp.get(c, &sm, (size_t)m)) || (rc = b.tmp.get(c, &Z, (size_t)m * PPLS_RMAX * P)) ||
+        (rc = b.tmp.get(c, &ll, (size_t)m * hist)) || (rc = b.tmp.get(c, &b.ints, (size_t)4 * m)))
+      return rc;
+    HIPCHK(c, hipMemset(b.ints, 0, sizeof(int) * 4 * m));
+    HIPCHK(c, hipHostMalloc((void**)&b.mirror, sizeof(int) * m, hipHostMallocMapped | hipHostMallocCoherent));
+    for (int j = 0; j < m; ++j) __atomic_store_n(b.mirror + j, 0, __ATOMIC_SEQ_CST);
+  }
+  int* mirror_dev = nullptr;
+  if (b.mirror) HIPCHK(c, hipHostGetDevicePointer((void**)&mirror_dev, b.mirror, 0));
+  b.ha.assign(m, PplsPo2Args{});
+  for (int j = 0; j < m; ++j) {
+    PplsPo2Args& a = b.ha[j];
+    a.S = S; a.ldx = ldx; a.ldy = ldy; a.p = p; a.q = q; a.r = sh[j].r; a.rx = sh[j].rx; a.ry = sh[j].ry; a.type = type;
+    a.Gx = b.Gx + (size_t)b.offx[j] * ldx;
+    a.Gy = b.Gy + (size_t)b.offy[j] * ldy;
+    a.M = b.Mx + (size_t)b.offx[j] * P;
+    a.My = b.My + (size_t)b.offy[j] * P;
+    a.Q = b.Q + b.qstride * j;
+    a.GGx = b.GGx + b.gstride * j;
+    a.GGy = b.GGy + b.gstride * j;
+    if (loop) {
+      a.sc = sc + j; a.sm = sm + j; a.Z = Z + (size_t)j * PPLS_RMAX * P; a.loglik = ll + (size_t)j * hist;
+      a.stop = b.ints + 4 * j; a.status = b.ints + 4 * j + 2; a.stop_mirror = mirror_dev + j;
+      a.N = (double)c->n_total; a.ssqX = c->ssq_host[0]; a.ssqY = c->ssq_host[1]; a.atol = atol;
+    }
+  }
+  HIPCHK(c, hipMemcpy(b.da, b.ha.data(), sizeof(PplsPo2Args) * m, hipMemcpyHostToDevice));
+  // rows of S per wave: the tile kernel's rule at the full chunk width (the sums of a row do not depend on it)
+  b.rw = ppls_xprod_tile_rows(P, PPLS_RMAX, c->xprod_rw, c->num_cus);
+  return PPLS_OK;
+}
+
+// One batched pass: the shared panels in chunks of up to 16 columns, then the Gram of every model.
+int po2_batch_pass(ppls_ctx* c, const Po2Batch& b) {
+  for (int c0 = 0; c0 < b.sumx; c0 += PPLS_RMAX)
+    HIPCHK(c, ppls_launch_po2_panel(b.S, b.P, 0, b.ldx, b.Gx + (size_t)c0 * b.ldx, b.ldx, std::min(PPLS_RMAX, b.sumx - c0), b.rw,
+                                    b.Mx + (size_t)c0 * b.P, nullptr, c->stream));
+  for (int c0 = 0; c0 < b.sumy; c0 += PPLS_RMAX)
+    HIPCHK(c, ppls_launch_po2_panel(b.S, b.P, b.ldx, b.ldy, b.Gy + (size_t)c0 * b.ldy, b.ldy, std::min(PPLS_RMAX, b.sumy - c0), b.rw,
+                                    b.My + (size_t)c0 * b.P, nullptr, c->stream));
+  HIPCHK(c, ppls_launch_po2_gram_batch(b.da, b.m, b.max_entries, c->stream));
+  return PPLS_OK;
+}
+
+// Theta up: the loadings into the shared padded columns, the scalars per model.
+int po2_batch_upload(ppls_ctx* c, Po2Batch& b, const ppls_po2_theta* th, int p, int q) {
+  const int ldx = b.ldx, ldy = b.ldy, m = b.m;
+  const std::vector<Po2Shape>& sh = b.sh;
+  std::vector<double> hx((size_t)ldx * b.sumx, 0.0), hy((size_t)ldy * b.sumy, 0.0);
+  std::vector<PplsPo2Scalars> hs((size_t)m);
+  for (int j = 0; j < m; ++j) {
+    const ppls_po2_theta& t = th[j];
+    for (int k = 0; k < sh[j].kx; ++k) {
+      const double* src = k < sh[j].r ? t.W + (size_t)k * p : t.Wo + (size_t)(k - sh[j].r) * p;
+      std::copy(src, src + p, hx.begin() + (size_t)(b.offx[j] + k) * ldx);
+    }
+    for (int k = 0; k < sh[j].ky; ++k) {
+      const double* src = k < sh[j].r ? t.C + (size_t)k * q : t.Co + (size_t)(k - sh[j].r) * q;
+      std::copy(src, src + q, hy.begin() + (size_t)(b.offy[j] + k) * ldy);
+    }
+    po2_pack_scalars(&t, sh[j], &hs[j]);
+  }
+  HIPCHK(c, hipMemcpy(b.Gx, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(b.Gy, hy.data(), sizeof(double) * hy.size(), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(b.ha[0].sc, hs.data(), sizeof(PplsPo2Scalars) * m, hipMemcpyHostToDevice));
+  return PPLS_OK;
+}
+
+const char* po2_status_text(int st) {
+  switch (st) {
+    case PPLS_PO2_ST_SIGMA: return "a sigma is not finite and above 0";
+    case PPLS_PO2_ST_LAMBDA: return "Lambda = Sigma_z^-1 + D G'G is not positive definite";
+    case PPLS_PO2_ST_VAR: return "an updated variance is not finite and above 0";
+    default: return "rank-deficient loading update";
+  }
+}
+
+// Lower Cholesky factor of the n x n matrix A (column-major, in place); false: not positive definite.
+bool po2_host_chol(std::vector<double>& A, int n) {
+  for (int j = 0; j < n; ++j) {
+    double d = A[(size_t)j * n + j];
+    for (int m = 0; m < j; ++m) d -= A[(size_t)m * n + j] * A[(size_t)m * n + j];
+    if (!(d > 0.0) || !std::isfinite(d)) return false;
+    d = std::sqrt(d);
+    A[(size_t)j * n + j] = d;
+    for (int i = j + 1; i < n; ++i) {
+      double s = A[(size_t)j * n + i];
+      for (int m = 0; m < j; ++m) s -= A[(size_t)m * n + i] * A[(size_t)m * n + j];
+      A[(size_t)j * n + i] = s / d;
+    }
+  }
+  return true;
+}
+
+// Owned buffers of one theta in the ABI's layout, sized for shape s.
+void po2_host_sized(Po2Host& h, const Po2Shape& s, int p, int q) {
+  h.W.assign((size_t)p * s.r, 0.0); h.Wo.assign((size_t)p * std::max(s.rx, 1), 0.0);
+  h.C.assign((size_t)q * s.r, 0.0); h.Co.assign((size_t)q * std::max(s.ry, 1), 0.0);
+  h.B.assign(s.r, 0.0); h.T.assign(s.r, 0.0); h.To.assign(std::max(s.rx, 1), 0.0); h.Uo.assign(std::max(s.ry, 1), 0.0);
 }
 
 }  // namespace
@@ -8068,7 +8217,7 @@ int ppls_po2_em_run(ppls_ctx* c, ppls_po2_theta* th, int r, int rx, int ry, int 
   Po2Host h;
   char after[48];
   snprintf(after, sizeof after, "%d EM iterations", npass - 1);
-  if ((rc = po2_pull(c, d, s, h, after))) return rc;
+  if ((rc = po2_pull(c, d.a, s, h, after))) return rc;
   ppls_po2_theta est = h.view();
   po2_canonical(&est, s, p, q);
   h.hs.sE = est.sigE; h.hs.sF = est.sigF; h.hs.sH = est.sigH;
@@ -8239,7 +8388,7 @@ int ppls_po2_em_step(ppls_ctx* c, const ppls_po2_theta* th, int r, int rx, int r
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if ((rc = po2_status(c, d))) return rc;
   Po2Host h;
-  if ((rc = po2_pull(c, d, s, h, "one ECM step"))) return rc;
+  if ((rc = po2_pull(c, d.a, s, h, "one ECM step"))) return rc;
   po2_give(h, s, c->p, c->q, out);
   return PPLS_OK;
 }
@@ -8278,6 +8427,7 @@ int ppls_po2_stats(ppls_ctx* c, const double* S, int P, int ldx, const double* G
   a.S = Sd; a.ldx = ldx; a.ldy = ldy; a.p = ldx; a.q = ldy; a.r = 1; a.rx = kx - 1; a.ry = ky - 1;
   a.Gx = gxd; a.Gy = gyd;
   a.M = out + guard;
+  a.My = a.M + (size_t)kx * P;
   a.Q = a.M + nM + guard;
   a.GGx = a.Q + nQ + guard;
   a.GGy = a.GGx + nGx + guard;
@@ -8442,6 +8592,389 @@ int ppls_po2_timing(ppls_ctx* c, const ppls_po2_theta* th, int r, int rx, int ry
     if ((rc = po2_status(c, d))) return rc;
   }
   return PPLS_OK;
+}
+
+// ---- batched PO2PLS: m fits on one S, prediction, cross-validation over (r, rx, ry)
+int ppls_po2_em_run_batch(ppls_ctx* c, int m, ppls_po2_theta* th, const int* r, const int* rx, const int* ry, int max_steps,
+                          double atol, int type, double* loglik, int cap, int* n_loglik, int* negative_increment, int* status) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  if (m < 1 || m > PPLS_PO2_BATCH_MAX) return fail(c, PPLS_E_ARG, "batch of %d models outside [1,%d]", m, PPLS_PO2_BATCH_MAX);
+  if (!th || !r || !rx || !ry || !n_loglik || !status) return fail(c, PPLS_E_ARG, "NULL argument");
+  int rc;
+  const int p = c->p, q = c->q;
+  std::vector<Po2Shape> sh((size_t)m);
+  for (int j = 0; j < m; ++j)
+    if ((rc = po2_shape(c, r[j], rx[j], ry[j], p, q, &sh[j])) || (rc = po2_check_theta(c, th + j, sh[j], p, q))) {
+      c->err = "model " + std::to_string(j) + ": " + c->err;
+      return rc;
+    }
+  if (max_steps < 1) return fail(c, PPLS_E_ARG, "EMsteps must be >= 1");
+  if (type != PPLS_ORTH_SVD && type != PPLS_ORTH_QR) return fail(c, PPLS_E_ARG, "type must be SVD (0) or QR (1)");
+  if (cap < 0 || (cap > 0 && !loglik) || std::isnan(atol)) return fail(c, PPLS_E_ARG, "bad loglik buffer or atol");
+  if ((rc = po2_ready(c))) return rc;
+  Po2Batch b;
+  const int hist = max_steps + 2;
+  if ((rc = po2_batch_alloc(c, b, c->xp_S, c->ldx, c->ldy, p, q, sh, hist, 0, true, type, atol))) return rc;
+  if ((rc = po2_batch_upload(c, b, th, p, q))) return rc;
+  const bool do_check = !(atol == -INFINITY);
+  struct EvGuard {
+    std::vector<hipEvent_t> evs;
+    ~EvGuard() {
+      for (auto e : evs) (void)hipEventDestroy(e);
+    }
+  } guard;
+  constexpr int LOOKAHEAD = 8;   // as ppls_po2_em_run
+  for (int i = 1; i <= max_steps + 1; ++i) {
+    if (i > LOOKAHEAD) {
+      HIPCHK(c, hipEventSynchronize(guard.evs[(size_t)(i - 1 - LOOKAHEAD) % LOOKAHEAD]));
+      bool all = true;
+      for (int j = 0; j < m && all; ++j) all = __atomic_load_n(b.mirror + j, __ATOMIC_ACQUIRE) != 0;
+      if (all) break;
+    }
+    const bool last = i == max_steps + 1;
+    if ((rc = po2_batch_pass(c, b))) return rc;
+    HIPCHK(c, ppls_launch_po2_small_batch(b.da, m, i, last ? 0 : 1, do_check ? 1 : 0, c->stream));
+    if (!last) HIPCHK(c, ppls_launch_po2_update_batch(b.da, m, c->stream));
+    const size_t e = (size_t)(i - 1) % LOOKAHEAD;
+    if (guard.evs.size() <= e) {
+      hipEvent_t ev;
+      HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      guard.evs.push_back(ev);
+    }
+    HIPCHK(c, hipEventRecord(guard.evs[e], c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<int> ints((size_t)4 * m);
+  HIPCHK(c, hipMemcpy(ints.data(), b.ints, sizeof(int) * 4 * m, hipMemcpyDeviceToHost));
+  std::string first;
+  std::vector<double> l;
+  for (int j = 0; j < m; ++j) {
+    const int* sv = &ints[(size_t)4 * j];
+    const int st = sv[2], npass = sv[0] > 0 && sv[0] <= max_steps + 1 ? sv[0] : max_steps + 1;
+    rc = PPLS_OK;
+    Po2Host h;
+    if (st != 0) {
+      rc = fail(c, PPLS_E_NUMERIC, "PO2PLS: %s (status %d)", po2_status_text(st), st);
+    } else if (sv[1]) {
+      rc = fail(c, PPLS_E_NUMERIC, "PO2PLS: the log-likelihood increment of EM iteration %d is NaN", npass - 1);
+    } else {
+      l.resize((size_t)npass);
+      HIPCHK(c, hipMemcpy(l.data(), b.ha[j].loglik, sizeof(double) * npass, hipMemcpyDeviceToHost));
+      for (int i = 0; i < npass && !rc; ++i)
+        if (!std::isfinite(l[i])) rc = fail(c, PPLS_E_NUMERIC, "PO2PLS: non-finite log-likelihood %g at pass %d", l[i], i + 1);
+      if (!rc) {
+        char after[48];
+        snprintf(after, sizeof after, "%d EM iterations", npass - 1);
+        rc = po2_pull(c, b.ha[j], sh[j], h, after);
+      }
+    }
+    if (rc && rc != PPLS_E_NUMERIC) return rc;
+    status[j] = rc;
+    if (rc) {   // theta j and its history stay as the caller gave them
+      n_loglik[j] = 0;
+      if (negative_increment) negative_increment[j] = 0;
+      if (first.empty()) first = "model " + std::to_string(j) + ": " + c->err;
+      continue;
+    }
+    ppls_po2_theta est = h.view();
+    po2_canonical(&est, sh[j], p, q);
+    h.hs.sE = est.sigE; h.hs.sF = est.sigF; h.hs.sH = est.sigH;
+    po2_give(h, sh[j], p, q, th + j);
+    for (int i = 0; i < npass && i < cap; ++i) loglik[(size_t)j * cap + i] = l[i];
+    n_loglik[j] = npass;
+    if (negative_increment) {
+      int neg = 0;
+      for (int i = 1; i < npass; ++i) neg |= (l[i] - l[i - 1] < 0);
+      negative_increment[j] = neg;
+    }
+  }
+  if (!first.empty()) c->err = first;
+  return PPLS_OK;
+}
+
+int ppls_po2_timing_batch(ppls_ctx* c, int m, const ppls_po2_theta* th, const int* r, const int* rx, const int* ry, int steps,
+                          int reps, double* ms4) {
+  if (!c || !ms4 || reps < 1 || steps < 1) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  if (m < 1 || m > PPLS_PO2_BATCH_MAX) return fail(c, PPLS_E_ARG, "batch of %d models outside [1,%d]", m, PPLS_PO2_BATCH_MAX);
+  if (!th || !r || !rx || !ry) return fail(c, PPLS_E_ARG, "NULL argument");
+  int rc;
+  const int p = c->p, q = c->q;
+  std::vector<Po2Shape> sh((size_t)m);
+  for (int j = 0; j < m; ++j)
+    if ((rc = po2_shape(c, r[j], rx[j], ry[j], p, q, &sh[j])) || (rc = po2_check_theta(c, th + j, sh[j], p, q))) return rc;
+  if ((rc = po2_ready(c))) return rc;
+  Po2Batch b;
+  if ((rc = po2_batch_alloc(c, b, c->xp_S, c->ldx, c->ldy, p, q, sh, 2, 0, true, PPLS_ORTH_SVD, -INFINITY))) return rc;
+  std::vector<int> rws((size_t)m);
+  for (int j = 0; j < m; ++j) rws[j] = ppls_xprod_tile_rows(b.P, std::max(sh[j].kx, sh[j].ky), c->xprod_rw, c->num_cus);
+  auto failed = [&]() -> int {   // any model's status word
+    std::vector<int> ints((size_t)4 * m);
+    HIPCHK(c, hipMemcpy(ints.data(), b.ints, sizeof(int) * 4 * m, hipMemcpyDeviceToHost));
+    for (int j = 0; j < m; ++j)
+      if (ints[(size_t)4 * j + 2]) return fail(c, PPLS_E_NUMERIC, "model %d: PO2PLS: %s", j, po2_status_text(ints[(size_t)4 * j + 2]));
+    return PPLS_OK;
+  };
+  for (int part = 0; part < 4; ++part) {   // every part from the same thetas; one untimed round warms the kernels
+    if ((rc = po2_batch_upload(c, b, th, p, q))) return rc;
+    double total = 0.0;
+    for (int rep = -1; rep < reps; ++rep) {
+      CvEvents ev;
+      HIPCHK(c, ev.begin(c->stream));
+      for (int i = 0; i < steps; ++i) {
+        if (part == 0) {          // one batched iteration
+          if ((rc = po2_batch_pass(c, b))) return rc;
+          HIPCHK(c, ppls_launch_po2_small_batch(b.da, m, 1, 1, 0, c->stream));
+          HIPCHK(c, ppls_launch_po2_update_batch(b.da, m, c->stream));
+        } else if (part == 2) {   // the batched pass alone
+          if ((rc = po2_batch_pass(c, b))) return rc;
+        } else {                  // the models one after another through the single-model launches
+          for (int j = 0; j < m; ++j) {
+            if ((rc = po2_panels(c, b.ha[j], sh[j].kx, sh[j].ky, rws[j]))) return rc;
+            HIPCHK(c, ppls_launch_po2_gram(&b.ha[j], c->stream));
+            if (part == 1) {
+              HIPCHK(c, ppls_launch_po2_small(&b.ha[j], 1, 1, 0, c->stream));
+              HIPCHK(c, ppls_launch_po2_update(&b.ha[j], c->stream));
+            }
+          }
+        }
+      }
+      HIPCHK(c, ev.end(c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      if (rep >= 0) total += ev.ms();
+    }
+    ms4[part] = total / ((double)reps * steps);
+    if ((rc = failed())) return rc;
+  }
+  return PPLS_OK;
+}
+
+int ppls_po2_stats_batch(ppls_ctx* c, const double* S, int P, int ldx, int m, const int* kx, const int* ky, const double* Gx,
+                         const double* Gy, double* M, double* Q, double* GG) {
+  if (!c) return PPLS_E_ARG;
+  if (!kx || !ky || !Gx || !Gy || !M || !Q || !GG) return fail(c, PPLS_E_ARG, "NULL argument");
+  if (m < 1 || m > PPLS_PO2_BATCH_MAX) return fail(c, PPLS_E_ARG, "batch of %d models outside [1,%d]", m, PPLS_PO2_BATCH_MAX);
+  const int ldy = P - ldx;
+  if (ldx < 2 || ldy < 2 || (ldx & 1) || (ldy & 1) || P >= (1 << 30)) return fail(c, PPLS_E_ARG, "bad layout P=%d ldx=%d", P, ldx);
+  std::vector<Po2Shape> sh((size_t)m);
+  for (int j = 0; j < m; ++j) {
+    if (kx[j] < 1 || ky[j] < 1 || kx[j] > PPLS_RMAX || ky[j] > PPLS_RMAX)
+      return fail(c, PPLS_E_ARG, "model %d: widths kx=%d ky=%d outside [1,%d]", j, kx[j], ky[j], PPLS_RMAX);
+    sh[j] = {1, kx[j] - 1, ky[j] - 1, kx[j], ky[j], kx[j] + ky[j]};
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  const double* Sd = nullptr;
+  CvScratch tmp;
+  if (S) {
+    double* up = nullptr;
+    if ((rc = tmp.get(c, &up, (size_t)P * P))) return rc;
+    HIPCHK(c, hipMemcpy(up, S, sizeof(double) * P * P, hipMemcpyHostToDevice));
+    Sd = up;
+  } else {
+    if (!c->have_data || !c->xp_ready || !c->xp_S) return fail(c, PPLS_E_STATE, "no cross-products S are ready");
+    if (P != c->ldx + c->ldy || ldx != c->ldx) return fail(c, PPLS_E_ARG, "P=%d ldx=%d are not the context's %d, %d", P, ldx, c->ldx + c->ldy, c->ldx);
+    Sd = c->xp_S;
+  }
+  const size_t guard = 64;
+  Po2Batch b;
+  if ((rc = po2_batch_alloc(c, b, Sd, ldx, ldy, ldx, ldy, sh, 0, guard, false, 0, 0.0))) return rc;
+  HIPCHK(c, hipMemcpy(b.Gx, Gx, sizeof(double) * ldx * b.sumx, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(b.Gy, Gy, sizeof(double) * ldy * b.sumy, hipMemcpyHostToDevice));
+  const size_t nMall = (size_t)P * (b.sumx + b.sumy) + 3 * guard, nQ = b.qstride * m, nG = b.gstride * m;
+  double* Mall = b.Mx - guard;
+  HIPCHK(c, hipMemsetAsync(Mall, 0xFF, sizeof(double) * nMall, c->stream));
+  HIPCHK(c, hipMemsetAsync(b.Q, 0xFF, sizeof(double) * nQ, c->stream));
+  HIPCHK(c, hipMemsetAsync(b.GGx, 0xFF, sizeof(double) * nG, c->stream));
+  HIPCHK(c, hipMemsetAsync(b.GGy, 0xFF, sizeof(double) * nG, c->stream));
+  if ((rc = po2_batch_pass(c, b))) return rc;
+  std::vector<double> hM(nMall), hQ(nQ), hX(nG), hY(nG);
+  HIPCHK(c, hipMemcpyAsync(hM.data(), Mall, sizeof(double) * nMall, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(hQ.data(), b.Q, sizeof(double) * nQ, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(hX.data(), b.GGx, sizeof(double) * nG, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(hY.data(), b.GGy, sizeof(double) * nG, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  // every double outside an output must still be the fill
+  const size_t oMx = guard, oMy = oMx + (size_t)P * b.sumx + guard;
+  bool clean = true;
+  for (size_t g = 0; g < guard && clean; ++g)
+    clean = std::isnan(hM[g]) && std::isnan(hM[oMy - guard + g]) && std::isnan(hM[nMall - guard + g]);
+  for (int j = 0; j < m && clean; ++j) {
+    for (size_t e = (size_t)sh[j].k * sh[j].k; e < b.qstride && clean; ++e) clean = std::isnan(hQ[b.qstride * j + e]);
+    for (size_t e = (size_t)sh[j].kx * sh[j].kx; e < b.gstride && clean; ++e) clean = std::isnan(hX[b.gstride * j + e]);
+    for (size_t e = (size_t)sh[j].ky * sh[j].ky; e < b.gstride && clean; ++e) clean = std::isnan(hY[b.gstride * j + e]);
+  }
+  if (!clean) return fail(c, PPLS_E_NUMERIC, "a batched PO2 statistics kernel wrote outside its output");
+  for (int j = 0; j < m; ++j) {   // per model: M (P x k), Q (k x k), GG = [kx^2 | ky^2], each packed after the one before
+    const size_t nx = (size_t)P * sh[j].kx, ny = (size_t)P * sh[j].ky, k2 = (size_t)sh[j].k * sh[j].k;
+    const size_t gx2 = (size_t)sh[j].kx * sh[j].kx, gy2 = (size_t)sh[j].ky * sh[j].ky;
+    std::copy(hM.begin() + oMx + (size_t)b.offx[j] * P, hM.begin() + oMx + (size_t)b.offx[j] * P + nx, M);
+    std::copy(hM.begin() + oMy + (size_t)b.offy[j] * P, hM.begin() + oMy + (size_t)b.offy[j] * P + ny, M + nx);
+    std::copy(hQ.begin() + b.qstride * j, hQ.begin() + b.qstride * j + k2, Q);
+    std::copy(hX.begin() + b.gstride * j, hX.begin() + b.gstride * j + gx2, GG);
+    std::copy(hY.begin() + b.gstride * j, hY.begin() + b.gstride * j + gy2, GG + gx2);
+    M += nx + ny; Q += k2; GG += gx2 + gy2;
+  }
+  return PPLS_OK;
+}
+
+int ppls_po2_predict_map(const ppls_po2_theta* th, int r, int rx, int ry, int p, int q, int xory, double* L, double* Bp) {
+  if (!th || !L || !Bp || (xory != 0 && xory != 1)) return PPLS_E_ARG;
+  int rc;
+  Po2Shape s;
+  if ((rc = po2_shape(nullptr, r, rx, ry, p, q, &s)) || (rc = po2_check_theta(nullptr, th, s, p, q))) return rc;
+  const int n = xory ? q : p, k = xory ? s.ky : s.kx;
+  const double *A = xory ? th->C : th->W, *Ao = xory ? th->Co : th->Wo, *sgo = xory ? th->sigUo : th->sigTo;
+  const double sn = xory ? th->sigF : th->sigE, dn = 1.0 / (sn * sn);
+  auto col = [&](int j) { return j < r ? A + (size_t)j * n : Ao + (size_t)(j - r) * n; };
+  // Lambda = Sigma^-1 + G'G / sigma^2 for the side's own latent variables: (t, to) with variances sigT^2,
+  // sigTo^2; (u, uo) with sigT^2 b^2 + sigH^2, sigUo^2 (the marginal of u, not its conditional given t)
+  std::vector<double> Lam((size_t)k * k);
+  for (int b = 0; b < k; ++b)
+    for (int a = b; a < k; ++a) {
+      double g = 0.0;
+      const double *u = col(a), *v = col(b);
+      for (int i = 0; i < n; ++i) g = std::fma(u[i], v[i], g);
+      Lam[(size_t)b * k + a] = Lam[(size_t)a * k + b] = g * dn;
+    }
+  for (int j = 0; j < k; ++j) {
+    double var;
+    if (j >= r) var = sgo[j - r] * sgo[j - r];
+    else if (xory) var = th->sigT[j] * th->sigT[j] * th->B[j] * th->B[j] + th->sigH * th->sigH;
+    else var = th->sigT[j] * th->sigT[j];
+    Lam[(size_t)j * k + j] += 1.0 / var;
+  }
+  if (!po2_host_chol(Lam, k)) return PPLS_E_NUMERIC;
+  if (xory)
+    for (int j = 0; j < r; ++j)   // 1 / beta_j must exist
+      if (th->B[j] == 0.0) return PPLS_E_NUMERIC;
+  std::vector<double> X((size_t)k * r, 0.0);   // Lambda X = the first r unit vectors
+  for (int c0 = 0; c0 < r; ++c0) {
+    double* x = &X[(size_t)c0 * k];
+    x[c0] = 1.0;
+    for (int i = 0; i < k; ++i) {
+      double sacc = x[i];
+      for (int m = 0; m < i; ++m) sacc -= Lam[(size_t)m * k + i] * x[m];
+      x[i] = sacc / Lam[(size_t)i * k + i];
+    }
+    for (int i = k - 1; i >= 0; --i) {
+      double sacc = x[i];
+      for (int m = i + 1; m < k; ++m) sacc -= Lam[(size_t)i * k + m] * x[m];
+      x[i] = sacc / Lam[(size_t)i * k + i];
+    }
+  }
+  for (int c0 = 0; c0 < r; ++c0)
+    for (int i = 0; i < n; ++i) {
+      double acc = 0.0;
+      for (int m = 0; m < k; ++m) acc = std::fma(col(m)[i], X[(size_t)c0 * k + m], acc);
+      L[(size_t)c0 * n + i] = acc * dn;
+    }
+  for (int j = 0; j < r; ++j) {
+    if (!xory) { Bp[j] = th->B[j]; continue; }
+    const double vt = th->sigT[j] * th->sigT[j], b = th->B[j];
+    Bp[j] = (vt * b * b + th->sigH * th->sigH) / (vt * b);   // 1 / beta_j
+  }
+  return PPLS_OK;
+}
+
+int ppls_po2_cv_stream(ppls_ctx* c, int ncand, const int* r, const int* rx, const int* ry, int max_steps, double atol, int type,
+                       const double* V0x, const double* V0y, int start_steps, double* rmsep, double* cond, int* steps,
+                       int* status, ppls_po2_theta* fits) {
+  if (!c) return PPLS_E_ARG;
+  int rc;
+  if ((rc = fold_state_check(c))) return rc;
+  if (c->em_active)
+    return fail(c, PPLS_E_STATE, "an ppls_em_begin session is active on the selected cross-products: finish it before cross-validating");
+  if (ncand < 1 || ncand > PPLS_PO2_BATCH_MAX) return fail(c, PPLS_E_ARG, "%d candidates outside [1,%d]", ncand, PPLS_PO2_BATCH_MAX);
+  if (!r || !rx || !ry || !rmsep || !status) return fail(c, PPLS_E_ARG, "NULL argument");
+  const int K = c->st_nfolds, p = c->p, q = c->q;
+  std::vector<Po2Shape> sh((size_t)ncand);
+  int mrx = 0, mry = 0;
+  for (int j = 0; j < ncand; ++j) {
+    if ((rc = po2_shape(c, r[j], rx[j], ry[j], p, q, &sh[j]))) return rc;
+    mrx = std::max(mrx, rx[j]); mry = std::max(mry, ry[j]);
+  }
+  if ((mrx && !V0x) || (mry && !V0y)) return fail(c, PPLS_E_ARG, "NULL argument");
+  for (size_t e = 0; e < (size_t)p * mrx; ++e)
+    if (!std::isfinite(V0x[e])) return fail(c, PPLS_E_ARG, "V0x has non-finite entries");
+  for (size_t e = 0; e < (size_t)q * mry; ++e)
+    if (!std::isfinite(V0y[e])) return fail(c, PPLS_E_ARG, "V0y has non-finite entries");
+  if (max_steps < 1 || start_steps < 0) return fail(c, PPLS_E_ARG, "EMsteps must be >= 1 and start_steps >= 0");
+  if (type != PPLS_ORTH_SVD && type != PPLS_ORTH_QR) return fail(c, PPLS_E_ARG, "type must be SVD (0) or QR (1)");
+  if (std::isnan(atol)) return fail(c, PPLS_E_ARG, "bad atol");
+  if (fits)
+    for (int e = 0; e < K * ncand; ++e) {
+      const Po2Shape& s = sh[(size_t)(e % ncand)];
+      const ppls_po2_theta& t = fits[e];
+      if (!t.W || !t.C || !t.B || !t.sigT || (s.rx && (!t.Wo || !t.sigTo)) || (s.ry && (!t.Co || !t.sigUo)))
+        return fail(c, PPLS_E_ARG, "fits[%d] has NULL fields", e);
+    }
+  auto run = [&]() -> int {
+    int rr;
+    std::vector<Po2Host> own((size_t)ncand);
+    std::vector<ppls_po2_theta> view((size_t)ncand), bth;
+    std::vector<int> idx, br, brx, bry, nl, bst;
+    std::vector<double> L, Bp((size_t)PPLS_RMAX), sse((size_t)PPLS_RMAX), mag((size_t)PPLS_RMAX);
+    for (int f = 0; f < K; ++f) {
+      if ((rr = ppls_stream_select(c, f))) return rr;
+      if (c->n_total < 1) return fail(c, PPLS_E_ARG, "fold %d leaves no training row", f);
+      idx.clear(); bth.clear(); br.clear(); brx.clear(); bry.clear();
+      for (int j = 0; j < ncand; ++j) {
+        const size_t o = (size_t)f * ncand + j;
+        rmsep[o] = NAN;
+        if (cond) cond[o] = NAN;
+        if (steps) steps[o] = 0;
+        po2_host_sized(own[j], sh[j], p, q);
+        view[j] = own[j].view();
+        rr = ppls_po2_start(c, r[j], rx[j], ry[j], V0x, V0y, start_steps, &view[j]);
+        if (rr && rr != PPLS_E_NUMERIC) return rr;
+        status[o] = rr;
+        if (rr) continue;
+        idx.push_back(j); bth.push_back(view[j]); br.push_back(r[j]); brx.push_back(rx[j]); bry.push_back(ry[j]);
+      }
+      const int mb = (int)idx.size();
+      if (mb == 0) continue;
+      nl.assign(mb, 0); bst.assign(mb, 0);
+      if ((rr = ppls_po2_em_run_batch(c, mb, bth.data(), br.data(), brx.data(), bry.data(), max_steps, atol, type, nullptr, 0,
+                                      nl.data(), nullptr, bst.data())))
+        return rr;
+      for (int i = 0; i < mb; ++i) {
+        const int j = idx[i];
+        const size_t o = (size_t)f * ncand + j;
+        status[o] = bst[i];
+        if (bst[i]) continue;
+        if (steps) steps[o] = nl[i] - 1;
+        const ppls_po2_theta& t = bth[i];
+        if (fits) {   // the caller's buffers (checked above)
+          ppls_po2_theta& o_ = fits[o];
+          std::copy(t.W, t.W + (size_t)p * r[j], o_.W);
+          std::copy(t.C, t.C + (size_t)q * r[j], o_.C);
+          std::copy(t.B, t.B + r[j], o_.B);
+          std::copy(t.sigT, t.sigT + r[j], o_.sigT);
+          if (rx[j]) { std::copy(t.Wo, t.Wo + (size_t)p * rx[j], o_.Wo); std::copy(t.sigTo, t.sigTo + rx[j], o_.sigTo); }
+          if (ry[j]) { std::copy(t.Co, t.Co + (size_t)q * ry[j], o_.Co); std::copy(t.sigUo, t.sigUo + ry[j], o_.sigUo); }
+          o_.sigE = t.sigE; o_.sigF = t.sigF; o_.sigH = t.sigH;
+        }
+        L.assign((size_t)p * r[j], 0.0);
+        if ((rr = ppls_po2_predict_map(&t, r[j], rx[j], ry[j], p, q, 0, L.data(), Bp.data()))) {
+          if (rr != PPLS_E_NUMERIC) return fail(c, rr, "PO2PLS prediction map of candidate %d refused", j);
+          status[o] = rr;
+          continue;
+        }
+        if ((rr = ppls_heldout_sse_fold(c, L.data(), t.C, Bp.data(), r[j], f, sse.data(), mag.data()))) return rr;
+        const double s1 = sse[(size_t)r[j] - 1];
+        rmsep[o] = std::sqrt(s1 / ((double)c->st_fN[(size_t)f] * q));
+        if (cond) cond[o] = mag[(size_t)r[j] - 1] / s1;
+      }
+    }
+    return PPLS_OK;
+  };
+  rc = run();
+  const std::string err = c->err;   // selected on all folds again, also after an error (whose message stays)
+  const int rs = fold_select(c, -1);
+  if (rc) c->err = err;
+  return rc ? rc : rs;
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@
 #include "ppls_math.h"
 
 #define PPLS_PO2_KMAX (2 * PPLS_RMAX)
+#define PPLS_PO2_BATCH_MAX 256   // models of one batched iteration
 
 // The scalars of theta (standard deviations, as in ppls_theta).
 struct PplsPo2Scalars {
@@ -44,7 +45,9 @@ struct PplsPo2Args {
   double* Gx;        // kx columns of ldx: W then Wo (padding rows zero)
   double* Gy;        // ky columns of ldy: C then Co
   PplsPo2Scalars* sc;
-  double* M;         // P x k, column-major, ld P
+  double* M;         // the X part of M = S G: P x kx, column-major, ld P
+  double* My;        // the Y part: P x ky, ld P.  One model alone: M + kx P (M is then P x k).  In a batch both lie
+                     // inside the batch's shared P x sum kx and P x sum ky buffers
   double* Q;         // k x k
   double* GGx;       // kx x kx
   double* GGy;       // ky x ky
@@ -79,5 +82,14 @@ hipError_t ppls_launch_po2_small(const PplsPo2Args* a, int pass, int mode, int c
 
 // The ECM loading updates from M, K and Czz (one workgroup per side; W then Wo, C then Co), orth by a->type.
 hipError_t ppls_launch_po2_update(const PplsPo2Args* a, hipStream_t st);
+
+// The same three kernel bodies over a batch of m models: args is a DEVICE array of m
+// PplsPo2Args, workgroup row blockIdx.y serves args[blockIdx.y].  Every model has its own stop pair, status,
+// scalars, moments and history; a model whose stop[0] is set returns at once in all three.  The Gram's grid is
+// (max_entries, m), max_entries = the largest k(k+1)/2 + kx(kx+1)/2 + ky(ky+1)/2 of the batch; workgroups past
+// a model's own count return.  pass, mode, check: as ppls_launch_po2_small, the same for every model.
+hipError_t ppls_launch_po2_gram_batch(const PplsPo2Args* args, int m, int max_entries, hipStream_t st);
+hipError_t ppls_launch_po2_small_batch(const PplsPo2Args* args, int m, int pass, int mode, int check, hipStream_t st);
+hipError_t ppls_launch_po2_update_batch(const PplsPo2Args* args, int m, hipStream_t st);
 
 }

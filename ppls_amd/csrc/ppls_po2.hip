@@ -18,6 +18,10 @@
 //
 // Loadings, scalars, moments and the log-likelihood history stay on the device; the stop rule follows
 // ppls_em_run's flag (every kernel returns at once when it is set).
+//
+// The Gram, small and update kernels are thin wrappers over __device__ bodies that take a PplsPo2Args; their
+// batched twins (ppls_po2_*_batch_kernel) read args[blockIdx.y] from a device array and call the
+// same bodies, one model per workgroup row, each model with its own stop flag.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -97,19 +101,22 @@ __device__ __forceinline__ void po2_tri(int t, int& a, int& b) {
   a = t - b * (b + 1) / 2;
 }
 
-__global__ __launch_bounds__(256) void ppls_po2_gram_kernel(PplsPo2Args g) {
+// The body serves ppls_po2_gram_kernel and its batched twin; workgroups past the model's own entry count
+// (a batch's grid is as wide as its largest model) return.
+__device__ __forceinline__ void po2_gram_body(const PplsPo2Args& g) {
   if (g.stop && *g.stop) return;
   __shared__ double red[4];
   const int kx = g.r + g.rx, ky = g.r + g.ry, k = kx + ky, P = g.ldx + g.ldy;
   const int nQ = k * (k + 1) / 2, nX = kx * (kx + 1) / 2;
   int t = blockIdx.x, a, b, rows, ldo;
+  if (t >= nQ + nX + ky * (ky + 1) / 2) return;
   const double *u, *v;
   double* out;
   if (t < nQ) {   // column a of G lives on the X rows (a < kx) or the Y rows
     po2_tri(t, a, b);
     rows = a < kx ? g.ldx : g.ldy;
     u = a < kx ? g.Gx + (int64_t)a * g.ldx : g.Gy + (int64_t)(a - kx) * g.ldy;
-    v = g.M + (int64_t)b * P + (a < kx ? 0 : g.ldx);
+    v = (b < kx ? g.M + (int64_t)b * P : g.My + (int64_t)(b - kx) * P) + (a < kx ? 0 : g.ldx);
     out = g.Q;
     ldo = k;
   } else if (t < nQ + nX) {
@@ -147,6 +154,12 @@ __global__ __launch_bounds__(256) void ppls_po2_gram_kernel(PplsPo2Args g) {
   }
 }
 
+__global__ __launch_bounds__(256) void ppls_po2_gram_kernel(PplsPo2Args g) { po2_gram_body(g); }
+__global__ __launch_bounds__(256) void ppls_po2_gram_batch_kernel(const PplsPo2Args* __restrict__ args) {
+  const PplsPo2Args g = args[blockIdx.y];   // wave-uniform: one copy in scalar registers
+  po2_gram_body(g);
+}
+
 // ---------------------------------------------------------------------------------------------- small
 __device__ __forceinline__ bool po2_pos(double v) { return v > 0.0 && isfinite(v); }
 
@@ -166,7 +179,7 @@ __device__ __forceinline__ double po2_sigz_inv(const PplsPo2Scalars& s, int r, i
   return 0.0;
 }
 
-__global__ __launch_bounds__(256) void ppls_po2_small_kernel(PplsPo2Args g, int pass, int mode, int check) {
+__device__ __forceinline__ void po2_small_body(const PplsPo2Args& g, int pass, int mode, int check) {
   if (g.stop && *g.stop) return;
   constexpr int KM = PPLS_PO2_KMAX;
   __shared__ double sA[KM * KM], sI[KM * KM], sK[KM * KM], sQ[KM * KM], sT[KM * KM], sC[KM * KM];
@@ -340,6 +353,15 @@ __global__ __launch_bounds__(256) void ppls_po2_small_kernel(PplsPo2Args g, int 
   g.sc->sH = sqrt(trh / (double)r);
 }
 
+__global__ __launch_bounds__(256) void ppls_po2_small_kernel(PplsPo2Args g, int pass, int mode, int check) {
+  po2_small_body(g, pass, mode, check);
+}
+__global__ __launch_bounds__(256) void ppls_po2_small_batch_kernel(const PplsPo2Args* __restrict__ args, int pass, int mode,
+                                                                   int check) {
+  const PplsPo2Args g = args[blockIdx.y];
+  po2_small_body(g, pass, mode, check);
+}
+
 // --------------------------------------------------------------------------------------------- update
 constexpr int PO2_UT = 1024;   // threads of the loading update's workgroup
 constexpr int PO2_C = PPLS_RMAX;
@@ -496,14 +518,15 @@ __device__ bool po2_orth_polar(double* __restrict__ Z, int ld, int n, int c, dou
 
 // Workgroup 0: W <- orth(Cxt - Wo Ctto'), then Wo <- orth(Cxto - W_new Ctto); workgroup 1 the same for
 // C, Co with Cuuo.  C_dz = M K / N row by row; the moments are those of the pass (g.sm).
-__global__ __launch_bounds__(PO2_UT) void ppls_po2_update_kernel(PplsPo2Args g) {
+__device__ __forceinline__ void po2_update_body(const PplsPo2Args& g) {
   if (g.stop && *g.stop) return;
   __shared__ double cK[PPLS_PO2_KMAX * PO2_C], cC[PO2_C * PO2_C], w[1536 + (PO2_UT / 64) * PO2_C];
   const int tid = threadIdx.x, side = blockIdx.x;
   const int r = g.r, kx = r + g.rx, k = kx + r + g.ry, P = g.ldx + g.ldy;
   const int n = side ? g.q : g.p, ld = side ? g.ldy : g.ldx, cs = side ? g.ry : g.rx, zoff = side ? kx : 0;
   double* G = side ? g.Gy : g.Gx;
-  const double* Mrow = g.M + (side ? g.ldx : 0);
+  const double* Mxrow = g.M + (side ? g.ldx : 0);   // this side's rows of the X and Y parts of M
+  const double* Myrow = g.My + (side ? g.ldx : 0);
   double* Z = g.Z + (side ? (int64_t)PO2_C * g.ldx : 0);
   for (int stage = 0; stage < 2; ++stage) {
     const int c = stage ? cs : r, koff = zoff + (stage ? r : 0);
@@ -523,7 +546,7 @@ __global__ __launch_bounds__(PO2_UT) void ppls_po2_update_kernel(PplsPo2Args g) 
 #pragma unroll
       for (int j = 0; j < PO2_C; ++j) acc[j] = 0.0;
       for (int a = 0; a < k; ++a) {
-        const double mv = Mrow[(int64_t)a * P + i];
+        const double mv = a < kx ? Mxrow[(int64_t)a * P + i] : Myrow[(int64_t)(a - kx) * P + i];
 #pragma unroll
         for (int j = 0; j < PO2_C; ++j)
           if (j < c) acc[j] = fma(mv, cK[a + j * PPLS_PO2_KMAX], acc[j]);
@@ -551,6 +574,12 @@ __global__ __launch_bounds__(PO2_UT) void ppls_po2_update_kernel(PplsPo2Args g) 
       return;
     }
   }
+}
+
+__global__ __launch_bounds__(PO2_UT) void ppls_po2_update_kernel(PplsPo2Args g) { po2_update_body(g); }
+__global__ __launch_bounds__(PO2_UT) void ppls_po2_update_batch_kernel(const PplsPo2Args* __restrict__ args) {
+  const PplsPo2Args g = args[blockIdx.y];
+  po2_update_body(g);
 }
 
 }  // namespace
@@ -590,6 +619,24 @@ hipError_t ppls_launch_po2_small(const PplsPo2Args* a, int pass, int mode, int c
 
 hipError_t ppls_launch_po2_update(const PplsPo2Args* a, hipStream_t st) {
   hipLaunchKernelGGL(ppls_po2_update_kernel, dim3(2), dim3(PO2_UT), 0, st, *a);
+  return hipGetLastError();
+}
+
+hipError_t ppls_launch_po2_gram_batch(const PplsPo2Args* args, int m, int max_entries, hipStream_t st) {
+  if (!args || m < 1 || m > PPLS_PO2_BATCH_MAX || max_entries < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ppls_po2_gram_batch_kernel, dim3((unsigned)max_entries, (unsigned)m), dim3(256), 0, st, args);
+  return hipGetLastError();
+}
+
+hipError_t ppls_launch_po2_small_batch(const PplsPo2Args* args, int m, int pass, int mode, int check, hipStream_t st) {
+  if (!args || m < 1 || m > PPLS_PO2_BATCH_MAX || pass < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ppls_po2_small_batch_kernel, dim3(1, (unsigned)m), dim3(256), 0, st, args, pass, mode, check);
+  return hipGetLastError();
+}
+
+hipError_t ppls_launch_po2_update_batch(const PplsPo2Args* args, int m, hipStream_t st) {
+  if (!args || m < 1 || m > PPLS_PO2_BATCH_MAX) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ppls_po2_update_batch_kernel, dim3(2, (unsigned)m), dim3(PO2_UT), 0, st, args);
   return hipGetLastError();
 }
 

@@ -1,4 +1,5 @@
-"""Host-side parts of PO2PLS (no GPU): the generator, the variation summary and the canonical form.
+"""Host-side parts of PO2PLS (no GPU): the generator, the variation summary, the canonical form, the prediction
+map and the grid selection rule of the cross-validation.
 
 The model is the reference's wider one (simulC, Package/PPLS/src/loglC.cpp:268-315):
     x = W t + P_Yosc t_o + e,   y = C u + P_Xosc u_o + f,   u = B t + h,
@@ -58,6 +59,61 @@ def canonical_PO2PLS(est):
         out[L] = A * np.where(A.sum(axis=0) < 0, -1.0, 1.0) if A.shape[1] else A
         out[s] = np.diag(sv[o])
     return out
+
+
+def po2_predict_map(estimates, XorY="X"):
+    """The linear map of a PO2PLS fit's prediction (``ppls_po2_predict_map``; host only).
+
+    ``XorY="X"``: (L, Bp) with E[y | x] = C diag(Bp) L'x, L (p x r) the first r columns of
+    Gx (diag(sigT, sigTo)^-2 + Gx'Gx / sigE^2)^-1 / sigE^2, Gx = [W Wo], and Bp = B.
+    ``XorY="Y"``: (L, Bp) with E[x | y] = W diag(1 / Bp) L'y, L (q x r) from Gy = [C Co], sigF and the
+    marginal variances sigT^2 b^2 + sigH^2, sigUo^2 of (u, uo); Bp = 1 / beta,
+    beta_j = sigT_j^2 b_j / (sigT_j^2 b_j^2 + sigH^2).
+    ``estimates``: a PO2PLS fit, its ``estimates`` dict or a ``Po2Theta``."""
+    import ctypes as ct
+
+    from . import _lib
+    xy = XorY if isinstance(XorY, str) else XorY[0]
+    if xy not in ("X", "Y"):
+        raise ValueError("'arg' should be one of \"X\", \"Y\"")
+    if isinstance(estimates, _lib.Po2Theta):
+        th = estimates
+    else:
+        th = _lib.Po2Theta.from_dict(estimates["estimates"] if "estimates" in estimates else estimates)
+    p, q, r = th.W.shape[0], th.C.shape[0], th.r
+    L = np.zeros((q if xy == "Y" else p, r), order="F")
+    Bp = np.zeros(r)
+    ts = th.struct()
+    rc = _lib.lib().ppls_po2_predict_map(ct.byref(ts), r, th.rx, th.ry, p, q, int(xy == "Y"), _lib.dptr(L), _lib.dptr(Bp))
+    if rc != 0:
+        raise _lib.PplsError(rc, "ppls_po2_predict_map: " + {-1: "sizes, a NULL loading, a non-finite value or a sigma not above 0",
+                                                              -3: "Lambda is not positive definite, or an entry of B is 0"}.get(rc, ""))
+    return L, Bp
+
+
+# Cells of a cross-validation grid whose fold-mean errors differ by less than this relative amount count as
+# equal (the mean of K roots of sums carries a few roundings; 64 u is far below any difference a model makes).
+GRID_TIE = 64 * 2.0 ** -53
+
+
+def select_grid_PO2PLS(per_fold, failed):
+    """The selection rule of ``crossval_PO2PLS`` on its arrays: ``per_fold`` (K x nr x nrx x nry) the RMSEP
+    of every fold and cell, ``failed`` (same shape, bool) where a start or fit failed.  Returns
+    (errors, which_error): ``errors`` the fold mean, NaN for a cell with any failed (or NaN) fold;
+    ``which_error`` the index triple of the first cell in grid order (C order: r slowest) whose error is
+    within ``GRID_TIE`` (relative) of the minimum over the finite cells -- so ties go to the cell listed
+    first -- or None when no cell is finite."""
+    per_fold = np.asarray(per_fold, dtype=np.float64)
+    failed = np.asarray(failed, dtype=bool)
+    if per_fold.ndim != 4 or failed.shape != per_fold.shape:
+        raise ValueError("per_fold and failed must be K x nr x nrx x nry")
+    bad = np.any(failed | ~np.isfinite(per_fold), axis=0)
+    errors = np.where(bad, np.nan, np.mean(np.where(bad[None], 0.0, per_fold), axis=0))
+    if np.all(bad):
+        return errors, None
+    lo = np.nanmin(errors)
+    hit = np.flatnonzero(np.ravel(~bad) & (np.ravel(np.nan_to_num(errors, nan=np.inf)) <= lo * (1.0 + GRID_TIE)))
+    return errors, tuple(int(v) for v in np.unravel_index(hit[0], errors.shape))
 
 
 def summary_PO2PLS(fit):
