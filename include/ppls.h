@@ -866,6 +866,44 @@ int ppls_po2_cv_stream(ppls_ctx* ctx, int ncand, const int* r, const int* rx, co
                        int type, const double* V0x, const double* V0y, int start_steps, double* rmsep, double* cond,
                        int* steps, int* status, ppls_po2_theta* fits);
 
+/* ---- PO2PLS row by row: diagnostics and the t-model weights --------------------------
+ * For a row (x, y) and a PO2PLS fit theta, Gx = [W Wo] = Qx Rx and Gy = [C Co] = Qy Ry (Householder QR on
+ * the host, fp64, R's diagonal positive; the loadings need not be orthonormal), a = Qx'x, b = Qy'y,
+ * R = blockdiag(Rx, Ry) and Sigma_c = R Sigma_z R' + diag(sigE^2 I_kx, sigF^2 I_ky), the covariance of (a; b):
+ *   odx2 = ||x - Qx a||^2, ody2 = ||y - Qy b||^2       (orthogonal distances, formed from the residual)
+ *   sd2  = ||Uc (a; b)||^2, Sigma_c^-1 = Uc'Uc, Uc upper triangular      (score distance, >= 0 as formed)
+ *   d2   = (odx2 / sigE^2 + ody2 / sigF^2) + sd2       (the squared Mahalanobis distance of (x; y))
+ *   loglik = -(p+q)/2 log 2 pi - logdet / 2 - d2 / 2,
+ *   logdet = (p-kx) log sigE^2 + (q-ky) log sigF^2 + log|Sigma_c|
+ *          = p log sigE^2 + q log sigF^2 + log|Sigma_z| + log|Lambda|        (DESIGN §26's),
+ * whose sum over all rows is ppls_po2_loglik's value on the same rows; mu = (a; b)' Kmu, Kmu = Sigma_c^-1 R
+ * Sigma_z = R K with §26's K: the posterior means [X Gx | Y Gy] K of z = (t, to, u, uo).  Under the model
+ * odx2/sigE^2, ody2/sigF^2, sd2 and d2 are chi-square with p-kx, q-ky, kx+ky and p+q degrees of freedom.
+ * One kernel pass over the rows, read in place (ppls_po2_rowdiag.hip); a row's results are bitwise the same
+ * whatever the other rows, the subset, the shard or the entry point (fp64 storage).  Every array is nullable.
+ * The row lists, NULL for all rows, the _new staging and PPLS_E_STATE on a context without rows are
+ * ppls_row_diagnostics{,_new}'s.  Unlike the other ppls_po2_* entries these read no S and form none; they end
+ * no ppls_em_begin session, change no option and leave the data bit for bit.
+ * PPLS_E_ARG, with the outputs (and the kept weights) untouched: sizes outside §26's, a NULL loading, a
+ * non-finite value, a sigma not above 0, a rank-deficient [W Wo] or [C Co] (a QR pivot with R_kk^2 <=
+ * 64 c u ||column k||^2, §26's rule), Sigma_c not positive definite, a row index out of range, NULL or
+ * non-finite rows. */
+typedef struct {
+  double *odx2, *ody2, *sd2, *d2, *loglik; /* nrows each, nullable */
+  double* mu;                              /* nrows x k column-major, order (t, to, u, uo), nullable */
+} ppls_po2_row_diag;
+int ppls_po2_row_diagnostics(ppls_ctx* ctx, const ppls_po2_theta* th, int r, int rx, int ry, const int64_t* rows,
+                             int64_t nrows, ppls_po2_row_diag* out);
+int ppls_po2_row_diagnostics_new(ppls_ctx* ctx, const ppls_po2_theta* th, int r, int rx, int ry, const double* X,
+                                 const double* Y, int64_t n, int layout, ppls_po2_row_diag* out);
+/* ppls_robust_weights under a PO2PLS fit: the distance pass above, then the same weight kernel on its three
+ * arrays.  The weights for nu[keep] and the distances go to the arrays ppls_robust_weights keeps (a row's d2
+ * has the bits ppls_po2_row_diagnostics reports), so ppls_robust_get and ppls_xprod_weighted(dst, src, NULL)
+ * work as they are and the same events drop them.  loglik_t[j] is §24's l_t with the logdet above; the m + 1
+ * sums and their all-reduce are §24's.  Refusals as above and §24's on m, nu and keep. */
+int ppls_po2_robust_weights(ppls_ctx* ctx, const ppls_po2_theta* th, int r, int rx, int ry, const double* nu, int m,
+                            int keep, double* loglik_t /* m */, double* sum_w /* nullable */);
+
 /* ---- host-side algebra (no GPU; the same code the device finalize runs) ------------------------ */
 /* From the all-reduced sufficient statistics of one sweep with theta (stats = [X'mu_T p x r |
  * Y'mu_U q x r | Gram 2r x 2r], all column-major) compute Expect_M's moments, logl_W(theta) and

@@ -328,6 +328,15 @@ int ppls_po2_timing_batch(ppls_ctx* ctx, int m, const ppls_po2_theta* th, const 
 int ppls_po2_stats_batch(ppls_ctx* ctx, const double* S, int P, int ldx, int m, const int* kx, const int* ky,
                          const double* Gx, const double* Gy, double* M, double* Q, double* GG);
 
+/* What ppls_po2_row_diagnostics runs for p, q columns of a storage type (f32: 0 or 1) and sizes (r, rx, ry):
+ * the tile (8 or 16) of the X block (kx = r + rx columns) and of the Y block (ky = r + ry), and the rows a
+ * wave owns at a time.  Host only.  PPLS_E_ARG: sizes outside §26's.  All outputs nullable. */
+int ppls_po2_rowdiag_info(int p, int q, int f32, int r, int rx, int ry, int* tile_x, int* tile_y, int* rows_per_wave);
+/* Benchmark (tools/bench_po2_rowdiag.py): the PO2PLS row kernel over all local rows at theta, reps launches
+ * between HIP events after one untimed launch; ms[0] = the average without, ms[1] with the posterior means
+ * written.  The results go to scratch of the call. */
+int ppls_po2_rowdiag_timing(ppls_ctx* ctx, const ppls_po2_theta* th, int r, int rx, int ry, int reps, double* ms /* [2] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@ from .api import (PPLS, Context, Expect_M, Maximiz_M, PPLS_simult, PPLS_simult_t
                   align_signs, bootstrap_summary, bootstrap_PPLS_simult, permutation_indices, permutation_pvalues,
                   permutation_PPLS, diagnostics_PPLS, robust_PPLS_simult, PO2PLS, PO2PLS_Expect, PO2PLS_logl,
                   simulate_PO2PLS, scores_PO2PLS, summary_PO2PLS, canonical_PO2PLS, po2_predict_map, predict_PO2PLS,
-                  cv_PO2PLS, crossval_PO2PLS)
+                  cv_PO2PLS, crossval_PO2PLS, diagnostics_PO2PLS, robust_PO2PLS)
 
 __all__ = ["Context", "fconstraint", "Expect_M", "Maximiz_M", "PPLS_simult", "PPLS", "PPLSi", "initial_guess", "print_PPLS", "scores_PPLS",
            "PPLS_simult_to_o2m", "PPLS_to_o2m", "meta_EMstep", "meta_PPLSi", "variances_PPLS_simult", "logl_W", "loglC_fast", "Theta",
@@ -20,4 +20,4 @@ __all__ = ["Context", "fconstraint", "Expect_M", "Maximiz_M", "PPLS_simult", "PP
            "bootstrap_counts", "align_signs", "bootstrap_summary", "bootstrap_PPLS_simult", "permutation_indices",
            "permutation_pvalues", "permutation_PPLS", "diagnostics_PPLS", "robust_PPLS_simult", "PO2PLS", "PO2PLS_Expect",
            "PO2PLS_logl", "simulate_PO2PLS", "scores_PO2PLS", "summary_PO2PLS", "canonical_PO2PLS", "po2_predict_map",
-           "predict_PO2PLS", "cv_PO2PLS", "crossval_PO2PLS"]
+           "predict_PO2PLS", "cv_PO2PLS", "crossval_PO2PLS", "diagnostics_PO2PLS", "robust_PO2PLS"]

@@ -59,6 +59,10 @@ class PplsRowDiag(ct.Structure):
     _fields_ = [("odx2", _dp), ("ody2", _dp), ("sd2", _dp), ("d2", _dp), ("loglik", _dp), ("mu_T", _dp), ("mu_U", _dp)]
 
 
+class PplsPo2RowDiag(ct.Structure):
+    _fields_ = [("odx2", _dp), ("ody2", _dp), ("sd2", _dp), ("d2", _dp), ("loglik", _dp), ("mu", _dp)]
+
+
 class PplsMetaFit(ct.Structure):
     _fields_ = [("W", _dp), ("C", _dp), ("params", _dp), ("log", _dp), ("steps", ct.c_int)]
 
@@ -255,6 +259,14 @@ SIGNATURES = {
     "ppls_po2_stats_batch": (ct.c_int, [ct.c_void_p, _dp, ct.c_int, ct.c_int, ct.c_int, _ip, _ip, _dp, _dp, _dp, _dp, _dp]),
     "ppls_po2_predict_map": (ct.c_int, [ct.POINTER(PplsPo2Theta), ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int,
                                         _dp, _dp]),
+    "ppls_po2_row_diagnostics": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsPo2Theta), ct.c_int, ct.c_int, ct.c_int, _i64p, ct.c_int64,
+                                            ct.POINTER(PplsPo2RowDiag)]),
+    "ppls_po2_row_diagnostics_new": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsPo2Theta), ct.c_int, ct.c_int, ct.c_int, _dp, _dp,
+                                                ct.c_int64, ct.c_int, ct.POINTER(PplsPo2RowDiag)]),
+    "ppls_po2_robust_weights": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsPo2Theta), ct.c_int, ct.c_int, ct.c_int, _dp, ct.c_int,
+                                           ct.c_int, _dp, _dp]),
+    "ppls_po2_rowdiag_info": (ct.c_int, [ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _ip, _ip, _ip]),
+    "ppls_po2_rowdiag_timing": (ct.c_int, [ct.c_void_p, ct.POINTER(PplsPo2Theta), ct.c_int, ct.c_int, ct.c_int, ct.c_int, _dp]),
     "ppls_po2_cv_stream": (ct.c_int, [ct.c_void_p, ct.c_int, _ip, _ip, _ip, ct.c_int, ct.c_double, ct.c_int, _dp, _dp, ct.c_int,
                                       _dp, _dp, _ip, _ip, ct.POINTER(PplsPo2Theta)]),
 }

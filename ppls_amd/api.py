@@ -1540,6 +1540,101 @@ class Context:
         self._chk(self._L.ppls_rowdiag_timing(self.h, int(r), int(reps), dptr(ms)))
         return dict(ms=ms[0], ms_mu=ms[1])
 
+    # -- PO2PLS row diagnostics and t-model weights
+    def _po2_rowdiag_out(self, n, k, want_mu):
+        """``_rowdiag_out`` for the PO2PLS entries: one ``mu`` of n x k."""
+        g = self._ROWDIAG_GUARD
+        bufs = {key: np.full(n + g, np.nan) for key in ("odx2", "ody2", "sd2", "d2", "loglik")}
+        if want_mu:
+            bufs["mu"] = np.full(n * k + g, np.nan)
+        self._rowdiag_last = bufs
+        return bufs, _lib.PplsPo2RowDiag(*[dptr(bufs.get(key)) for key in ("odx2", "ody2", "sd2", "d2", "loglik", "mu")])
+
+    def _po2_rowdiag_result(self, bufs, n, k):
+        g = self._ROWDIAG_GUARD
+        out = {}
+        for key, b in bufs.items():
+            if not np.all(np.isnan(b[b.shape[0] - g:])):
+                raise PplsError(-1, f"row diagnostics wrote past the end of {key}")
+            out[key] = b[: n * k].reshape((n, k), order="F") if key == "mu" else b[:n]
+        return out
+
+    def po2_row_diagnostics(self, th: Po2Theta, rows=None, want_mu=False):
+        """``row_diagnostics`` under a PO2PLS fit (ppls_po2_row_diagnostics): ``odx2``, ``ody2`` are the squared
+        distances to the planes of [W Wo] and [C Co], ``sd2`` the distance of the k = 2r + rx + ry scores under
+        their dense covariance, ``d2`` and ``loglik`` as there (the sum of ``loglik`` over all rows is
+        ``po2_loglik(th)``); with ``want_mu`` the posterior means ``mu`` (n x k, columns t, to, u, uo).  The
+        loadings need not be orthonormal.  Reads no S and forms none."""
+        if rows is None:
+            n, rp = int(self.n_local), None
+        else:
+            rows, rp = self._rows(rows)
+            n = rows.shape[0]
+            if n == 0:
+                rp = None
+        k = 2 * th.r + th.rx + th.ry
+        bufs, s = self._po2_rowdiag_out(n, k, want_mu)
+        t = th.struct()
+        if rows is not None and n == 0:   # an empty list is not "all rows"
+            return self._po2_rowdiag_result(bufs, 0, k)
+        self._chk(self._L.ppls_po2_row_diagnostics(self.h, ct.byref(t), th.r, th.rx, th.ry, rp, n, ct.byref(s)))
+        return self._po2_rowdiag_result(bufs, n, k)
+
+    def po2_row_diagnostics_new(self, th: Po2Theta, X, Y, want_mu=False):
+        """The same for host rows ``X, Y`` in the fit's units (ppls_po2_row_diagnostics_new), staged as
+        ``row_diagnostics_new`` stages them: any context of the fit's shape serves."""
+        X = np.asarray(X, dtype=np.float64)
+        Y = np.asarray(Y, dtype=np.float64)
+        if X.ndim != 2 or Y.ndim != 2 or X.shape[0] != Y.shape[0]:
+            raise ValueError("X and Y must be matrices with the same number of rows")
+        if X.shape[1] != self.p or Y.shape[1] != self.q:
+            raise ValueError("Number of columns mismatch!")
+        if X.flags.f_contiguous and Y.flags.f_contiguous and not (X.flags.c_contiguous and Y.flags.c_contiguous):
+            layout = _lib.PPLS_LAYOUT_COLMAJOR
+        else:
+            X = np.ascontiguousarray(X)
+            Y = np.ascontiguousarray(Y)
+            layout = _lib.PPLS_LAYOUT_ROWMAJOR
+        n = X.shape[0]
+        k = 2 * th.r + th.rx + th.ry
+        bufs, s = self._po2_rowdiag_out(n, k, want_mu)
+        t = th.struct()
+        self._chk(self._L.ppls_po2_row_diagnostics_new(self.h, ct.byref(t), th.r, th.rx, th.ry, dptr(X), dptr(Y), n, layout,
+                                                       ct.byref(s)))
+        return self._po2_rowdiag_result(bufs, n, k)
+
+    def po2_robust_weights(self, th: Po2Theta, nu=4.0, keep=0):
+        """``robust_weights`` under a PO2PLS fit (ppls_po2_robust_weights): the distance pass of
+        ``po2_row_diagnostics`` and the same weight kernel.  The weights and distances are kept where
+        ``robust_weights`` keeps them: ``robust_get`` and ``xprod_weighted(src, None)`` work as they are."""
+        nus = np.ascontiguousarray(np.atleast_1d(np.asarray(nu, dtype=np.float64)))
+        g = self._ROWDIAG_GUARD
+        ll = np.full(nus.shape[0] + g, np.nan)
+        sw = np.full(1 + g, np.nan)
+        self._robust_last = (ll, sw)
+        t = th.struct()
+        self._chk(self._L.ppls_po2_robust_weights(self.h, ct.byref(t), th.r, th.rx, th.ry, dptr(nus), nus.shape[0], int(keep),
+                                                  dptr(ll), dptr(sw)))
+        if not (np.all(np.isnan(ll[nus.shape[0]:])) and np.all(np.isnan(sw[1:]))):
+            raise PplsError(-1, "po2_robust_weights wrote past the end of its outputs")
+        return ll[: nus.shape[0]].copy(), float(sw[0])
+
+    def po2_rowdiag_info(self, r, rx, ry, f32=False):
+        """What ``po2_row_diagnostics`` runs for these sizes on this context's shape and fp64 (``f32``: fp32)
+        storage (ppls_po2_rowdiag_info): dict(tile_x, tile_y, rows_per_wave)."""
+        tx, ty, rw = ct.c_int(), ct.c_int(), ct.c_int()
+        self._chk(self._L.ppls_po2_rowdiag_info(self.p, self.q, int(bool(f32)), int(r), int(rx), int(ry), ct.byref(tx), ct.byref(ty),
+                                                ct.byref(rw)))
+        return dict(tile_x=tx.value, tile_y=ty.value, rows_per_wave=rw.value)
+
+    def po2_rowdiag_timing(self, th: Po2Theta, reps=20):
+        """The PO2PLS row kernel alone over all local rows, ms between HIP events averaged over ``reps``
+        launches (ppls_po2_rowdiag_timing): dict(ms, ms_mu) without and with the posterior means."""
+        ms = np.zeros(2)
+        t = th.struct()
+        self._chk(self._L.ppls_po2_rowdiag_timing(self.h, ct.byref(t), th.r, th.rx, th.ry, int(reps), dptr(ms)))
+        return dict(ms=ms[0], ms_mu=ms[1])
+
     def cv_ppls(self, a: int, fold_of_row, fold_total, max_steps: int, atol: float, inits, crit_abs=False):
         """cv_PPLS's loop for given folds (ppls_cv_ppls).  ``fold_of_row``: the fold of each local
         row; ``fold_total``: rows per fold over all ranks; ``inits``: per fold a list of ``a``
@@ -3167,14 +3262,15 @@ def chisq_upper(x, df):
     return np.asarray(scipy.special.gammaincc(0.5 * df, 0.5 * np.maximum(x, 0.0)), dtype=np.float64)
 
 
-def diagnostics_summary(res, p, q, r, sigE, sigF, alpha=0.01, adjust="none"):
+def diagnostics_summary(res, p, q, r, sigE, sigF, alpha=0.01, adjust="none", df=None):
     """``df``, ``pvalue``, ``flag`` and ``outliers`` from the distances of one diagnostics call (the host
-    part of ``diagnostics_PPLS``).  ``adjust="bonferroni"`` tests at ``alpha / n``, n the rows of this call."""
+    part of ``diagnostics_PPLS``).  ``adjust="bonferroni"`` tests at ``alpha / n``, n the rows of this call.
+    ``df``: the degrees of freedom when they are not ``diagnostics_df(p, q, r)``'s."""
     if adjust not in ("none", "bonferroni"):
         raise ValueError("adjust should be one of \"none\", \"bonferroni\"")
     n = int(np.asarray(res["d2"]).shape[0])
     level = float(alpha) / n if adjust == "bonferroni" and n > 0 else float(alpha)
-    df = diagnostics_df(p, q, r)
+    df = diagnostics_df(p, q, r) if df is None else df
     stat = dict(odx2=np.asarray(res["odx2"]) / (float(sigE) * float(sigE)),
                 ody2=np.asarray(res["ody2"]) / (float(sigF) * float(sigF)), sd2=np.asarray(res["sd2"]),
                 d2=np.asarray(res["d2"]))
@@ -3184,34 +3280,10 @@ def diagnostics_summary(res, p, q, r, sigE, sigF, alpha=0.01, adjust="none"):
     return dict(df=df, pvalue=pv, flag=flag, outliers=hit[np.argsort(pv["d2"][hit], kind="stable")])
 
 
-def diagnostics_PPLS(fit, X=None, Y=None, ctx=None, subset=None, new=False, rescale=False, alpha=0.01, adjust="none",
-                     want_mu=False, Z=None):
-    """Which rows does a ``PPLS_simult`` fit not explain?  Per row, on the GPU in one pass over the rows:
-    the squared Mahalanobis distance ``d2`` under the fitted covariance, its in-plane part ``sd2`` (score
-    distance) and off-plane parts ``odx2``, ``ody2`` (squared orthogonal distances in X and Y) and the
-    log-density ``loglik``, which sums to ``logl_W``; with ``want_mu`` Expect_M's ``mu_T``, ``mu_U``.  On
-    the host: ``df``, upper chi-square ``pvalue`` and ``flag`` (``p < alpha``, or ``p < alpha / n`` with
-    ``adjust="bonferroni"``) per distance, and ``outliers``, the rows with ``flag["d2"]`` sorted by p.
-
-    ``fit``: a ``PPLS_simult`` fit or a ``Theta``.  ``X, Y`` given: loaded into the context and scored;
-    ``X=None``: the rows resident in ``ctx``; ``subset``: 0-based local row indices.  ``new=True``: ``X, Y``
-    are rows scored against the fit without touching the context's data (any context of the fit's shape:
-    streamed, or without rows); with ``rescale=True`` they come in the units the data were loaded in and
-    are brought to the fit's with ``ctx.scaling()`` on the host, as ``predict_PPLS`` does -- called once
-    per chunk this is the second pass that screens a ``stream_data`` fit.  On a context whose data were
-    adjusted for covariates ``rescale=True`` needs ``Z``, the new rows' covariates (``adjust_new``)."""
+def _diagnostics_rows(p, q, X, Y, ctx, subset, new, rescale, Z, resident, fresh):
+    """The rows of a diagnostics call and the context that scores them, as ``diagnostics_PPLS`` documents:
+    ``resident(ctx, subset)`` on rows a context holds, ``fresh(ctx, X, Y)`` on new rows in the fit's units."""
     global _PREDICT_CTX
-    if adjust not in ("none", "bonferroni"):
-        raise ValueError("adjust should be one of \"none\", \"bonferroni\"")
-    if isinstance(fit, Theta):
-        th = fit
-    elif isinstance(fit, dict) and "estimates" in fit:
-        e = fit["estimates"]
-        th = Theta(e["W"], e["C"], e["B"], e["sigE"], e["sigF"], e["sigH"], e["sigT"])
-    else:
-        raise ValueError("diagnostics need one joint covariance: pass a PPLS_simult fit (or a Theta); the components "
-                         "of a sequential PPLS / PPLSi fit carry their own sigmas")
-    p, q, r = th.W.shape[0], th.C.shape[0], th.r
     if new:
         if X is None or Y is None:
             raise ValueError("new=True needs the rows X and Y")
@@ -3244,14 +3316,45 @@ def diagnostics_PPLS(fit, X=None, Y=None, ctx=None, subset=None, new=False, resc
             sc = ctx.scaling()
             X = (X - sc["centerX"]) / sc["scaleX"]
             Y = (Y - sc["centerY"]) / sc["scaleY"]
-        res = ctx.row_diagnostics_new(th, X, Y, want_mu=want_mu)
+        return fresh(ctx, X, Y)
+    if X is not None and (np.ndim(X) != 2 or np.ndim(Y) != 2 or np.shape(X)[1] != p or np.shape(Y)[1] != q):
+        raise ValueError("Number of columns mismatch!")
+    ctx = _ctx_with(X, Y, ctx)
+    if (ctx.p, ctx.q) != (p, q):
+        raise ValueError("Number of columns mismatch!")
+    return resident(ctx, subset)
+
+
+def diagnostics_PPLS(fit, X=None, Y=None, ctx=None, subset=None, new=False, rescale=False, alpha=0.01, adjust="none",
+                     want_mu=False, Z=None):
+    """Which rows does a ``PPLS_simult`` fit not explain?  Per row, on the GPU in one pass over the rows:
+    the squared Mahalanobis distance ``d2`` under the fitted covariance, its in-plane part ``sd2`` (score
+    distance) and off-plane parts ``odx2``, ``ody2`` (squared orthogonal distances in X and Y) and the
+    log-density ``loglik``, which sums to ``logl_W``; with ``want_mu`` Expect_M's ``mu_T``, ``mu_U``.  On
+    the host: ``df``, upper chi-square ``pvalue`` and ``flag`` (``p < alpha``, or ``p < alpha / n`` with
+    ``adjust="bonferroni"``) per distance, and ``outliers``, the rows with ``flag["d2"]`` sorted by p.
+
+    ``fit``: a ``PPLS_simult`` fit or a ``Theta``.  ``X, Y`` given: loaded into the context and scored;
+    ``X=None``: the rows resident in ``ctx``; ``subset``: 0-based local row indices.  ``new=True``: ``X, Y``
+    are rows scored against the fit without touching the context's data (any context of the fit's shape:
+    streamed, or without rows); with ``rescale=True`` they come in the units the data were loaded in and
+    are brought to the fit's with ``ctx.scaling()`` on the host, as ``predict_PPLS`` does -- called once
+    per chunk this is the second pass that screens a ``stream_data`` fit.  On a context whose data were
+    adjusted for covariates ``rescale=True`` needs ``Z``, the new rows' covariates (``adjust_new``)."""
+    if adjust not in ("none", "bonferroni"):
+        raise ValueError("adjust should be one of \"none\", \"bonferroni\"")
+    if isinstance(fit, Theta):
+        th = fit
+    elif isinstance(fit, dict) and "estimates" in fit:
+        e = fit["estimates"]
+        th = Theta(e["W"], e["C"], e["B"], e["sigE"], e["sigF"], e["sigH"], e["sigT"])
     else:
-        if X is not None and (np.ndim(X) != 2 or np.ndim(Y) != 2 or np.shape(X)[1] != p or np.shape(Y)[1] != q):
-            raise ValueError("Number of columns mismatch!")
-        ctx = _ctx_with(X, Y, ctx)
-        if (ctx.p, ctx.q) != (p, q):
-            raise ValueError("Number of columns mismatch!")
-        res = ctx.row_diagnostics(th, rows=subset, want_mu=want_mu)
+        raise ValueError("diagnostics need one joint covariance: pass a PPLS_simult fit (or a Theta); the components "
+                         "of a sequential PPLS / PPLSi fit carry their own sigmas")
+    p, q, r = th.W.shape[0], th.C.shape[0], th.r
+    res = _diagnostics_rows(p, q, X, Y, ctx, subset, new, rescale, Z,
+                            lambda c, rows: c.row_diagnostics(th, rows=rows, want_mu=want_mu),
+                            lambda c, Xn, Yn: c.row_diagnostics_new(th, Xn, Yn, want_mu=want_mu))
     out = dict(res)
     out.update(diagnostics_summary(res, p, q, r, th.sigE, th.sigF, alpha=alpha, adjust=adjust))
     return out
@@ -3432,3 +3535,96 @@ def scores_PO2PLS(fit, X=None, Y=None, ctx=None):
     Gxp[:, :kx], Gyp[:, :ky] = Gx, Gy
     T, Us = ctx.scores(Gxp, Gyp)
     return np.hstack([T[:, :kx], Us[:, :ky]]) @ np.asarray(fit["Expectations"]["K"])
+
+
+def _po2_fit_theta(fit):
+    if isinstance(fit, Po2Theta):
+        return fit
+    if isinstance(fit, dict):
+        return Po2Theta.from_dict(fit["estimates"] if "estimates" in fit else fit)
+    raise ValueError("pass a PO2PLS fit, its estimates or a Po2Theta")
+
+
+def diagnostics_PO2PLS(fit, X=None, Y=None, ctx=None, subset=None, new=False, rescale=False, alpha=0.01, adjust="none",
+                       want_mu=False, Z=None):
+    """``diagnostics_PPLS`` for a PO2PLS fit: per row, in one pass over the rows on the GPU, the
+    squared distances ``odx2``, ``ody2`` to the planes of [W Wo] and [C Co], the distance ``sd2`` of the
+    k = 2r + rx + ry scores under their dense covariance, ``d2``, the log-density ``loglik`` (it sums to
+    ``PO2PLS_logl``) and, with ``want_mu``, the posterior means ``mu`` (n x k: t, to, u, uo).  ``df`` is
+    p - kx, q - ky, kx + ky and p + q; ``pvalue``, ``flag``, ``outliers`` and every other argument are
+    ``diagnostics_PPLS``'s.  ``fit``: a PO2PLS fit, its ``estimates`` or a ``Po2Theta``; the loadings need not
+    be orthonormal."""
+    if adjust not in ("none", "bonferroni"):
+        raise ValueError("adjust should be one of \"none\", \"bonferroni\"")
+    th = _po2_fit_theta(fit)
+    p, q, kx, ky = th.W.shape[0], th.C.shape[0], th.r + th.rx, th.r + th.ry
+    res = _diagnostics_rows(p, q, X, Y, ctx, subset, new, rescale, Z,
+                            lambda c, rows: c.po2_row_diagnostics(th, rows=rows, want_mu=want_mu),
+                            lambda c, Xn, Yn: c.po2_row_diagnostics_new(th, Xn, Yn, want_mu=want_mu))
+    out = dict(res)
+    out.update(diagnostics_summary(res, p, q, th.r, th.sigE, th.sigF, alpha=alpha, adjust=adjust,
+                                   df=dict(odx2=p - kx, ody2=q - ky, sd2=kx + ky, d2=p + q)))
+    return out
+
+
+def robust_PO2PLS(X, Y, r, rx, ry, nu=4.0, outer=50, inner=5, atol=1e-4, type="SVD", init=None, ctx=None, work=None,
+                  rng=None):
+    """PO2PLS under the multivariate-t model with ``nu`` degrees of freedom: ``robust_PPLS_simult``'s loop
+     with the PO2PLS distances and M-step.  From theta (``init``: a dict as for
+    ``PO2PLS``, default the estimates of ``PO2PLS(X, Y, r, rx, ry)`` on the same context) it repeats:
+    (1) ``ctx.po2_robust_weights`` -- d2_i, u_i = (nu + p + q) / (nu + d2_i) and the t log-likelihood at theta;
+    (2) ``work.xprod_weighted(ctx)`` -- S_u = sum u_i d_i d_i' with ``n_total = N``; (3) ``inner`` forced ECM
+    steps of ``work.po2_em_run``, warm-started at theta.  The stop rule, ``nu="estimate"``, ``X``, ``Y``,
+    ``ctx`` and ``work`` are ``robust_PPLS_simult``'s; ``rng`` draws the default start's specific loadings, as
+    in ``PO2PLS``.
+
+    Returns ``dict(estimates, loglik, nu, weights, d2, steps, converged, gaussian)``: ``estimates`` in PO2PLS's
+    canonical form; ``gaussian`` the starting PO2PLS fit (None when ``init`` was given)."""
+    estimate = isinstance(nu, str)
+    if estimate and nu != "estimate":
+        raise ValueError("nu must be a positive number or 'estimate'")
+    if not estimate and not (np.isfinite(nu) and nu > 0):
+        raise ValueError(f"nu = {nu} must be positive and finite")
+    if outer < 1 or inner < 1:
+        raise ValueError(f"outer = {outer}, inner = {inner} must be at least 1")
+    ctx = _ctx_with(X, Y, ctx)
+    t = _orth_type(type)
+    gauss = None
+    if init is None:
+        gauss = PO2PLS(None, None, r, rx, ry, type=type, rng=rng, ctx=ctx)
+        init = gauss["estimates"]
+    th = Po2Theta.from_dict(init)
+    if (th.r, th.rx, th.ry) != (int(r), int(rx), int(ry)):
+        raise ValueError(f"init has (r, rx, ry) = {(th.r, th.rx, th.ry)}, asked for {(int(r), int(rx), int(ry))}")
+
+    def estep(th):
+        if not estimate:
+            return float(nu), float(ctx.po2_robust_weights(th, nu)[0][0])
+        lo, hi = 1.0, 1000.0
+        for _ in range(4):
+            grid = t_nu_grid(lo, hi)
+            k = int(np.argmax(ctx.po2_robust_weights(th, grid)[0]))
+            lo, hi = t_nu_bracket(grid, k)
+        return float(grid[k]), float(ctx.po2_robust_weights(th, grid[k])[0][0])   # keeps the weights of the chosen nu
+
+    own = work is None
+    work = Context(ctx.device) if own else work
+    ll, steps, converged = [], 0, False
+    try:
+        while True:
+            nu_k, l = estep(th)
+            ll.append(l)
+            if len(ll) > 1 and ll[-1] - ll[-2] < atol:
+                converged = True
+                break
+            if steps >= outer:
+                break
+            work.xprod_weighted(ctx)
+            th = work.po2_em_run(th, int(inner), -np.inf, t, want_eout=False)[0]
+            steps += 1
+    finally:
+        if own:
+            work.close()
+    w, d2 = ctx.robust_get()
+    return {"estimates": th.as_dict(), "loglik": np.array(ll), "nu": nu_k, "weights": w, "d2": d2, "steps": steps,
+            "converged": converged, "gaussian": gauss, "class": "robust_PO2PLS"}

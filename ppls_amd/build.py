@@ -19,7 +19,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 SOURCES = ["ppls_kernels.hip", "ppls_variances.hip", "ppls_xprod.hip", "ppls_xprod_meta.hip", "ppls_linalg.hip",
            "ppls_varxprod.hip", "ppls_ozaki.hip", "ppls_cv.hip", "ppls_scale.hip", "ppls_stream.hip", "ppls_cvstream.hip", "ppls_o2m.hip",
-           "ppls_permute.hip", "ppls_rowdiag.hip", "ppls_robust.hip", "ppls_adjust.hip", "ppls_po2.hip", "ppls_capi.cpp"]
+           "ppls_permute.hip", "ppls_rowdiag.hip", "ppls_robust.hip", "ppls_adjust.hip", "ppls_po2.hip", "ppls_po2_rowdiag.hip",
+           "ppls_capi.cpp"]
 # Per-file flags.  ppls_kernels.hip: the panel dots kernel keeps its MFMA accumulators in VGPRs
 # (the default AGPR form copied them VGPR <-> AGPR on every tile; its only MFMA user).
 FILE_FLAGS = {"ppls_kernels.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}

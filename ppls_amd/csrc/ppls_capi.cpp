@@ -28,6 +28,7 @@
 #include "ppls_math.h"
 #include "ppls_cv.h"
 #include "ppls_robust.h"
+#include "ppls_po2_rowdiag.h"
 #include "ppls_rowdiag.h"
 #include "ppls_o2m.h"
 #include "ppls_permute.h"
@@ -1567,37 +1568,49 @@ bool theta_finite(const ppls_theta* th, int p, int q, int r) {
   return ok;
 }
 
+// Sequential Householder QR of the n x c matrix S (ld n, c <= n): E becomes the first c columns of Q (n x c) and
+// R the c x c factor (column-major, upper; its diagonal carries the reflectors' signs).  floor2: per column,
+// what the squared norm of the pivot column must exceed (NULL: 0).  Returns the first column whose pivot does
+// not, or -1.
+int host_householder(const double* S, int n, int c, const double* floor2, std::vector<double>& E, double* R) {
+  std::vector<double> A(S, S + (size_t)n * c), vtv(c);
+  std::fill(R, R + (size_t)c * c, 0.0);
+  for (int k = 0; k < c; ++k) {
+    double s2 = 0.0;
+    for (int i = k; i < n; ++i) s2 += A[(size_t)k * n + i] * A[(size_t)k * n + i];
+    const double sig = std::sqrt(s2), akk = A[(size_t)k * n + k];
+    if (!(s2 > (floor2 ? floor2[k] : 0.0))) return k;
+    const bool last = k == n - 1;   // nothing to reflect: R_kk = a_kk (dqrdc2, dlarfg), H_k = I
+    const double alpha = last ? akk : akk >= 0.0 ? -sig : sig;
+    vtv[k] = last ? 0.0 : 2.0 * sig * (sig + std::fabs(akk));
+    A[(size_t)k * n + k] = akk - alpha;
+    R[k * c + k] = alpha;
+    for (int j = k + 1; j < c; ++j) {
+      double d = 0.0;
+      for (int i = k; i < n; ++i) d += A[(size_t)k * n + i] * A[(size_t)j * n + i];
+      const double f = 2.0 * d / vtv[k];
+      for (int i = k; i < n; ++i) A[(size_t)j * n + i] -= f * A[(size_t)k * n + i];
+      R[j * c + k] = A[(size_t)j * n + k];
+    }
+  }
+  E.assign((size_t)n * c, 0.0);
+  for (int j = 0; j < c; ++j) E[(size_t)j * n + j] = 1.0;
+  for (int k = c - 1; k >= 0; --k)
+    for (int j = 0; j < c; ++j) {
+      double d = 0.0;
+      for (int i = k; i < n; ++i) d += A[(size_t)k * n + i] * E[(size_t)j * n + i];
+      const double f = vtv[k] > 0.0 ? 2.0 * d / vtv[k] : 0.0;
+      for (int i = k; i < n; ++i) E[(size_t)j * n + i] -= f * A[(size_t)k * n + i];
+    }
+  return -1;
+}
+
 // Host polar factor / QR factor of the p x r matrix S (ld p): sequential Householder QR, then the
 // same small Jacobi polar as the device.  out: p x r.
 int host_orth(const double* S, int p, int r, int type, double* out) {
-  std::vector<double> A(S, S + (size_t)p * r), E((size_t)p * r, 0.0), vtv(r);
-  double R[PPLS_RMAX * PPLS_RMAX] = {0}, P[PPLS_RMAX * PPLS_RMAX];
-  for (int k = 0; k < r; ++k) {
-    double s2 = 0.0;
-    for (int i = k; i < p; ++i) s2 += A[(size_t)k * p + i] * A[(size_t)k * p + i];
-    const double sig = std::sqrt(s2), akk = A[(size_t)k * p + k];
-    if (!(sig > 0.0)) return PPLS_E_NUMERIC;
-    const bool last = k == p - 1;   // nothing to reflect: R_kk = a_kk (dqrdc2, dlarfg), H_k = I
-    const double alpha = last ? akk : akk >= 0.0 ? -sig : sig;
-    vtv[k] = last ? 0.0 : 2.0 * sig * (sig + std::fabs(akk));
-    A[(size_t)k * p + k] = akk - alpha;
-    R[k * r + k] = alpha;
-    for (int j = k + 1; j < r; ++j) {
-      double d = 0.0;
-      for (int i = k; i < p; ++i) d += A[(size_t)k * p + i] * A[(size_t)j * p + i];
-      const double f = 2.0 * d / vtv[k];
-      for (int i = k; i < p; ++i) A[(size_t)j * p + i] -= f * A[(size_t)k * p + i];
-      R[j * r + k] = A[(size_t)j * p + k];
-    }
-  }
-  for (int j = 0; j < r; ++j) E[(size_t)j * p + j] = 1.0;
-  for (int k = r - 1; k >= 0; --k)
-    for (int j = 0; j < r; ++j) {
-      double d = 0.0;
-      for (int i = k; i < p; ++i) d += A[(size_t)k * p + i] * E[(size_t)j * p + i];
-      const double f = vtv[k] > 0.0 ? 2.0 * d / vtv[k] : 0.0;
-      for (int i = k; i < p; ++i) E[(size_t)j * p + i] -= f * A[(size_t)k * p + i];
-    }
+  std::vector<double> E;
+  double R[PPLS_RMAX * PPLS_RMAX], P[PPLS_RMAX * PPLS_RMAX];
+  if (host_householder(S, p, r, nullptr, E, R) >= 0) return PPLS_E_NUMERIC;
   if (type == PPLS_ORTH_QR) {   // sign_e * qr.Q(qr(S)), sign_e = sign(<e_1, S_1>) = sign(R_11) (functions.R:257-259)
     const double sg = R[0] < 0.0 ? -1.0 : 1.0;
     for (size_t e = 0; e < E.size(); ++e) out[e] = sg * E[e];
@@ -5416,6 +5429,56 @@ int rowdiag_device(ppls_ctx* c, CvScratch& tmp, const ppls_theta* th, int r, con
   return PPLS_OK;
 }
 
+// What ppls_robust_weights and ppls_po2_robust_weights do once the fit has passed its checks: §24's checks on m,
+// nu and keep, every allocation, the distance pass (pass(tmp, n, &res) queues it on the context stream and
+// gives res = [odx2 | ody2 | sd2], n each), the weight kernel, the all-reduce of the m + 1 sums and l_t.
+template <class Pass>
+int robust_weights_run(ppls_ctx* c, const double* nu, int m, int keep, double* loglik_t, double* sum_w, double sE2, double sF2,
+                       double logdet, Pass&& pass) {
+  int rc;
+  if (m < 1 || m > PPLS_ROBUST_MAXNU) return fail(c, PPLS_E_ARG, "m=%d values of nu outside [1, %d]", m, PPLS_ROBUST_MAXNU);
+  if (keep < 0 || keep >= m) return fail(c, PPLS_E_ARG, "keep=%d outside [0, %d)", keep, m);
+  PplsRobustNu nus;
+  memset(&nus, 0, sizeof nus);
+  for (int j = 0; j < m; ++j) {
+    if (!(nu[j] > 0.0) || !std::isfinite(nu[j])) return fail(c, PPLS_E_ARG, "nu[%d] = %g must be positive and finite", j, nu[j]);
+    nus.nu[j] = nu[j];
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const int64_t n = c->n_local;
+  // every allocation before the kept weights are touched
+  CvScratch tmp;
+  double *part = nullptr, *sums = nullptr, *res = nullptr;
+  if ((rc = tmp.get(c, &part, (size_t)ppls_robust_blocks(n) * PPLS_ROBUST_SUMS))) return rc;
+  if ((rc = tmp.get(c, &sums, (size_t)PPLS_ROBUST_SUMS))) return rc;
+  if (c->rb_len < n || !c->rb_w || !c->rb_d2) {
+    c->rb_kept = false;
+    c->rb_len = 0;
+    if ((rc = dalloc(c, &c->rb_w, (size_t)std::max<int64_t>(n, 1)))) return rc;
+    if ((rc = dalloc(c, &c->rb_d2, (size_t)std::max<int64_t>(n, 1)))) return rc;
+    c->rb_len = std::max<int64_t>(n, 1);
+  }
+  if (n > 0 && (rc = pass(tmp, n, &res))) return rc;
+  c->rb_kept = false;   // from here the kept arrays are overwritten
+  const double P = (double)(c->p + c->q);
+  const int grid = c->rb_grid > 0 ? c->rb_grid : ppls_robust_grid(n, c->num_cus);
+  HIPCHK(c, ppls_launch_robust_weights(res, res ? res + n : nullptr, res ? res + 2 * n : nullptr, n, sE2, sF2, &nus, m, keep,
+                                       P, c->rb_w, c->rb_d2, part, sums, grid, c->stream));
+  if ((rc = allreduce(c, sums, (size_t)PPLS_ROBUST_SUMS))) return rc;
+  double hs[PPLS_ROBUST_SUMS];
+  HIPCHK(c, hipMemcpyAsync(hs, sums, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const double N = (double)c->n_total;
+  for (int j = 0; j < m; ++j) {
+    const double v = nu[j];
+    const double cst = std::lgamma(0.5 * (v + P)) - std::lgamma(0.5 * v) - 0.5 * P * std::log(v * 3.141592653589793);
+    loglik_t[j] = (N * cst - 0.5 * N * logdet) - 0.5 * (v + P) * hs[j];
+  }
+  if (sum_w) *sum_w = hs[PPLS_ROBUST_MAXNU];
+  c->rb_kept = true;
+  return PPLS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -5458,47 +5521,10 @@ int ppls_robust_weights(ppls_ctx* c, const ppls_theta* th, int r, const double* 
   RowDiagFit f;
   int rc;
   if ((rc = rowdiag_check_fit(c, th, r, h, f))) return rc;
-  if (m < 1 || m > PPLS_ROBUST_MAXNU) return fail(c, PPLS_E_ARG, "m=%d values of nu outside [1, %d]", m, PPLS_ROBUST_MAXNU);
-  if (keep < 0 || keep >= m) return fail(c, PPLS_E_ARG, "keep=%d outside [0, %d)", keep, m);
-  PplsRobustNu nus;
-  memset(&nus, 0, sizeof nus);
-  for (int j = 0; j < m; ++j) {
-    if (!(nu[j] > 0.0) || !std::isfinite(nu[j])) return fail(c, PPLS_E_ARG, "nu[%d] = %g must be positive and finite", j, nu[j]);
-    nus.nu[j] = nu[j];
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  const int64_t n = c->n_local;
-  // every allocation before the kept weights are touched
-  CvScratch tmp;
-  double *part = nullptr, *sums = nullptr, *res = nullptr, *dmu = nullptr;
-  if ((rc = tmp.get(c, &part, (size_t)ppls_robust_blocks(n) * PPLS_ROBUST_SUMS))) return rc;
-  if ((rc = tmp.get(c, &sums, (size_t)PPLS_ROBUST_SUMS))) return rc;
-  if (c->rb_len < n || !c->rb_w || !c->rb_d2) {
-    c->rb_kept = false;
-    c->rb_len = 0;
-    if ((rc = dalloc(c, &c->rb_w, (size_t)std::max<int64_t>(n, 1)))) return rc;
-    if ((rc = dalloc(c, &c->rb_d2, (size_t)std::max<int64_t>(n, 1)))) return rc;
-    c->rb_len = std::max<int64_t>(n, 1);
-  }
-  if (n > 0 && (rc = rowdiag_device(c, tmp, th, r, h, f, nullptr, n, false, &res, &dmu))) return rc;
-  c->rb_kept = false;   // from here the kept arrays are overwritten
-  const double P = (double)(c->p + c->q);
-  const int grid = c->rb_grid > 0 ? c->rb_grid : ppls_robust_grid(n, c->num_cus);
-  HIPCHK(c, ppls_launch_robust_weights(res, res ? res + n : nullptr, res ? res + 2 * n : nullptr, n, f.sE2, f.sF2, &nus, m, keep,
-                                       P, c->rb_w, c->rb_d2, part, sums, grid, c->stream));
-  if ((rc = allreduce(c, sums, (size_t)PPLS_ROBUST_SUMS))) return rc;
-  double hs[PPLS_ROBUST_SUMS];
-  HIPCHK(c, hipMemcpyAsync(hs, sums, sizeof hs, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const double N = (double)c->n_total;
-  for (int j = 0; j < m; ++j) {
-    const double v = nu[j];
-    const double cst = std::lgamma(0.5 * (v + P)) - std::lgamma(0.5 * v) - 0.5 * P * std::log(v * 3.141592653589793);
-    loglik_t[j] = (N * cst - 0.5 * N * f.logdet) - 0.5 * (v + P) * hs[j];
-  }
-  if (sum_w) *sum_w = hs[PPLS_ROBUST_MAXNU];
-  c->rb_kept = true;
-  return PPLS_OK;
+  return robust_weights_run(c, nu, m, keep, loglik_t, sum_w, f.sE2, f.sF2, f.logdet, [&](CvScratch& tmp, int64_t n, double** res) {
+    double* dmu = nullptr;
+    return rowdiag_device(c, tmp, th, r, h, f, nullptr, n, false, res, &dmu);
+  });
 }
 
 int ppls_robust_get(ppls_ctx* c, double* w, double* d2) {
@@ -8975,6 +9001,300 @@ int ppls_po2_cv_stream(ppls_ctx* c, int ncand, const int* r, const int* rx, cons
   const int rs = fold_select(c, -1);
   if (rc) c->err = err;
   return rc ? rc : rs;
+}
+
+}  // extern "C"
+
+// ============================================================================ PO2PLS row diagnostics
+// Per row under a PO2PLS fit: the orthogonal distances to the planes of [W Wo] and [C Co], the in-plane score
+// distance, the log-density and the posterior means (ppls_po2_rowdiag.hip).  The loadings need not be
+// orthonormal: the host factors them (Householder QR, R's diagonal positive) and the kernel works in the
+// orthonormal bases; the k x k covariance of the scores is dense.  The weights of the t model follow from the
+// same three arrays by §24's kernel.
+namespace {
+
+struct Po2RowFit {
+  std::vector<double> Qx, Qy, tab;   // p x kx, q x ky, PPLS_PO2_ROWDIAG_TAB
+  double *dQx = nullptr, *dQy = nullptr, *dtab = nullptr;
+  RowDiagFit f;   // sE2, sF2, cst, logdet (its device pointers are not used)
+};
+
+// [A | Ao] = Q R by Householder QR: Q (n x c, orthonormal columns), R (c x c column-major, upper, diagonal
+// positive).  false: a pivot at or below §26's rule, R_kk^2 <= 64 c u ||column k||^2 (rank deficient).
+bool po2_row_qr(const double* A, int ca, const double* Ao, int co, int n, std::vector<double>& Q, double* R) {
+  const int c = ca + co;
+  std::vector<double> G((size_t)n * c), floor2(c);
+  for (int j = 0; j < c; ++j) {
+    const double* src = j < ca ? A + (size_t)j * n : Ao + (size_t)(j - ca) * n;
+    std::copy(src, src + n, &G[(size_t)j * n]);
+    floor2[j] = hdot(src, src, n) * (64.0 * c * 1.1102230246251565e-16);
+  }
+  if (host_householder(G.data(), n, c, floor2.data(), Q, R) >= 0) return false;
+  for (int k = 0; k < c; ++k)
+    if (!std::isfinite(R[(size_t)k * c + k])) return false;   // |R_kk| is the pivot column's norm
+  for (int k = 0; k < c; ++k)
+    if (R[(size_t)k * c + k] < 0.0) {   // R's diagonal positive: row k of R and column k of Q change sign
+      for (int j = k; j < c; ++j) R[(size_t)j * c + k] = -R[(size_t)j * c + k];
+      for (int i = 0; i < n; ++i) Q[(size_t)k * n + i] = -Q[(size_t)k * n + i];
+    }
+  return true;
+}
+
+// Everything the PO2 row entries refuse about the fit, and the host algebra of §29, before any device work.
+int po2_row_check_fit(ppls_ctx* c, const ppls_po2_theta* th, int r, int rx, int ry, Po2Shape& s, Po2RowFit& f) {
+  int rc;
+  const int p = c->p, q = c->q;
+  if ((rc = po2_shape(c, r, rx, ry, p, q, &s)) || (rc = po2_check_theta(c, th, s, p, q))) return rc;
+  const int kx = s.kx, k = s.k;
+  std::vector<double> R((size_t)k * k, 0.0), Rx((size_t)kx * kx), Ry((size_t)s.ky * s.ky);
+  if (!po2_row_qr(th->W, r, th->Wo, rx, p, f.Qx, Rx.data())) return fail(c, PPLS_E_ARG, "PO2PLS theta: [W Wo] is rank deficient");
+  if (!po2_row_qr(th->C, r, th->Co, ry, q, f.Qy, Ry.data())) return fail(c, PPLS_E_ARG, "PO2PLS theta: [C Co] is rank deficient");
+  auto at = [k](std::vector<double>& M, int i, int j) -> double& { return M[(size_t)j * k + i]; };
+  for (int j = 0; j < kx; ++j)
+    for (int i = 0; i <= j; ++i) at(R, i, j) = Rx[(size_t)j * kx + i];
+  for (int j = 0; j < s.ky; ++j)
+    for (int i = 0; i <= j; ++i) at(R, kx + i, kx + j) = Ry[(size_t)j * s.ky + i];
+  // Sigma_z of z = (t, to | u, uo)
+  std::vector<double> Sz((size_t)k * k, 0.0), T1((size_t)k * k, 0.0), Sc((size_t)k * k, 0.0);
+  const double sE2 = th->sigE * th->sigE, sF2 = th->sigF * th->sigF, sH2 = th->sigH * th->sigH;
+  for (int j = 0; j < r; ++j) {
+    const double t2 = th->sigT[j] * th->sigT[j], b = th->B[j];
+    at(Sz, j, j) = t2;
+    at(Sz, j, kx + j) = at(Sz, kx + j, j) = t2 * b;
+    at(Sz, kx + j, kx + j) = t2 * b * b + sH2;
+  }
+  for (int j = 0; j < rx; ++j) at(Sz, r + j, r + j) = th->sigTo[j] * th->sigTo[j];
+  for (int j = 0; j < ry; ++j) at(Sz, kx + r + j, kx + r + j) = th->sigUo[j] * th->sigUo[j];
+  // T1 = R Sigma_z; Sigma_c = T1 R' + diag(sE2 I, sF2 I), its lower triangle mirrored
+  for (int j = 0; j < k; ++j)
+    for (int i = 0; i < k; ++i) {
+      double a = 0.0;
+      for (int m = i; m < k; ++m) a += at(R, i, m) * at(Sz, m, j);
+      at(T1, i, j) = a;
+    }
+  for (int j = 0; j < k; ++j)
+    for (int i = j; i < k; ++i) {
+      double a = 0.0;
+      for (int m = j; m < k; ++m) a += at(T1, i, m) * at(R, j, m);
+      if (i == j) a += i < kx ? sE2 : sF2;
+      at(Sc, i, j) = at(Sc, j, i) = a;
+    }
+  // Sigma_c^-1 = Uc'Uc with Uc upper: the lower Cholesky factor of Sigma_c with its indices reversed, inverted
+  std::vector<double> Lr((size_t)k * k), Li((size_t)k * k, 0.0), Uc((size_t)k * k, 0.0), UT((size_t)k * k, 0.0);
+  for (int j = 0; j < k; ++j)
+    for (int i = 0; i < k; ++i) at(Lr, i, j) = at(Sc, k - 1 - i, k - 1 - j);
+  if (!po2_host_chol(Lr, k)) return fail(c, PPLS_E_ARG, "PO2PLS theta: the covariance of the scores is not positive definite");
+  double logdet_c = 0.0;
+  for (int j = 0; j < k; ++j) {
+    logdet_c += 2.0 * std::log(at(Lr, j, j));
+    at(Li, j, j) = 1.0 / at(Lr, j, j);
+    for (int i = j + 1; i < k; ++i) {
+      double a = 0.0;
+      for (int m = j; m < i; ++m) a += at(Lr, i, m) * at(Li, m, j);
+      at(Li, i, j) = -a / at(Lr, i, i);
+    }
+  }
+  for (int j = 0; j < k; ++j)
+    for (int i = 0; i <= j; ++i) at(Uc, i, j) = at(Li, k - 1 - i, k - 1 - j);
+  // Kmu = R K = Sigma_c^-1 R Sigma_z = Uc' (Uc T1): row j belongs to score j, column i to latent i
+  for (int j = 0; j < k; ++j)
+    for (int i = 0; i < k; ++i) {
+      double a = 0.0;
+      for (int m = i; m < k; ++m) a += at(Uc, i, m) * at(T1, m, j);
+      at(UT, i, j) = a;
+    }
+  f.tab.assign(PPLS_PO2_ROWDIAG_TAB, 0.0);
+  bool ok = std::isfinite(logdet_c);
+  for (int j = 0; j < k; ++j)
+    for (int i = 0; i < k; ++i) {
+      double a = 0.0;
+      for (int m = 0; m <= j; ++m) a += at(Uc, m, j) * at(UT, m, i);
+      f.tab[(size_t)j * 64 + i] = at(Uc, i, j);
+      f.tab[(size_t)j * 64 + 32 + i] = a;
+      ok = ok && std::isfinite(a) && std::isfinite(at(Uc, i, j));
+    }
+  if (!ok) return fail(c, PPLS_E_ARG, "PO2PLS theta: the covariance of the scores is not positive definite");
+  f.f.sE2 = sE2;
+  f.f.sF2 = sF2;
+  f.f.logdet = ((double)(p - kx) * std::log(sE2) + (double)(q - s.ky) * std::log(sF2)) + logdet_c;
+  f.f.cst = -0.5 * ((double)(p + q) * std::log(6.283185307179586) + f.f.logdet);
+  return PPLS_OK;
+}
+
+int po2_row_upload_fit(ppls_ctx* c, CvScratch& tmp, const Po2Shape& s, Po2RowFit& f) {
+  int rc;
+  if ((rc = cv_upload_coef(c, tmp, f.Qx.data(), c->p, s.kx, &f.dQx))) return rc;
+  if ((rc = cv_upload_coef(c, tmp, f.Qy.data(), c->q, s.ky, &f.dQy))) return rc;
+  return cv_upload_coef(c, tmp, f.tab.data(), PPLS_PO2_ROWDIAG_TAB, 1, &f.dtab);
+}
+
+// The device stage on the resident rows, queued on the context stream with no copy-out, as rowdiag_device:
+// res = [odx2 | ody2 | sd2] (nrows each) and, with mu, dmu (nrows x k); both live in tmp.
+int po2_row_device(ppls_ctx* c, CvScratch& tmp, const Po2Shape& s, Po2RowFit& f, const int64_t* d_rows, int64_t nrows, bool mu,
+                   double** res_out, double** dmu_out) {
+  int rc;
+  if ((rc = po2_row_upload_fit(c, tmp, s, f))) return rc;
+  double *res = nullptr, *dmu = nullptr;
+  if ((rc = tmp.get(c, &res, (size_t)3 * nrows))) return rc;
+  if (mu && (rc = tmp.get(c, &dmu, (size_t)nrows * s.k))) return rc;
+  HIPCHK(c, ppls_launch_po2_rowdiag(c->X, c->ldx, c->p, c->Y, c->ldy, c->q, c->dtype, d_rows, nrows, f.dQx, s.kx, f.dQy, s.ky,
+                                    f.dtab, res, res + nrows, res + 2 * nrows, dmu, nrows,
+                                    ppls_po2_rowdiag_grid(nrows, c->p, c->q, c->dtype, s.kx, s.ky, c->num_cus), c->stream));
+  *res_out = res;
+  *dmu_out = dmu;
+  return PPLS_OK;
+}
+
+// rowdiag_collect with the k columns of mu in the place of mu_T.
+int po2_row_collect(ppls_ctx* c, const Po2RowFit& f, const double* dres, const double* dmu, int64_t count, int k, int64_t at,
+                    int64_t n, ppls_po2_row_diag* out) {
+  ppls_row_diag o = {out->odx2, out->ody2, out->sd2, out->d2, out->loglik, out->mu, nullptr};
+  return rowdiag_collect(c, f.f, dres, dmu, count, k, at, n, &o);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ppls_po2_row_diagnostics(ppls_ctx* c, const ppls_po2_theta* th, int r, int rx, int ry, const int64_t* rows, int64_t nrows,
+                             ppls_po2_row_diag* out) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
+  if (!out) return fail(c, PPLS_E_ARG, "NULL output");
+  Po2Shape s;
+  Po2RowFit f;
+  int rc;
+  if ((rc = po2_row_check_fit(c, th, r, rx, ry, s, f))) return rc;
+  if (!rows) nrows = c->n_local;   // all local rows
+  if (nrows < 0) return fail(c, PPLS_E_ARG, "row list: %lld rows", (long long)nrows);
+  for (int64_t i = 0; rows && i < nrows; ++i)   // any order, repeats allowed: the kernel only reads
+    if (rows[i] < 0 || rows[i] >= c->n_local)
+      return fail(c, PPLS_E_ARG, "row index %lld (entry %lld) outside [0, %lld)", (long long)rows[i], (long long)i,
+                  (long long)c->n_local);
+  if (nrows == 0) return PPLS_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  CvScratch tmp;
+  int64_t* d_rows = nullptr;
+  if (rows && (rc = cv_upload_rows(c, tmp, rows, nrows, &d_rows))) return rc;
+  double *res = nullptr, *dmu = nullptr;
+  if ((rc = po2_row_device(c, tmp, s, f, d_rows, nrows, out->mu != nullptr, &res, &dmu))) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return po2_row_collect(c, f, res, dmu, nrows, s.k, 0, nrows, out);
+}
+
+int ppls_po2_robust_weights(ppls_ctx* c, const ppls_po2_theta* th, int r, int rx, int ry, const double* nu, int m, int keep,
+                            double* loglik_t, double* sum_w) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
+  if (!nu || !loglik_t) return fail(c, PPLS_E_ARG, "NULL argument");
+  Po2Shape s;
+  Po2RowFit f;
+  int rc;
+  if ((rc = po2_row_check_fit(c, th, r, rx, ry, s, f))) return rc;
+  return robust_weights_run(c, nu, m, keep, loglik_t, sum_w, f.f.sE2, f.f.sF2, f.f.logdet,
+                            [&](CvScratch& tmp, int64_t n, double** res) {
+                              double* dmu = nullptr;
+                              return po2_row_device(c, tmp, s, f, nullptr, n, false, res, &dmu);
+                            });
+}
+
+int ppls_po2_row_diagnostics_new(ppls_ctx* c, const ppls_po2_theta* th, int r, int rx, int ry, const double* X, const double* Y,
+                                 int64_t n, int layout, ppls_po2_row_diag* out) {
+  if (!c) return PPLS_E_ARG;
+  if (c->p < 1 || c->q < 1) return fail(c, PPLS_E_STATE, "no data shape: load data (p, q) first");
+  if (!out) return fail(c, PPLS_E_ARG, "NULL output");
+  Po2Shape s;
+  Po2RowFit f;
+  int rc;
+  if ((rc = po2_row_check_fit(c, th, r, rx, ry, s, f))) return rc;
+  if (layout != PPLS_LAYOUT_COLMAJOR && layout != PPLS_LAYOUT_ROWMAJOR)
+    return fail(c, PPLS_E_ARG, "layout must be 0 (column-major) or 1 (row-major)");
+  if (n < 0 || (n > 0 && (!X || !Y))) return fail(c, PPLS_E_ARG, "NULL X or Y with %lld rows", (long long)n);
+  if (n == 0) return PPLS_OK;
+  const int p = c->p, q = c->q;
+  for (int blk = 0; blk < 2; ++blk) {   // the whole call is refused, as ppls_set_data refuses such data
+    const double* D = blk ? Y : X;
+    const size_t len = (size_t)n * (blk ? q : p);
+    for (size_t e = 0; e < len; ++e)
+      if (!std::isfinite(D[e])) return fail(c, PPLS_E_ARG, "%c contains NaN or Inf", blk ? 'Y' : 'X');
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  CvScratch tmp;
+  if ((rc = po2_row_upload_fit(c, tmp, s, f))) return rc;
+  // row blocks through a staging buffer (~64 MB of rows at a time), always staged in fp64
+  const int ldx = (p + 1) & ~1, ldy = (q + 1) & ~1;
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(64 << 20) / (8LL * (ldx + ldy))));
+  double *inX = nullptr, *inY = nullptr, *cm = nullptr, *res = nullptr, *dmu = nullptr;
+  if ((rc = tmp.get(c, &inX, (size_t)chunk * ldx))) return rc;
+  if ((rc = tmp.get(c, &inY, (size_t)chunk * ldy))) return rc;
+  if (layout == PPLS_LAYOUT_COLMAJOR && (rc = tmp.get(c, &cm, (size_t)chunk * std::max(p, q)))) return rc;
+  if ((rc = tmp.get(c, &res, (size_t)3 * chunk))) return rc;
+  if (out->mu && (rc = tmp.get(c, &dmu, (size_t)chunk * s.k))) return rc;
+  HIPCHK(c, hipMemsetAsync(inX, 0, sizeof(double) * chunk * ldx, c->stream));
+  HIPCHK(c, hipMemsetAsync(inY, 0, sizeof(double) * chunk * ldy, c->stream));
+  for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+    const int64_t nc = std::min(chunk, n - r0);
+    for (int blk = 0; blk < 2; ++blk) {
+      const double* D = blk ? Y : X;
+      double* in = blk ? inY : inX;
+      const int cols = blk ? q : p, ld = blk ? ldy : ldx;
+      if (layout == PPLS_LAYOUT_ROWMAJOR) {
+        HIPCHK(c, hipMemcpy2DAsync(in, sizeof(double) * ld, D + r0 * cols, sizeof(double) * cols, sizeof(double) * cols, nc,
+                                   hipMemcpyHostToDevice, c->stream));
+      } else {
+        HIPCHK(c, hipMemcpy2DAsync(cm, sizeof(double) * nc, D + r0, sizeof(double) * n, sizeof(double) * nc, cols,
+                                   hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, ppls_launch_to_rowmajor(cm, nc, cols, ld, in, c->stream));
+      }
+    }
+    HIPCHK(c, ppls_launch_po2_rowdiag(inX, ldx, p, inY, ldy, q, 0, nullptr, nc, f.dQx, s.kx, f.dQy, s.ky, f.dtab, res, res + nc,
+                                      res + 2 * nc, dmu, nc, ppls_po2_rowdiag_grid(nc, p, q, 0, s.kx, s.ky, c->num_cus),
+                                      c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = po2_row_collect(c, f, res, dmu, nc, s.k, r0, n, out))) return rc;
+  }
+  return PPLS_OK;
+}
+
+int ppls_po2_rowdiag_info(int p, int q, int f32, int r, int rx, int ry, int* tile_x, int* tile_y, int* rows_per_wave) {
+  if (r < 1 || rx < 0 || ry < 0 || r + rx > PPLS_RMAX || r + ry > PPLS_RMAX || r + rx > p || r + ry > q) return PPLS_E_ARG;
+  if (tile_x) *tile_x = ppls_po2_rowdiag_tile(r + rx);
+  if (tile_y) *tile_y = ppls_po2_rowdiag_tile(r + ry);
+  if (rows_per_wave) *rows_per_wave = ppls_po2_rowdiag_rows_per_wave(p, q, f32, r + rx, r + ry);
+  return PPLS_OK;
+}
+
+int ppls_po2_rowdiag_timing(ppls_ctx* c, const ppls_po2_theta* th, int r, int rx, int ry, int reps, double* ms) {
+  if (!c) return PPLS_E_ARG;
+  if (!c->have_data) return fail(c, PPLS_E_STATE, "no data");
+  NEED_ROWS(c);
+  if (!ms || reps < 1) return fail(c, PPLS_E_ARG, "ms must be given with reps >= 1");
+  Po2Shape s;
+  Po2RowFit f;
+  int rc;
+  if ((rc = po2_row_check_fit(c, th, r, rx, ry, s, f))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  CvScratch tmp;
+  if ((rc = po2_row_upload_fit(c, tmp, s, f))) return rc;
+  const int64_t n = c->n_local;
+  double *res = nullptr, *dmu = nullptr;
+  if ((rc = tmp.get(c, &res, (size_t)3 * std::max<int64_t>(n, 1)))) return rc;
+  if ((rc = tmp.get(c, &dmu, (size_t)std::max<int64_t>(n, 1) * s.k))) return rc;
+  const int grid = ppls_po2_rowdiag_grid(n, c->p, c->q, c->dtype, s.kx, s.ky, c->num_cus);
+  for (int v = 0; v < 2; ++v) {
+    CvEvents ev;
+    for (int it = 0; it <= reps; ++it) {   // one untimed launch first
+      if (it == 1) HIPCHK(c, ev.begin(c->stream));
+      HIPCHK(c, ppls_launch_po2_rowdiag(c->X, c->ldx, c->p, c->Y, c->ldy, c->q, c->dtype, nullptr, n, f.dQx, s.kx, f.dQy, s.ky,
+                                        f.dtab, res, res + n, res + 2 * n, v ? dmu : nullptr, n, grid, c->stream));
+    }
+    HIPCHK(c, ev.end(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ms[v] = ev.ms() / reps;
+  }
+  return PPLS_OK;
 }
 
 }  // extern "C"
